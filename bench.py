@@ -12,7 +12,7 @@ Steps rotate over --batches (default 4) distinct query batches, all resident bef
 
 N > 1 (weak scaling: every GPU holds a full index replica and gets its own batches; no data-path collective):
   --mode procs (default)  one process per GPU under torch.distributed.run.  Started WITHOUT a launcher
-                          (`python bench.py --gpus 8`, no WORLD_SIZE) the script re-executes itself under
+                          (`python bench.py --gpus 8`, no WORLD_SIZE) the script runs itself as a child under
                           `python -m torch.distributed.run --nproc-per-node N` — it never measures one GPU and
                           calls it N.  Rank 0 then also measures the single-process replica path below and
                           reports it as `replicas_mode`, beside the process-per-GPU number.
@@ -102,9 +102,43 @@ def parse_args(argv=None):
                     help="roofline.traffic: live = a rocprofv3 --pmc FETCH_SIZE pass over this same workload in a child process "
                          "(after the timed region; N=1 only); file = the committed measurement in profiles/traffic.json; "
                          "auto = live when rocprofv3 is there, else file")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (rank 0's result rows) as DIR/<name>.npy in "
+                         "float64, at most 64 MB in all (a fixed, seeded sample of the rows above that): two builds can be compared output for output")
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.mode == "replicas":
+        ap.error("--dump-outputs: not available with --mode replicas")
     args.explicit_workload = any(getattr(args, k) is not None for k in WORKLOAD_KEYS)
     return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(directory, ids, counts, scores=None, log=None):
+    """Result rows of one call -> `directory`/{ids,scores,counts,rows}.npy, float64.  Slots past a row's result count carry no result
+    (ids -1, scores 0), so the files hold what a caller reads and nothing a kernel may leave in the unused slots.  `rows` = the query
+    indices written: all of them, or a fixed sample (seed 0, ascending) when the rows would take more than DUMP_LIMIT_BYTES."""
+    import numpy as np
+    n_q, width = ids.shape
+    valid = np.arange(width)[None, :] < np.minimum(counts, width).astype(np.int64)[:, None]
+    row_bytes = 8 * (width * (1 if scores is None else 2) + 2)
+    if n_q * row_bytes > DUMP_LIMIT_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(n_q, DUMP_LIMIT_BYTES // row_bytes, replace=False))
+    else:
+        rows = np.arange(n_q)
+    out = {"rows": rows.astype(np.float64),
+           "ids": np.where(valid, ids.view(np.uint32).astype(np.float64), -1.0)[rows],
+           "counts": counts.view(np.uint32).astype(np.float64)[rows]}
+    if scores is not None:
+        out["scores"] = np.where(valid, scores.astype(np.float64), 0.0)[rows]
+    os.makedirs(directory, exist_ok=True)
+    for name, arr in out.items():
+        np.save(os.path.join(directory, name + ".npy"), arr)
+    if log:
+        log("outputs of the last timed step -> %s: %s" % (directory, ", ".join("%s %s" % (n, a.shape) for n, a in out.items())))
 
 
 def apply_preset(args, name):
@@ -114,7 +148,10 @@ def apply_preset(args, name):
 
 
 def self_spawn(args):
-    """`python bench.py --gpus N` with N > 1 and no launcher: become `python -m torch.distributed.run ... bench.py <same args>`."""
+    """`python bench.py --gpus N` with N > 1 and no launcher: run `python -m torch.distributed.run ... bench.py <same args>` as a
+    child and exit with its status.  (A child, not exec: this process may already hold the GPU open through torch, and replacing
+    such a process's program is not safe on every driver.)"""
+    import subprocess
     import torch
     have = torch.cuda.device_count() if torch.cuda.is_available() else 0
     if have < args.gpus and os.environ.get("SG_BENCH_SINGLE_DEVICE") != "1":
@@ -127,9 +164,10 @@ def self_spawn(args):
             port = str(s.getsockname()[1])
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus),
            "--master-addr", "127.0.0.1", "--master-port", port, os.path.abspath(__file__)] + sys.argv[1:]
-    print("[bench] --gpus %d without a launcher: re-executing as %s" % (args.gpus, " ".join(cmd[1:8])), file=sys.stderr, flush=True)
+    print("[bench] --gpus %d without a launcher: running %s" % (args.gpus, " ".join(cmd[1:8])), file=sys.stderr, flush=True)
     sys.stdout.flush()
-    os.execv(sys.executable, cmd)
+    rc = subprocess.run(cmd).returncode
+    raise SystemExit(128 - rc if rc < 0 else rc)          # (a child killed by signal N: 128 + N, as a shell reports it)
 
 
 class Env:
@@ -227,8 +265,10 @@ def cpu_quota():
     return quota, hw
 
 
-def measure(env, args, w, steps, warmup, cpu_baseline=True, host_rate=True, traffic_mode="auto", replicas_leg=False, parity_rows=None):
-    """One workload `w` (dict of WORKLOAD_KEYS + variant) on this rank's GPU -> the record (rank 0) or None."""
+def measure(env, args, w, steps, warmup, cpu_baseline=True, host_rate=True, traffic_mode="auto", replicas_leg=False, parity_rows=None,
+            dump_dir=None):
+    """One workload `w` (dict of WORKLOAD_KEYS + variant) on this rank's GPU -> the record (rank 0) or None.  `dump_dir`: where
+    rank 0 writes the rows of the last timed step (dump_outputs)."""
     import numpy as np
     torch, dist = env.torch, env.dist
     from suggest_amd import IndexDescription, NGramIndex, synth
@@ -351,6 +391,9 @@ def measure(env, args, w, steps, warmup, cpu_baseline=True, host_rate=True, traf
     ids = [x.cpu().numpy().view(np.uint32) for x in d_ids]
     sc = [x.cpu().numpy() for x in d_sc]
     cnt = [x.cpu().numpy().view(np.uint32) for x in d_cnt]
+    if dump_dir and rank == 0:
+        b_last = (steps - 1) % n_b                       # (each batch has its own result buffers: nothing after the timed region overwrote them)
+        dump_outputs(dump_dir, ids[b_last], cnt[b_last], sc[b_last], log=log)
 
     # ---- N > 1: every rank holds a sample of ITS OWN rows (its own batch, its own GPU, its own replica of the index) against the
     #      CPU oracle, and the ranks the RCCL group really spans are listed: a run nobody can watch checks itself ----
@@ -723,7 +766,7 @@ def main():
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
     if args.mode == "procs" and args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        self_spawn(args)            # does not return
+        self_spawn(args)            # exits with the launcher's status
     env = Env(args)
     import numpy as np  # noqa: F401
 
@@ -740,7 +783,7 @@ def main():
         if env.world > 1:
             raise SystemExit("--sub-configs is an N=1 option")
     rec = measure(env, args, w, args.steps, args.warmup, cpu_baseline=not args.no_cpu_baseline, traffic_mode=args.traffic,
-                  replicas_leg=env.world > 1, host_rate=not args.no_host_rate)
+                  replicas_leg=env.world > 1, host_rate=not args.no_host_rate, dump_dir=args.dump_outputs)
     sub_recs = {}
     for name in subs:       # cfg3 and cfg4 first: they share the headline's dictionary
         t0 = time.time()
@@ -752,6 +795,7 @@ def main():
             sa = argparse.Namespace(**vars(args))
             sa.dict_size = sa.queries = sa.topk = sa.similarity = None
             sa.steps, sa.warmup, sa.cpu_sample = max(5, min(args.steps, 10)), 2, 4096
+            sa.dump_outputs = None          # (the outputs written are the main workload's)
             try:
                 r5 = bench_spell.run(sa, env=env)
             except (Exception, SystemExit) as exc:      # a failed sub-record must not lose the main line

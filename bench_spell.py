@@ -119,6 +119,10 @@ def run(args, env=None):
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:      # the rows of the last timed step, before anything else runs
+        import bench
+        b_last = (args.steps - 1) % n_b
+        bench.dump_outputs(args.dump_outputs, d_ids[b_last].cpu().numpy(), d_cnt[b_last].cpu().numpy(), log=log)
     for b in range(n_b):
         step(b)
     torch.cuda.synchronize(dev)
