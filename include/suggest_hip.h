@@ -329,7 +329,10 @@ int sg_debug_tune_index(sg_index* index, double out_stats[2], int32_t out[6]);
 int sg_debug_replica_devices(sg_index* index, uint32_t replica, int32_t out[8]);
 
 /* Sets a tuning knob of the index (names and ranges of the SG_* environment variables in DESIGN.md: SG_LOG2_CNT, SG_T_FLOOR,
- * SG_FILTER_LEVEL, SG_TIGHTEN, SG_ROOMY, SG_ORDER, SG_PRETOK, SG_SPLIT_CHUNKS, SG_PARTS_CNT_BONUS).  Results never depend on the knobs; for parameter sweeps. */
+ * SG_FILTER_LEVEL, SG_TIGHTEN, SG_ROOMY, SG_ORDER, SG_PRETOK, SG_SPLIT_CHUNKS, SG_PARTS_CNT_BONUS; the pipeline's SG_PIPE,
+ * SG_PIPE_SUB, SG_PIPE_CAND_CAP, SG_PIPE_WIDE, SG_PLAN2, SG_PIPE_SHAPE_BIAS).  SG_PIPE_NW, SG_PIPE_LOG2_CNT and SG_PIPE_DT_BYTES
+ * freeze the stream workgroup's shape for every launch; SG_PIPE_SHAPE_AUTO = 1 hands it back to the per-launch choice.
+ * Results never depend on the knobs; for parameter sweeps. */
 int sg_index_tune(sg_index* index, const char* knob, int value);
 
 /* Tokens of `text` as the index sees them, one packed 64-bit term key each (DESIGN.md §Term keys);

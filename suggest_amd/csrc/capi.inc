@@ -27,6 +27,76 @@ using namespace sg;
   catch (const std::exception& e_) { set_error(std::string("internal error: ") + e_.what()); return on_fail(SG_E_INVALID); }
 #define SG_RC(x) (x)
 
+// ---- the launch controllers (plan_launch): each reads the words of the replica's statistics block it needs from the host's copy,
+// and keeps what it saw last ----
+
+// [SG_TIGHTEN=2] The tightening instantiation for fuzzy launches: on while more than 30 % of the queries sampled since the last look
+// (32 at least) ended with a full top-k, off again below 15 %.  Before the first statistics, on for a similarity below 0.3: it admits
+// most of the window — over a dictionary of near-duplicates a million candidates per query unless the thresholds follow the top-k;
+// the wrong guess costs a few per cent.
+struct TightenCtl {
+  std::atomic<uint32_t> seen_full{0}, seen_total{0};
+  std::atomic<bool> on{false};
+  bool now(const volatile uint32_t* h, double similarity) const {   // the decision as it stands (h may be null)
+    return on.load(std::memory_order_relaxed) || (similarity < 0.3 && h && h[SG_STAT_SAMPLED] == 0u);
+  }
+  bool step(const volatile uint32_t* h, double similarity) {
+    const uint32_t full = h[SG_STAT_FULL], total = h[SG_STAT_SAMPLED];
+    const uint32_t d_total = total - seen_total.load(std::memory_order_relaxed), d_full = full - seen_full.load(std::memory_order_relaxed);
+    if (d_total >= 32u && d_full <= d_total) {
+      seen_total.store(total, std::memory_order_relaxed); seen_full.store(full, std::memory_order_relaxed);
+      if (d_full * 100u > d_total * 30u) on.store(true, std::memory_order_relaxed);
+      else if (d_full * 100u < d_total * 15u) on.store(false, std::memory_order_relaxed);
+    }
+    return on.load(std::memory_order_relaxed) || (total == 0u && similarity < 0.3);
+  }
+};
+
+// [r5, SG_PIPE=2] The pipeline's run-time guard: a replica that saw more than a fifth of its recent pipeline queries (4 096 at least
+// since the last look) come back to the fused kernel — dictionaries of near-duplicates: hundreds of flagged postings per query;
+// documents that repeat terms — keeps its next 64 launches off the pipeline, then tries again.
+struct PipeGuard {
+  std::atomic<uint64_t> seen_queries{0};
+  std::atomic<uint32_t> seen_fb{0}, off_launches{0};
+  bool holding() const { return off_launches.load(std::memory_order_relaxed) != 0u; }
+  // q_now: the queries sent through the pipeline so far; true: this launch stays off it
+  bool step(const volatile uint32_t* h, uint64_t q_now) {
+    const uint32_t fb = h[SG_STAT_UNPLANNED] + h[SG_STAT_OVERFLOW] + h[SG_STAT_REPEATS];
+    const uint64_t q_seen = seen_queries.load(std::memory_order_relaxed);
+    const uint32_t d_fb = fb - seen_fb.load(std::memory_order_relaxed);
+    if (d_fb && q_now - q_seen >= 4096u) {
+      seen_fb.store(fb, std::memory_order_relaxed); seen_queries.store(q_now, std::memory_order_relaxed);
+      if ((uint64_t)d_fb * 5u > q_now - q_seen) off_launches.store(64u, std::memory_order_relaxed);
+    }
+    const uint32_t off = off_launches.load(std::memory_order_relaxed);
+    if (off) off_launches.store(off - 1u, std::memory_order_relaxed);
+    return off != 0u;
+  }
+};
+
+// [r6] The lightest stream-workgroup shape this replica's pipeline launches may take: raised past the latest launch's shape when
+// more than a hundredth of a window's queries (4 096 at least) came back unplanned.  `last`: the latest launch's shape (0 .. 2, 3 =
+// the knobs' own; sg_index_pipe_volumes).
+struct ShapeFloor {
+  std::atomic<uint32_t> floor{0}, last{2}, seen_unplanned{0};
+  std::atomic<uint64_t> seen_queries{0};
+  // shape: the model's; returns the one this launch takes.  h may be null: no new statistics
+  uint32_t step(const volatile uint32_t* h, uint64_t q_now, uint32_t shape) {
+    if (h) {
+      const uint32_t unplanned = h[SG_STAT_UNPLANNED];
+      const uint64_t q_seen = seen_queries.load(std::memory_order_relaxed);
+      if (q_now - q_seen >= 4096u) {
+        const uint32_t d_un = unplanned - seen_unplanned.load(std::memory_order_relaxed), l = last.load(std::memory_order_relaxed);
+        seen_unplanned.store(unplanned, std::memory_order_relaxed); seen_queries.store(q_now, std::memory_order_relaxed);
+        if ((uint64_t)d_un * 100u > q_now - q_seen && l < 2u && l >= floor.load(std::memory_order_relaxed)) floor.store(l + 1u, std::memory_order_relaxed);
+      }
+    }
+    shape = std::max(shape, floor.load(std::memory_order_relaxed));
+    last.store(shape, std::memory_order_relaxed);
+    return shape;
+  }
+};
+
 // One copy of the index in the HBM of one GPU.  Immutable once published in sg_index::replicas.
 struct Replica {
   int device = -1;
@@ -39,22 +109,17 @@ struct Replica {
   const uint32_t* x_of = nullptr;      // [n_docs] docID -> the packed store's number (packed_store.inc; introspection only)
   uint64_t packed_chunks = 0;          // 16-byte chunks of the packed store
   int n_cus = 256;                     // compute units of the device (the persistent launches' grids)
-  // which instantiation the fuzzy launches use (SG_TIGHTEN auto): the kernel counts, for one query in 32, whether its top-k
-  // ended full; every few launches the two counters are copied to pinned memory behind the kernel and the next launch
-  // looks at what has arrived (no synchronisation: a decision that lags a launch or two only costs a few per cent)
+  // the statistics block (StatWord, engine.hip): the kernels count into it, and every few launches a one-thread kernel copies it to
+  // pinned memory behind them, where the next launches' controllers read what has arrived (no synchronisation: a decision that
+  // lags a launch or two only costs a few per cent)
   uint32_t* d_fill = nullptr;
-  uint32_t* h_fill = nullptr;          // pinned + mapped: a one-thread kernel stores the counters into it (h_fill_dev = its device address)
+  uint32_t* h_fill = nullptr;          // pinned + mapped (h_fill_dev = its device address)
   uint32_t* h_fill_dev = nullptr;
-  std::atomic<uint32_t> seen_full{0}, seen_total{0}, seen_results{0}, launches{0};
-  std::atomic<int> tight_now{0}, roomy_now{0};
-  // [r5] the pipeline's run-time guard: queries sent through it and the fallbacks seen when the counters were last looked at; a
-  // replica whose recent queries mostly came back to the fused kernel takes the fused kernel for a while
-  std::atomic<uint64_t> pipe_queries{0}, pipe_seen_queries{0};
-  std::atomic<uint32_t> pipe_seen_fb{0}, pipe_off_launches{0};
-  // [r6] the stream workgroup's shape per launch (pipe_shape, below): the lightest shape this replica's launches may still take
-  // (raised when a lighter one left more than a hundredth of its queries unplanned), the shape of the latest launch
-  std::atomic<uint32_t> pipe_shape_floor{0}, pipe_last_shape{2}, pipe_shape_seen_unplanned{0};
-  std::atomic<uint64_t> pipe_shape_seen_queries{0};
+  std::atomic<uint32_t> launches{0};   // launches that fed the block (every fourth copies it)
+  std::atomic<uint64_t> pipe_queries{0};   // queries sent through the pipeline
+  TightenCtl tighten;
+  PipeGuard pipe_guard;
+  ShapeFloor shape_floor;
   // sg_*_batch_multi and the single-query coalescer drive a replica from threads of their own: a stream and a pinned
   // staging buffer per lane, made on first use
   struct AsyncPool* async_pool = nullptr;   // sg_suggest_submit / sg_ticket_wait: three streams + a ring of slots (made on first use)
@@ -206,15 +271,33 @@ int check_search_args(sg_index* index, uint32_t k, bool need_alpha, double simil
 }
 
 struct LmRanges { const uint64_t* values; const uint32_t *from, *to; };   // device pointers (spellchecker mode)
-// what sg_suggest_batch_from / _tables add to a fuzzy launch: docID-ordered paging (+ the rows' segment / overlap words) and a
-// tabulated metric
-struct LaunchExtra { int by_doc = 0; uint32_t* out_aux = nullptr; const MetricTab* mt = nullptr; };
+
+// One launch as its caller asks for it: device pointers, on `stream`.
+struct LaunchReq {
+  const void* q = nullptr; const void* offs = nullptr; uint32_t n_q = 0;   // query blob and n_q + 1 u64 offsets
+  int metric = 0; double similarity = 0; uint32_t k = 0;
+  int autocomplete = 0;               // 1: prefix search (BatchArgs::autocomplete)
+  bool by_doc = false;                // sg_suggest_batch_from: fuzzy window and thresholds, rows ordered by docID from ac_first on
+  uint32_t ac_first = 0;
+  void* ids = nullptr; void* scores = nullptr; void* counts = nullptr;      // [n_q][k] u32, [n_q][k] f64 (may be null), [n_q] u32
+  hipStream_t stream = nullptr;
+  const LmRanges* lm = nullptr;       // the spellchecker's LM collector (Predict)
+  const uint32_t* sel = nullptr; const uint32_t* sel_n = nullptr;   // the queries to answer (BatchArgs::q_sel / q_sel_n)
+  const uint32_t* len = nullptr;      // query lengths (BatchArgs::q_len)
+  bool no_long_queries = false;       // the caller knows no query passes the wavefront kernel's tables: no long-query launch
+  uint32_t* out_aux = nullptr;        // by_doc: [n_q][k] segment << 16 | overlap (may be null)
+  const MetricTab* mt = nullptr;      // a tabulated metric in place of (metric, similarity)
+  const uint8_t* flag = nullptr;      // only the queries this [n_q] array marks (Predict's fuzzy launch)
+};
 
 // Working memory of a launch (top-k rows above SG_K_LDS, the split-query queue): one grow-only buffer per calling thread
 // and (device, stream), reused by that thread's next launch on the stream — which is ordered behind this one.  No
 // stream-ordered pool: its blocks were seen handed to a second stream while the first still used them (callers on
 // several streams during an index swap, tests/cpp/service_test.cpp).  hipFree waits for the device, so growing or
 // dropping a buffer never pulls it from under a running kernel.
+// A block per tag: one launch holds SCRATCH_ROWS, SCRATCH_LONG_LIST and one of SCRATCH_PRETOK / SCRATCH_PIPE of its stream at
+// once, and Predict's block besides when Predict is the caller — four at most.
+enum ScratchTag { SCRATCH_ROWS = 0, SCRATCH_PREDICT = 1, SCRATCH_LONG_LIST = 2, SCRATCH_PRETOK = 3, SCRATCH_PIPE = 4 };
 struct ScratchSlot { int device; hipStream_t stream; int tag; void* p; size_t cap; };
 inline bool on_main_thread() { return (long)getpid() == (long)syscall(SYS_gettid); }
 // (a thread that ends hands its buffers back; the main thread's are left to process exit, when the HIP runtime may already
@@ -235,14 +318,12 @@ size_t block_capacity(size_t bytes) {
   while (cap < bytes) cap <<= 1;
   return cap;
 }
-// (tag: a caller that itself calls launch() on the stream — Predict's pipeline — keeps a block of its own)
-int stream_scratch(int device, hipStream_t stream, size_t bytes, void** out, int tag = 0) {
+int stream_scratch(int device, hipStream_t stream, size_t bytes, void** out, ScratchTag tag) {
   ScratchSlot* sl = nullptr;
   for (auto& x : t_scratch) if (x.device == device && x.stream == stream && x.tag == tag) sl = &x;
   if (!sl) {
-    // One launch holds up to four blocks of ITS stream at once (tags 0..3: rows / long-query list / Predict's block /
-    // pre-tokenised terms), so a block of the requesting (device, stream) is never the one to go: the oldest block of
-    // ANOTHER stream is (hipFree waits for the device, so nothing running loses its memory).
+    // a block of the requesting (device, stream) is never the one to go: the oldest block of ANOTHER stream is (hipFree waits
+    // for the device, so nothing running loses its memory)
     if (t_scratch.size() >= 16) {
       for (size_t i = 0; i < t_scratch.size(); i++) {
         if (t_scratch[i].device == device && t_scratch[i].stream == stream) continue;
@@ -265,13 +346,32 @@ int stream_scratch(int device, hipStream_t stream, size_t bytes, void** out, int
   return SG_OK;
 }
 
+// A block cut into regions, in order: take() places the next one at the first multiple of `align` bytes behind the last;
+// size() is the block's size (a multiple of 16 bytes).
+struct Carve {
+  size_t off = 0;
+  size_t take(size_t bytes, size_t align = 16) { const size_t at = (off + align - 1) & ~(align - 1); off = at + bytes; return at; }
+  size_t size() const { return (off + 15) & ~(size_t)15; }
+};
+
 // [r6] Whether the three-launch pipeline can run on this replica at all (one predicate for every place that asks): a dictionary
 // above the one-counter-per-document size, a chunk index of 32 bits.  Stores of 2^26 chunks (1 GiB) and more take the stream
 // launch's 8-byte sub-row descriptors (pipe_wide); top-k rows above SG_K_LDS entries live in HBM as the fused kernel's.
 bool pipe_capable(const sg_index* index, const Replica* rep) {
   return index->pipe != 0 && rep->dix.n_docs > (4u << index->log2_cnt) && rep->packed_chunks < (1ull << 32) && index->pipe_sub >= 3 && index->pipe_sub <= 5;
 }
-// [r6] The stream workgroup a launch starts from (launch(), "shape, per launch"): 0 / 1 / 2 = 2 / 4 / 8 wavefronts on 2^11 / 2^12 /
+// the tokeniser as a launch of its own (512 B of scratch per query: a batch of more than 2 M queries — 1 GiB of it — lets the
+// search kernel tokenise itself)
+bool pretok_launch(const sg_index* index, uint32_t n_q) { return index->pre_tokenize && n_q >= (uint32_t)index->pre_tokenize && n_q <= (1u << 21); }
+// [r5] Whether a launch may go through plan -> stream -> verify (pipeline.inc: the plan launch tokenises; the fused kernel runs
+// behind them over the queries they hand back): an ordinary fuzzy batch — top-k by score, no LM collector, no 8-bit gaps, no
+// tightening — large enough for a tokeniser launch of its own, on a replica that can run the pipeline, always (SG_PIPE=1) or
+// where it pays (tune_choice; profiles/r05r_*) while the run-time guard does not hold it off.  launch() adds: no split queries.
+bool pipe_eligible(const sg_index* index, const Replica* rep, const LaunchReq& r, bool tight, bool guard_off) {
+  return pipe_capable(index, rep) && !r.lm && !r.autocomplete && !r.by_doc && !rep->dix.has_g8 && !tight && pretok_launch(index, r.n_q) &&
+         (index->pipe == 1 || (index->pipe_pays && !guard_off));
+}
+// [r6] The stream workgroup a launch starts from (plan_launch): 0 / 1 / 2 = 2 / 4 / 8 wavefronts on 2^11 / 2^12 /
 // 2^13 counters, by the index's expected query volume x the square of the share of a typical query's lists that skipping leaves
 // under the metric and similarity.  One place, so that a test can hold it against the launches it was measured on
 // (tests/test_capi_cpu.py::test_stream_shapes_are_pinned; sg_debug_pipe_shape).
@@ -293,91 +393,40 @@ bool plan2_usable(const sg_index* index, const Replica* rep, int metric) {
 }
 bool pipe_wide(const sg_index* index, const Replica* rep) { return index->pipe_wide || rep->packed_chunks >= (1ull << 26); }
 
-int launch(sg_index* index, Replica* rep, const void* d_q, const void* d_offs, uint32_t n_q, int metric, double similarity, uint32_t k,
-           int autocomplete, void* d_ids, void* d_scores, void* d_counts, hipStream_t stream, const LmRanges* lm = nullptr,
-           const uint32_t* d_sel = nullptr, const uint32_t* d_sel_n = nullptr, const uint32_t* d_len = nullptr, uint32_t ac_first = 0,
-           bool no_long_queries = false, const LaunchExtra* ex = nullptr, const uint8_t* d_flag = nullptr) {
-  if (n_q == 0) return SG_OK;
-  // top-k rows above SG_K_LDS entries live in HBM, k x 12 bytes per query: a batch whose rows would pass 1 GiB goes
-  // through in pieces (the queries are independent)
-  if (k > SG_K_LDS && !d_sel && (size_t)n_q * k * 12 > ((size_t)1 << 30)) {
-    const uint32_t piece = (uint32_t)std::max<size_t>(1, ((size_t)1 << 30) / ((size_t)k * 12));
-    for (uint32_t lo = 0; lo < n_q; lo += piece) {
-      const uint32_t m = std::min(piece, n_q - lo);
-      LmRanges sub{};
-      if (lm) sub = LmRanges{lm->values, lm->from + lo, lm->to + lo};
-      LaunchExtra sub_ex;
-      if (ex) { sub_ex = *ex; if (sub_ex.out_aux) sub_ex.out_aux += (size_t)lo * k; }
-      const int rc = launch(index, rep, d_q, (const uint64_t*)d_offs + lo, m, metric, similarity, k, autocomplete, (uint32_t*)d_ids + (size_t)lo * k,
-                            d_scores ? (double*)d_scores + (size_t)lo * k : nullptr, (uint32_t*)d_counts + lo, stream, lm ? &sub : nullptr, nullptr, nullptr,
-                            d_len ? d_len + lo : nullptr, ac_first, no_long_queries, ex ? &sub_ex : nullptr, d_flag ? d_flag + lo : nullptr);
-      if (rc) return rc;
-    }
-    return SG_OK;
-  }
-  BatchArgs a{};
-  a.ix = rep->dix;
-  a.q_sel = d_sel; a.q_sel_n = d_sel_n;
-  a.long_scratch = rep->long_scratch; a.long_lock = rep->long_lock; a.long_slot_bytes = rep->long_slot_bytes; a.long_max_seg = rep->long_max_seg;
-  a.q_len = d_len;
-  a.ac_first = ac_first;
-  if (ex) {
-    a.out_aux = ex->out_aux;
-    if (ex->mt) { a.mt = *ex->mt; metric = SG_TABLE; }
-    if (ex->by_doc) autocomplete = 2;                    // fuzzy window and thresholds, rows ordered by docID (BatchArgs::autocomplete)
-  }
-  const bool by_doc = autocomplete == 2;
-  if (lm) { a.lm_values = lm->values; a.lm_from = lm->from; a.lm_to = lm->to; }
-  a.q_blob = (const uint8_t*)d_q;
-  a.q_offs = (const uint64_t*)d_offs;
-  a.out_ids = (uint32_t*)d_ids;
-  a.out_scores = (double*)d_scores;
-  a.out_counts = (uint32_t*)d_counts;
-  a.alpha = similarity;
-  a.n_q = n_q;
-  a.k = k;
-  a.metric = metric;
-  a.autocomplete = autocomplete;
-  a.log2_cnt = index->log2_cnt;
-  a.t_floor = index->t_floor;
-  a.filter_level = index->filter_level;
-  a.prof = (unsigned long long*)g_prof_buf;
-#ifdef SG_PHASE_TIMING
-  { const char* e = getenv("SG_DEBUG_SKIP"); a.dbg_skip = e ? (uint32_t)atoi(e) : 0u; }
-#endif
-  int prev_dev = -1;   // the launch goes to the replica's device whatever the calling thread's current device is
-  HIP_TRY(hipGetDevice(&prev_dev));
-  if (prev_dev != rep->device) HIP_TRY(hipSetDevice(rep->device));
-  struct Restore { int d, want; ~Restore() { if (d != want) (void)hipSetDevice(d); } } restore{prev_dev, rep->device};
-  void* scratch = nullptr;
-  if (a.long_scratch && !no_long_queries) {   // the list of queries beyond the wavefront kernel's tables (a block of its own: tag 2)
-    void* ll = nullptr;
-    if (int rc = stream_scratch(rep->device, stream, ((size_t)n_q + 1) * 4, &ll, 2)) return rc;
-    a.long_list = (uint32_t*)ll;                             // (its count is zeroed below: by the ordering launch when there is one)
-  }
+// What a launch does, decided before it allocates or enqueues anything.  One thing may change it afterwards: a pipeline launch
+// whose block of records the device cannot give takes the fused kernel with the tokeniser launch instead (launch()).
+struct LaunchPlan {
+  int mode = 0, metric = 0;            // BatchArgs::autocomplete (2: by_doc) and ::metric (SG_TABLE: tabulated)
+  bool long_list = false;              // a list of the queries beyond the wavefront kernel's tables, for sg_long_kernel
+  bool reorder = false, ord_direct = false;   // heaviest queries first (query_order_*); per-block histograms instead of atomics
+  uint32_t ord_blocks = 0;
+  uint32_t split_min = 0, split_chunks = 0, slot_cap = 0, item_cap = 0;      // split queries (BatchArgs); split_min 0: none
+  bool sample = false;                 // the kernels sample the statistics block for the tightening controller
+  bool tight = false, roomy = false, slim = false, g8 = false;               // the fused kernel's instantiation and queue
+  bool pretok = false;                 // the tokeniser as a launch of its own (on the pipeline: the plan launch's job)
+  bool pipe = false;                   // plan -> stream -> verify, the fused kernel behind them
+  uint32_t nw = 0, log2_cnt = 0, dt_bytes = 0;   // the stream workgroup: wavefronts, log2 of its counters, LDS of its descriptors
+  bool wide = false;                   // 8-byte sub-row descriptors
+  bool two = false; Plan2Args p2{};    // sg_plan2_kernel (two queries per wavefront) and its LDS
+};
+
+LaunchPlan plan_launch(sg_index* index, Replica* rep, const LaunchReq& r) {
+  const uint32_t n_q = r.n_q, k = r.k;
+  const volatile uint32_t* h = rep->h_fill;
+  LaunchPlan p;
+  p.mode = r.by_doc ? 2 : r.autocomplete; p.metric = r.mt ? SG_TABLE : r.metric;
+  p.long_list = rep->long_scratch && !r.no_long_queries;
   // heaviest queries first (query_order_kernel): a batch that fills the machine many times over, no order given by the caller
-  // (d_flag: a launch over the queries a flag array marks — the order kernels make the list, heaviest first like any other)
-  bool long_zeroed = false;
-  uint32_t* order_ctl = nullptr;
-  const bool reorder = d_flag || (!d_sel && index->order_queries && n_q >= (index->order_queries == 1 ? 8192u : (uint32_t)index->order_queries));
-  const unsigned ord_blocks = (n_q + 1023u) / 1024u;
-  const bool ord_direct = ord_blocks <= SG_ORDER_DIRECT_BLOCKS;      // per-block histograms instead of atomics (engine.hip, query_order_*)
-  const size_t ord_bytes = reorder ? (((size_t)n_q * 4 + 15) & ~(size_t)15) + SG_ORDER_CTL_WORDS * 4 + (ord_direct ? (size_t)ord_blocks * 1024 : 0) : 0;
-  char* ord = nullptr;
-  // [r6] Whether this launch will take plan -> stream -> verify (decided for good further down): such a launch sets up no query
-  // splitting — round 5 had the two exclude each other the other way round, and an index whose queries pass the splitting
-  // threshold (25 M strings) dropped to the fused kernel without a word.  A stream workgroup per query is the balance there.
-  const bool pipe_likely = pipe_capable(index, rep) && !lm && !autocomplete && !rep->dix.has_g8 && index->tighten != 1 &&
-                           !(index->tighten == 2 && rep->tight_now.load(std::memory_order_relaxed)) && !(similarity < 0.3 && index->tighten == 2 && rep->h_fill && ((volatile uint32_t*)rep->h_fill)[1] == 0u) &&
-                           index->pre_tokenize && n_q >= (uint32_t)index->pre_tokenize && n_q <= (1u << 21) &&
-                           (index->pipe == 1 || (index->pipe_pays && rep->pipe_off_launches.load(std::memory_order_relaxed) == 0u));
-  if (k > SG_K_LDS) {  // top-k working rows in HBM
-    const size_t rows_bytes = ((size_t)n_q * k * 12 + 15) & ~(size_t)15;
-    if (int rc = stream_scratch(rep->device, stream, rows_bytes + ord_bytes, &scratch)) return rc;
-    a.scratch_s = (uint64_t*)scratch;
-    a.scratch_id = (uint32_t*)((char*)scratch + (size_t)n_q * k * 8);
-    ord = (char*)scratch + rows_bytes;
-  } else if (index->split_chunks && !lm && !by_doc && !pipe_likely) {
+  // (flag: a launch over the queries a flag array marks — the order kernels make the list, heaviest first like any other)
+  p.reorder = r.flag || (!r.sel && index->order_queries && n_q >= (index->order_queries == 1 ? 8192u : (uint32_t)index->order_queries));
+  p.ord_blocks = (n_q + 1023u) / 1024u; p.ord_direct = p.ord_blocks <= SG_ORDER_DIRECT_BLOCKS;
+  p.pretok = pretok_launch(index, n_q);
+  p.g8 = rep->dix.has_g8 != 0u;             // dense terms with 8-bit gaps: the kG8 instantiations (full LDS layout)
+  // [r6] Split queries, unless the launch will take the pipeline — judged on the controllers as they stand before this launch steps
+  // them: a stream workgroup per query is the balance there.  (Round 5 had the two exclude each other the other way round, and an
+  // index whose queries pass the splitting threshold — 25 M strings — dropped to the fused kernel without a word.)
+  const bool tight_before = index->tighten == 1 || (index->tighten == 2 && rep->tighten.now(h, r.similarity));
+  if (k <= SG_K_LDS && index->split_chunks && !r.lm && !r.by_doc && !pipe_eligible(index, rep, r, tight_before, rep->pipe_guard.holding())) {
     // Splitting pays (1) when the batch cannot fill the machine by itself: every query above 2 MiB of postings is cut
     // into 1 MiB parts; (2) for the outliers of a big batch, which would otherwise be its tail: one wavefront streams
     // ~1/3000 of the machine's rate, so a query holding more than 2x the expected volume and more than ~1/30000 of the
@@ -387,71 +436,18 @@ int launch(sg_index* index, Replica* rep, const void* d_q, const void* d_offs, u
     if (n_q > 4096u) smin = std::max(smin, std::max(2.0 * index->est_query_chunks, batch_chunks / 30000.0));
     // (the figures above are in chunks of the u32 CSR — 4 postings; the kernel counts chunks of the packed store — SG_PPC)
     const double pk = 4.0 / SG_PPC;
-    a.split_min = (uint32_t)std::min(smin * pk, 4.0e9);
-    a.split_chunks = std::max<uint32_t>((uint32_t)(index->split_chunks * pk), a.split_min / 4u);
+    p.split_min = (uint32_t)std::min(smin * pk, 4.0e9);
+    p.split_chunks = std::max<uint32_t>((uint32_t)(index->split_chunks * pk), p.split_min / 4u);
     // an index whose queries do not come near the threshold (4x the expected volume) pays nothing for the machinery
-    if (4.0 * index->est_query_chunks * pk < (double)a.split_min) a.split_min = 0;
+    if (4.0 * index->est_query_chunks * pk < (double)p.split_min) p.split_min = 0;
   }
-  if (a.split_min) {
-    const size_t per_slot = (size_t)SG_MAX_PARTS * k * 12;
-    a.slot_cap = (uint32_t)std::min<size_t>(n_q, ((size_t)1 << 30) / per_slot);
-    a.item_cap = std::min<uint32_t>(std::max<uint32_t>(n_q * 4u, 4096u), 262144u);
-    const size_t o_items = 64, o_slot = o_items + (size_t)a.item_cap * 16, o_pn = o_slot + (size_t)a.slot_cap * 8,
-                 o_ps = (o_pn + (size_t)a.slot_cap * SG_MAX_PARTS * 4 + 15) & ~(size_t)15,
-                 o_pid = o_ps + (size_t)a.slot_cap * SG_MAX_PARTS * k * 8,
-                 total = (o_pid + (size_t)a.slot_cap * SG_MAX_PARTS * k * 4 + 15) & ~(size_t)15;
-    if (int rc = stream_scratch(rep->device, stream, total + ord_bytes, &scratch)) return rc;
-    ord = (char*)scratch + total;
-    HIP_TRY(hipMemsetAsync(scratch, 0, o_items, stream));    // queue control words
-    char* base = (char*)scratch;
-    a.split_ctl = (uint32_t*)base;
-    a.items = (uint32_t*)(base + o_items);
-    a.slot_ctl = (uint32_t*)(base + o_slot);
-    a.part_n = (uint32_t*)(base + o_pn);
-    a.part_s = (uint64_t*)(base + o_ps);
-    a.part_id = (uint32_t*)(base + o_pid);
+  if (p.split_min) {
+    p.slot_cap = (uint32_t)std::min<size_t>(n_q, ((size_t)1 << 30) / ((size_t)SG_MAX_PARTS * k * 12));
+    p.item_cap = std::min<uint32_t>(std::max<uint32_t>(n_q * 4u, 4096u), 262144u);
   }
-  if (reorder) {
-    if (!ord) { if (int rc = stream_scratch(rep->device, stream, ord_bytes, &scratch)) return rc; ord = (char*)scratch; }
-    uint32_t* ctl = (uint32_t*)(ord + (((size_t)n_q * 4 + 15) & ~(size_t)15));
-    uint32_t* blk_hist = ord_direct ? ctl + SG_ORDER_CTL_WORDS : nullptr;
-    const unsigned blocks = ord_blocks;
-    if (!ord_direct) HIP_TRY(hipMemsetAsync(ctl, 0, SG_ORDER_CTL_WORDS * 4, stream));     // (the direct path keeps no batch-wide histogram there)
-    hipLaunchKernelGGL(query_order_count_kernel, dim3(blocks), dim3(1024), 0, stream, (const uint64_t*)d_offs, d_len, n_q, autocomplete == 1, ctl, d_flag, blk_hist,
-                       a.long_list, nullptr);
-    long_zeroed = true;
-    order_ctl = ctl;                                         // (ctl[1]: the pipeline's count of queries left to the fused kernel — zeroed with the block above)
-    hipLaunchKernelGGL(query_order_scatter_kernel, dim3(blocks), dim3(1024), 0, stream, (const uint64_t*)d_offs, d_len, n_q, autocomplete == 1, (uint32_t*)ord, ctl, d_flag, blk_hist);
-    HIP_TRY(hipGetLastError());
-    a.q_sel = (const uint32_t*)ord; a.q_sel_n = ctl;
-  }
-  if (a.long_list && !long_zeroed) HIP_TRY(hipMemsetAsync(a.long_list, 0, 4, stream));
-  bool tight = false, roomy = false;
-  if (!lm && !autocomplete && !by_doc) {
-    tight = roomy = index->tighten == 1;
-    if (index->tighten == 2 && rep->h_fill) {
-      const uint32_t full = ((volatile uint32_t*)rep->h_fill)[0], total = ((volatile uint32_t*)rep->h_fill)[1], results = ((volatile uint32_t*)rep->h_fill)[2];
-      const uint32_t d_total = total - rep->seen_total.load(std::memory_order_relaxed), d_full = full - rep->seen_full.load(std::memory_order_relaxed);
-      const uint32_t d_results = results - rep->seen_results.load(std::memory_order_relaxed);
-      if (d_total >= 32u && d_full <= d_total) {                // enough new sampled queries: on above 30 % full, off below 15 %
-        rep->seen_total.store(total, std::memory_order_relaxed); rep->seen_full.store(full, std::memory_order_relaxed);
-        rep->seen_results.store(results, std::memory_order_relaxed);
-        if (d_full * 100u > d_total * 30u) rep->tight_now.store(1, std::memory_order_relaxed);
-        else if (d_full * 100u < d_total * 15u) rep->tight_now.store(0, std::memory_order_relaxed);
-        // queries with more than a result each have many candidates in flight: they keep the large queue (11 wavefronts per
-        // CU); the others take the small one and the 12th wavefront (words Jaccard k=10: 41 vs 37 M q/s with the large one,
-        // headline +4.5 % with the small one)
-        if (d_results * 4u > d_total * 5u) rep->roomy_now.store(1, std::memory_order_relaxed);          // > 1.25 results per query
-        else if (d_results * 10u < d_total * 11u) rep->roomy_now.store(0, std::memory_order_relaxed);   // < 1.1
-      }
-      tight = rep->tight_now.load(std::memory_order_relaxed) != 0;
-      roomy = rep->roomy_now.load(std::memory_order_relaxed) != 0;
-      // (before the first statistics: a similarity this low admits most of the window — over a dictionary of near-duplicates
-      //  a million candidates per query unless the thresholds follow the top-k; the wrong guess costs a few per cent)
-      if (total == 0u && similarity < 0.3) tight = true;
-      a.fill_stat = rep->d_fill;
-      a.fill_mask = n_q <= 1024u ? 0u : 31u;
-    }
+  if (!r.lm && p.mode == 0) {
+    p.tight = index->tighten == 1;
+    if (index->tighten == 2 && h) { p.tight = rep->tighten.step(h, r.similarity); p.sample = true; }
   }
   // [r4] The large queue (11 wavefronts per CU instead of 12) only for the tightening instantiation (the full layout anyway)
   // and the docID-ordered mode (every candidate is a result).  Rounds 2-3 also gave it to launches whose recent queries had
@@ -459,180 +455,258 @@ int launch(sg_index* index, Replica* rep, const void* d_q, const void* d_offs, u
   // small / large: words Jaccard 58.9 / 56.7 M q/s, families 33.4 / 32.5, cfg 5 39.5 / 37.1 M predictions/s —
   // profiles/r04t_*, r04s_spell_sweep.txt): a queue that fills is emptied by the overflow walk, a wavefront that is missing is missing
   // all the time.
-  roomy = index->roomy == 2 ? (tight || by_doc) : index->roomy == 1;
+  p.roomy = index->roomy == 2 ? (p.tight || r.by_doc) : index->roomy == 1;
   // the slim table sizes where they buy a wavefront per CU (engine.hip, Lds<>); the tightening instantiation has the full ones
-  const bool g8 = rep->dix.has_g8 != 0u;                 // dense terms with 8-bit gaps: the kG8 instantiations (full LDS layout)
-  const bool slim = !tight && !g8 && sg_lds_waves(a.log2_cnt, k, roomy, true) > sg_lds_waves(a.log2_cnt, k, roomy, false);
-  a.cq_cap = sg_queue_cap(a.log2_cnt, k, roomy, slim);
-  const size_t lds = lds_bytes(a.log2_cnt, k, roomy, slim);
-  // the tokeniser as a launch of its own: every query of the batch in the caller's numbering (the search launch may run
-  // them in another order), or the caller's subset of it
-  // (512 B of scratch per query: a batch of more than 2 M queries — 1 GiB of it — lets the search kernel tokenise itself)
-  const bool pretok = index->pre_tokenize && n_q >= (uint32_t)index->pre_tokenize && n_q <= (1u << 21);
-  // [r5] An ordinary fuzzy batch (top-k by score in LDS, no tightening, no split queries, large enough for a tokeniser launch of
-  // its own, a dictionary above the one-counter-per-document size) goes through plan -> stream -> verify (pipeline.inc: the plan
-  // launch tokenises); the fused kernel runs behind them over the queries they list for it.
-  bool pipe = pipe_capable(index, rep) && pretok && !lm && !autocomplete && !tight && !g8 && !a.split_ctl;
-  if (pipe && index->pipe == 2) {
-    // Where it pays (tune_choice: by the index's expected query volume; profiles/r05r_*), and only while
-    // the plan can express the queries and their candidates fit the slots: a replica that saw more than a fifth of its recent
-    // pipeline queries come back to the fused kernel (dictionaries of near-duplicates: hundreds of flagged postings per query;
-    // documents that repeat terms) skips the pipeline for its next 64 launches, then tries again.
-    if (!index->pipe_pays) pipe = false;
-    else if (rep->h_fill) {
-      const uint32_t fb = ((volatile uint32_t*)rep->h_fill)[3] + ((volatile uint32_t*)rep->h_fill)[6] + ((volatile uint32_t*)rep->h_fill)[7];
-      const uint64_t q_now = rep->pipe_queries.load(std::memory_order_relaxed), q_seen = rep->pipe_seen_queries.load(std::memory_order_relaxed);
-      const uint32_t d_fb = fb - rep->pipe_seen_fb.load(std::memory_order_relaxed);
-      if (d_fb && q_now - q_seen >= 4096u) {
-        rep->pipe_seen_fb.store(fb, std::memory_order_relaxed); rep->pipe_seen_queries.store(q_now, std::memory_order_relaxed);
-        if ((uint64_t)d_fb * 5u > q_now - q_seen) rep->pipe_off_launches.store(64u, std::memory_order_relaxed);
-      }
-      const uint32_t off = rep->pipe_off_launches.load(std::memory_order_relaxed);
-      if (off) { rep->pipe_off_launches.store(off - 1u, std::memory_order_relaxed); pipe = false; }
-    }
-  }
+  p.slim = !p.tight && !p.g8 && sg_lds_waves(index->log2_cnt, k, p.roomy, true) > sg_lds_waves(index->log2_cnt, k, p.roomy, false);
+  // the pipeline on the controllers' state after this launch's step; the guard looks only at launches that could take it
+  p.pipe = !p.split_min && pipe_eligible(index, rep, r, p.tight, false) &&
+           !(index->pipe == 2 && h && rep->pipe_guard.step(h, rep->pipe_queries.load(std::memory_order_relaxed)));
+  if (!p.pipe) return p;
   // [r6] The stream workgroup's shape, per launch.  Which of the three measured shapes is fastest follows what a query of THIS
   // launch streams, not the index alone: 10 M strings want four wavefronts on 2^12 counters at Jaccard >= 0.5 (1.324 against
   // 1.346 ms; 8 M: 1.10 against 1.15) and eight on 2^13 at Cosine >= 0.4 (2.45 against 4.44 ms: the lighter shape leaves 40 % of
   // the queries unplanned).  The estimate: the index's expected query volume (tune_index) x the square of the share of a typical
   // query's lists that list skipping leaves under this metric and similarity (the lists left are the short ones); the cuts, 3 200
   // and 12 000 chunks, put all sixteen measured launches — 1 M ... 16 M strings under both — on their fastest shape
-  // (profiles/r06final_shape_by_size.txt, r06final_shape_auto_by_size.txt).  Where the model is wrong the counters correct it: a
-  // replica that saw more than a hundredth of a window's queries unplanned under a shape takes the next heavier one from then on.
-  uint32_t pipe_nw = index->pipe_nw, pipe_log2_cnt = index->pipe_log2_cnt, pipe_dt_bytes = index->pipe_dt_bytes;
-  if (pipe && !index->pipe_shape_fixed && metric >= SG_JACCARD && metric <= SG_OVERLAP) {
-    uint32_t shape = pipe_shape_model(index->est_query_chunks, index->terms_per_doc, index->t_floor, metric, similarity);
+  // (profiles/r06final_shape_by_size.txt, r06final_shape_auto_by_size.txt).  Where the model is wrong, ShapeFloor corrects it.
+  p.nw = index->pipe_nw; p.log2_cnt = index->pipe_log2_cnt; p.dt_bytes = index->pipe_dt_bytes;
+  if (!index->pipe_shape_fixed && p.metric >= SG_JACCARD && p.metric <= SG_OVERLAP) {
+    uint32_t shape = pipe_shape_model(index->est_query_chunks, index->terms_per_doc, index->t_floor, p.metric, r.similarity);
     shape = (uint32_t)std::max(0, (int)shape + index->pipe_shape_bias);
-    if (rep->h_fill) {
-      const uint32_t unplanned = ((volatile uint32_t*)rep->h_fill)[3];
-      const uint64_t q_now = rep->pipe_queries.load(std::memory_order_relaxed), q_seen = rep->pipe_shape_seen_queries.load(std::memory_order_relaxed);
-      if (q_now - q_seen >= 4096u) {
-        const uint32_t d_un = unplanned - rep->pipe_shape_seen_unplanned.load(std::memory_order_relaxed), last = rep->pipe_last_shape.load(std::memory_order_relaxed);
-        rep->pipe_shape_seen_unplanned.store(unplanned, std::memory_order_relaxed); rep->pipe_shape_seen_queries.store(q_now, std::memory_order_relaxed);
-        if ((uint64_t)d_un * 100u > q_now - q_seen && last < 2u && last >= rep->pipe_shape_floor.load(std::memory_order_relaxed)) rep->pipe_shape_floor.store(last + 1u, std::memory_order_relaxed);
-      }
-    }
-    shape = std::max(shape, rep->pipe_shape_floor.load(std::memory_order_relaxed));
-    rep->pipe_last_shape.store(shape, std::memory_order_relaxed);
+    shape = rep->shape_floor.step(h, rep->pipe_queries.load(std::memory_order_relaxed), shape);
     static const uint32_t kShape[3][3] = {{2u, 11u, 2048u}, {4u, 12u, 4096u}, {8u, 13u, 8192u}};
-    pipe_nw = kShape[shape][0]; pipe_log2_cnt = kShape[shape][1]; pipe_dt_bytes = kShape[shape][2];
-  } else if (pipe) rep->pipe_last_shape.store(3u, std::memory_order_relaxed);      // (the knobs' / the index's own: its unplanned queries say nothing about the three)
-  // [r6] the pipeline's records: a grow-only block of this thread and stream, bounded whatever the batch (pieces, below); if the
-  // device cannot give it the launch takes the fused kernel with the tokeniser launch — less memory — instead of failing
-  void* pipe_block = nullptr;
-  const uint32_t pipe_piece = std::min<uint32_t>(n_q, SG_PIPE_PIECE), pipe_vrec_words = sg_pipe_vrec_words(index->pipe_cand_cap),
-                 pipe_ovf_cap = std::max<uint32_t>(pipe_piece / 8u, 64u);
-  const size_t o_rec = 256, o_vrec = o_rec + (size_t)pipe_piece * SG_PIPE_REC_STRIDE * 4, o_ovf = o_vrec + (size_t)pipe_piece * pipe_vrec_words * 4,
-               o_cn = o_ovf + (size_t)pipe_ovf_cap * SG_PIPE_OVF_WORDS * 4, o_fb = o_cn + (((size_t)pipe_piece * 4 + 255) & ~(size_t)255),
-               pipe_total = o_fb + ((((size_t)n_q + 1) * 4 + 15) & ~(size_t)15);
-  if (pipe && stream_scratch(rep->device, stream, pipe_total, &pipe_block, 4) != SG_OK) { pipe = false; (void)hipGetLastError(); }
-  if (pipe) rep->pipe_queries.fetch_add(n_q, std::memory_order_relaxed);
-  if (pretok && !pipe) {
+    p.nw = kShape[shape][0]; p.log2_cnt = kShape[shape][1]; p.dt_bytes = kShape[shape][2];
+  } else rep->shape_floor.last.store(3u, std::memory_order_relaxed);   // (the knobs' / the index's own: its unplanned queries say nothing about the three)
+  p.wide = pipe_wide(index, rep);                                         // sub-row descriptors of 8 bytes: a store of 2^26 chunks and more
+  // [r6] two queries per plan wavefront (plan2.inc) where the description allows.  Its LDS — hence its wavefronts per SIMD — follows
+  // the largest table of chunk offsets a query of <= 32 n-grams can need under this metric and similarity: n-grams x (segments of
+  // the window + 1); queries beyond are planned one per wavefront inside the same launch.
+  p.two = plan2_usable(index, rep, p.metric);
+  if (p.two) {
+    uint32_t need = 0;
+    const int S_i = (int)rep->dix.S;
+    for (int A_i = 1; A_i <= 32; A_i++) {
+      const int lo = std::max(metric_min_y(p.metric, r.similarity, A_i), 0), hi = std::min(metric_max_y(p.metric, r.similarity, A_i), S_i - 1), W_i = hi - lo + 1;
+      if (W_i >= 1 && W_i <= 32) need = std::max<uint32_t>(need, (uint32_t)A_i * (uint32_t)(W_i + 1));
+    }
+    p.p2.rows_cap = std::min<uint32_t>(std::max<uint32_t>(need, 64u), SG_PLAN2_ROWS_MAX);
+    p.p2.half_words = std::max<uint32_t>(p.p2.rows_cap + 32u, SG_PIPE_ROWS_WORDS / 2u);
+    p.p2.half_words = std::max<uint32_t>(p.p2.half_words, SG_PLAN2_RUNES + 96u);
+  }
+  return p;
+}
+
+// The SCRATCH_ROWS block: the top-k rows in HBM (k > SG_K_LDS) or the split-query queue (a 64-byte control head, then items, slot
+// words, the parts' counts, rows and ids), then the ordered list of the queries, its control words and block histograms.
+struct RowsLayout { size_t s = 0, id = 0, split = 0, items = 0, slot = 0, part_n = 0, part_s = 0, part_id = 0, ord = 0, ord_ctl = 0, bytes = 0; };
+RowsLayout rows_layout(const LaunchPlan& p, uint32_t n_q, uint32_t k) {
+  RowsLayout L;
+  Carve c;
+  if (k > SG_K_LDS) {
+    L.s = c.take((size_t)n_q * k * 8); L.id = c.take((size_t)n_q * k * 4, 4);
+  } else if (p.split_min) {
+    L.split = c.take(64); L.items = c.take((size_t)p.item_cap * 16); L.slot = c.take((size_t)p.slot_cap * 8);
+    L.part_n = c.take((size_t)p.slot_cap * SG_MAX_PARTS * 4, 4);
+    L.part_s = c.take((size_t)p.slot_cap * SG_MAX_PARTS * k * 8); L.part_id = c.take((size_t)p.slot_cap * SG_MAX_PARTS * k * 4);
+  }
+  if (p.reorder) {   // (the block histograms follow the control words)
+    L.ord = c.take((size_t)n_q * 4); L.ord_ctl = c.take(SG_ORDER_CTL_WORDS * 4); c.take(p.ord_direct ? (size_t)p.ord_blocks * 1024 : 0);
+  }
+  L.bytes = c.size();
+  return L;
+}
+
+// The SCRATCH_PIPE block: its two counters, then a piece's records (SG_PIPE_PIECE queries at most), verify records, overflow
+// blocks and candidate counts, then the batch's list of the queries handed back to the fused kernel.  ~5.2 KB per query of a piece
+// (4 KB + 0.64 KB + an eighth of a 4 KB overflow block), so the block stays below ~345 MB whatever the batch (round 5: 8.5 KB per
+// query of the batch, 17 GB for 2 M queries).
+struct PipeLayout { uint32_t piece, vrec_words, ovf_cap; size_t rec, vrec, ovf, cand_n, fb_list, bytes; };
+PipeLayout pipe_layout(uint32_t n_q, uint32_t cand_cap) {
+  PipeLayout L;
+  L.piece = std::min<uint32_t>(n_q, SG_PIPE_PIECE); L.vrec_words = sg_pipe_vrec_words(cand_cap); L.ovf_cap = std::max<uint32_t>(L.piece / 8u, 64u);
+  Carve c;
+  c.take(8);                                                    // fb_n, ovf_n (unless the ordering launch keeps them)
+  L.rec = c.take((size_t)L.piece * SG_PIPE_REC_STRIDE * 4, 256); L.vrec = c.take((size_t)L.piece * L.vrec_words * 4);
+  L.ovf = c.take((size_t)L.ovf_cap * SG_PIPE_OVF_WORDS * 4); L.cand_n = c.take(((size_t)L.piece * 4 + 255) & ~(size_t)255);
+  L.fb_list = c.take(((size_t)n_q + 1) * 4);
+  L.bytes = c.size();
+  return L;
+}
+
+BatchArgs batch_args(const sg_index* index, const Replica* rep, const LaunchReq& r, const LaunchPlan& p) {
+  BatchArgs a{};
+  a.ix = rep->dix;
+  a.q_sel = r.sel; a.q_sel_n = r.sel_n;
+  a.long_scratch = rep->long_scratch; a.long_lock = rep->long_lock; a.long_slot_bytes = rep->long_slot_bytes; a.long_max_seg = rep->long_max_seg;
+  a.q_len = r.len; a.ac_first = r.ac_first; a.out_aux = r.out_aux;
+  if (r.mt) a.mt = *r.mt;
+  if (r.lm) { a.lm_values = r.lm->values; a.lm_from = r.lm->from; a.lm_to = r.lm->to; }
+  a.q_blob = (const uint8_t*)r.q; a.q_offs = (const uint64_t*)r.offs;
+  a.out_ids = (uint32_t*)r.ids; a.out_scores = (double*)r.scores; a.out_counts = (uint32_t*)r.counts;
+  a.alpha = r.similarity; a.n_q = r.n_q; a.k = r.k; a.metric = p.metric; a.autocomplete = p.mode;
+  a.log2_cnt = index->log2_cnt; a.t_floor = index->t_floor; a.filter_level = index->filter_level;
+  a.prof = (unsigned long long*)g_prof_buf;
+#ifdef SG_PHASE_TIMING
+  { const char* e = getenv("SG_DEBUG_SKIP"); a.dbg_skip = e ? (uint32_t)atoi(e) : 0u; }
+#endif
+  a.split_min = p.split_min; a.split_chunks = p.split_chunks; a.slot_cap = p.slot_cap; a.item_cap = p.item_cap;
+  if (p.sample) { a.fill_stat = rep->d_fill; a.fill_mask = r.n_q <= 1024u ? 0u : 31u; }
+  a.cq_cap = sg_queue_cap(a.log2_cnt, r.k, p.roomy, p.slim);
+  return a;
+}
+
+// ---- the kernel instantiations a plan takes (defined in the order the launch ladders named them: the device code's function
+// order follows the host's first references) ----
+using BatchKernel = void (*)(BatchArgs);
+using PipeKernel = void (*)(BatchArgs, PipeArgs);
+PipeKernel stream_kernel(uint32_t nw, bool wide) {   // nw: 2, 4 or 8 wavefronts of a workgroup
+  static const PipeKernel kByShape[2][3] = {{sg_stream_kernel<8, true>, sg_stream_kernel<4, true>, sg_stream_kernel<2, true>},
+                                            {sg_stream_kernel<8, false>, sg_stream_kernel<4, false>, sg_stream_kernel<2, false>}};
+  return kByShape[wide ? 0 : 1][nw == 8 ? 0 : nw == 4 ? 1 : 2];
+}
+
+// plan -> stream -> verify over pieces of at most SG_PIPE_PIECE queries (positions of the ordered list, or of the batch), then the
+// fused kernel over the queries they handed back, in its full LDS layout
+int enqueue_pipeline(const sg_index* index, const Replica* rep, const BatchArgs& a, const LaunchPlan& p, const PipeLayout& L, char* blk,
+                     uint32_t* order_ctl, hipStream_t stream) {
+  const uint32_t n_q = a.n_q, k = a.k;
+  PipeArgs pa{};
+  pa.sub_log2 = index->pipe_sub;
+  pa.stat = rep->d_fill; pa.stat_mask = n_q <= 1024u ? 0u : 255u;      // (one query in 256: a few hundred atomics on one line per launch)
+  pa.log2_cnt = p.log2_cnt; pa.cand_cap = index->pipe_cand_cap; pa.vrec_words = L.vrec_words;
+  // a stream workgroup's LDS (pipeline.inc): counters | sub-row descriptors of the query's groups + a dead one
+  const size_t cnt_bytes = 4 * std::max<size_t>((size_t)1 << pa.log2_cnt, SG_PIPE_REC_WORDS);
+  const size_t lds = std::min<size_t>((cnt_bytes + p.dt_bytes + 1279) / 1280 * 1280, 65536);   // (whole allocation granules: 40 960 B = four workgroups per CU with the defaults; a workgroup's limit is 64 KB)
+  pa.dt_rows = (uint32_t)((lds - cnt_bytes - 16) / (p.wide ? 8 : 4) / (64u >> pa.sub_log2));     // (behind the table: a dead descriptor)
+  pa.ovf_cap = L.ovf_cap; pa.rec = (uint32_t*)(blk + L.rec); pa.vrec = (uint32_t*)(blk + L.vrec); pa.ovf = (uint32_t*)(blk + L.ovf); pa.cand_n = (uint32_t*)(blk + L.cand_n);
+  pa.fb_list = (uint32_t*)(blk + L.fb_list);
+  if (order_ctl) { pa.fb_n = order_ctl + 1; pa.ovf_n = order_ctl + 2; }     // (zeroed by the ordering launch)
+  else { pa.fb_n = (uint32_t*)blk; pa.ovf_n = (uint32_t*)blk + 1; HIP_TRY(hipMemsetAsync(blk, 0, 8, stream)); }
+  const PipeKernel stream_k = stream_kernel(p.nw, p.wide), verify_k = k > SG_K_LDS ? sg_verify_kernel_bigk : sg_verify_kernel;
+  for (uint32_t b0 = 0; b0 < n_q; b0 += L.piece) {
+    pa.b0 = b0; pa.n = std::min(L.piece, n_q - b0);
+    if (p.two) hipLaunchKernelGGL(sg_plan2_kernel, dim3((pa.n + 1u) / 2u), dim3(64), (size_t)p.p2.half_words * 8, stream, a, pa, p.p2);
+    else hipLaunchKernelGGL(sg_plan_kernel, dim3(pa.n), dim3(64), 0, stream, a, pa);
+    hipLaunchKernelGGL(stream_k, dim3(pa.n), dim3(64 * p.nw), lds, stream, a, pa);
+    hipLaunchKernelGGL(verify_k, dim3(pa.n), dim3(64), 0, stream, a, pa);
+    if (b0 + L.piece < n_q) HIP_TRY(hipMemsetAsync(pa.ovf_n, 0, 4, stream));       // (the next piece's overflow blocks)
+  }
+  BatchArgs fa = a;
+  fa.q_sel = pa.fb_list; fa.q_sel_n = pa.fb_n; fa.cq_cap = sg_queue_cap(a.log2_cnt, k, p.roomy, false);
+  hipLaunchKernelGGL(sg_search_kernel_loop, dim3(std::min<uint32_t>(n_q, 3072u)), dim3(64), lds_bytes(a.log2_cnt, k, p.roomy, false), stream, fa);
+  return SG_OK;
+}
+
+BatchKernel fused_kernel(bool lm, bool tight, bool slim, bool g8) {
+  if (g8 && lm) return sg_lm_kernel_g8;                 // (8-bit gaps: the full LDS layout)
+  if (g8) return tight ? sg_search_kernel_tight_g8 : sg_search_kernel_g8;
+  if (lm) return slim ? sg_lm_kernel_slim : sg_lm_kernel;
+  if (tight) return sg_search_kernel_tight;
+  return slim ? sg_search_kernel_slim : sg_search_kernel;
+}
+BatchKernel parts_kernel(bool tight, bool g8) {
+  return g8 ? (tight ? sg_parts_kernel_tight_g8 : sg_parts_kernel_g8) : (tight ? sg_parts_kernel_tight : sg_parts_kernel);
+}
+
+// Every batch goes through here: plan, allocate, enqueue.
+int launch(sg_index* index, Replica* rep, const LaunchReq& r) {
+  const uint32_t n_q = r.n_q, k = r.k;
+  const hipStream_t stream = r.stream;
+  if (n_q == 0) return SG_OK;
+  // top-k rows above SG_K_LDS entries live in HBM, k x 12 bytes per query: a batch whose rows would pass 1 GiB goes
+  // through in pieces (the queries are independent)
+  if (k > SG_K_LDS && !r.sel && (size_t)n_q * k * 12 > ((size_t)1 << 30)) {
+    const uint32_t piece = (uint32_t)std::max<size_t>(1, ((size_t)1 << 30) / ((size_t)k * 12));
+    for (uint32_t lo = 0; lo < n_q; lo += piece) {
+      LaunchReq s = r;
+      LmRanges lm{};
+      s.offs = (const uint64_t*)r.offs + lo; s.n_q = std::min(piece, n_q - lo); s.sel_n = nullptr;
+      s.ids = (uint32_t*)r.ids + (size_t)lo * k; s.counts = (uint32_t*)r.counts + lo;
+      if (r.scores) s.scores = (double*)r.scores + (size_t)lo * k;
+      if (r.lm) { lm = LmRanges{r.lm->values, r.lm->from + lo, r.lm->to + lo}; s.lm = &lm; }
+      if (r.len) s.len = r.len + lo;
+      if (r.out_aux) s.out_aux = r.out_aux + (size_t)lo * k;
+      if (r.flag) s.flag = r.flag + lo;
+      if (int rc = launch(index, rep, s)) return rc;
+    }
+    return SG_OK;
+  }
+  LaunchPlan p = plan_launch(index, rep, r);
+  BatchArgs a = batch_args(index, rep, r, p);
+  int prev_dev = -1;   // the launch goes to the replica's device whatever the calling thread's current device is
+  HIP_TRY(hipGetDevice(&prev_dev));
+  if (prev_dev != rep->device) HIP_TRY(hipSetDevice(rep->device));
+  struct Restore { int d, want; ~Restore() { if (d != want) (void)hipSetDevice(d); } } restore{prev_dev, rep->device};
+  void* blk = nullptr;
+  if (p.long_list) {   // the list of queries beyond the wavefront kernel's tables (its count is zeroed below: by the ordering launch when there is one)
+    if (int rc = stream_scratch(rep->device, stream, ((size_t)n_q + 1) * 4, &blk, SCRATCH_LONG_LIST)) return rc;
+    a.long_list = (uint32_t*)blk;
+  }
+  const RowsLayout R = rows_layout(p, n_q, k);
+  uint32_t* order_ctl = nullptr;            // (ctl[1], ctl[2]: the pipeline's counts of queries handed back and overflow blocks — zeroed with it)
+  if (R.bytes) {
+    if (int rc = stream_scratch(rep->device, stream, R.bytes, &blk, SCRATCH_ROWS)) return rc;
+    char* b = (char*)blk;
+    if (k > SG_K_LDS) { a.scratch_s = (uint64_t*)(b + R.s); a.scratch_id = (uint32_t*)(b + R.id); }
+    if (p.split_min) {
+      HIP_TRY(hipMemsetAsync(b + R.split, 0, 64, stream));    // queue control words
+      a.split_ctl = (uint32_t*)(b + R.split); a.items = (uint32_t*)(b + R.items); a.slot_ctl = (uint32_t*)(b + R.slot);
+      a.part_n = (uint32_t*)(b + R.part_n); a.part_s = (uint64_t*)(b + R.part_s); a.part_id = (uint32_t*)(b + R.part_id);
+    }
+    if (p.reorder) {
+      uint32_t* ord = (uint32_t*)(b + R.ord);
+      order_ctl = (uint32_t*)(b + R.ord_ctl);
+      uint32_t* blk_hist = p.ord_direct ? order_ctl + SG_ORDER_CTL_WORDS : nullptr;
+      if (!p.ord_direct) HIP_TRY(hipMemsetAsync(order_ctl, 0, SG_ORDER_CTL_WORDS * 4, stream));   // (the direct path keeps no batch-wide histogram there)
+      hipLaunchKernelGGL(query_order_count_kernel, dim3(p.ord_blocks), dim3(1024), 0, stream, (const uint64_t*)r.offs, r.len, n_q, p.mode == 1, order_ctl, r.flag,
+                         blk_hist, a.long_list, nullptr);
+      hipLaunchKernelGGL(query_order_scatter_kernel, dim3(p.ord_blocks), dim3(1024), 0, stream, (const uint64_t*)r.offs, r.len, n_q, p.mode == 1, ord, order_ctl,
+                         r.flag, blk_hist);
+      HIP_TRY(hipGetLastError());
+      a.q_sel = ord; a.q_sel_n = order_ctl;
+    }
+  }
+  if (a.long_list && !order_ctl) HIP_TRY(hipMemsetAsync(a.long_list, 0, 4, stream));
+  // the pipeline's records; if the device cannot give them the launch takes the fused kernel with the tokeniser launch — less memory
+  // — instead of failing (the one change to a plan after it is made)
+  const PipeLayout P = pipe_layout(n_q, index->pipe_cand_cap);
+  void* pipe_blk = nullptr;
+  if (p.pipe && stream_scratch(rep->device, stream, P.bytes, &pipe_blk, SCRATCH_PIPE) != SG_OK) { p.pipe = false; (void)hipGetLastError(); }
+  if (p.pipe) rep->pipe_queries.fetch_add(n_q, std::memory_order_relaxed);
+  else if (p.pretok) {   // every query of the batch in the caller's numbering (the search launch may run them in another order), or the caller's subset
+    Carve c;
+    const size_t o_A = c.take((size_t)n_q * 4), o_terms = c.take((size_t)n_q * SG_MAX_A * 4, 256);
     void* pt = nullptr;
-    const size_t a_bytes = ((size_t)n_q * 4 + 255) & ~(size_t)255;
-    if (int rc = stream_scratch(rep->device, stream, a_bytes + (size_t)n_q * SG_MAX_A * 4, &pt, 3)) return rc;
-    a.pre_A = (int32_t*)pt;
-    a.pre_terms = (uint32_t*)((char*)pt + a_bytes);
+    if (int rc = stream_scratch(rep->device, stream, c.size(), &pt, SCRATCH_PRETOK)) return rc;
+    a.pre_A = (int32_t*)((char*)pt + o_A); a.pre_terms = (uint32_t*)((char*)pt + o_terms);
     BatchArgs ta = a;
-    if (!d_flag) { ta.q_sel = d_sel; ta.q_sel_n = d_sel_n; }      // (the caller's subset; a flagged subset: the list just made)
+    if (!r.flag) { ta.q_sel = r.sel; ta.q_sel_n = r.sel_n; }      // (the caller's subset; a flagged subset: the list just made)
     hipLaunchKernelGGL(sg_terms_kernel, dim3(n_q), dim3(64), 0, stream, ta);
     HIP_TRY(hipGetLastError());
   }
-
-  if (pipe) {
-    PipeArgs pa{};
-    pa.sub_log2 = index->pipe_sub;
-    pa.stat = rep->d_fill; pa.stat_mask = n_q <= 1024u ? 0u : 255u;      // (one query in 256: a few hundred atomics on one line per launch)
-    pa.log2_cnt = pipe_log2_cnt;
-    pa.cand_cap = index->pipe_cand_cap;
-    pa.vrec_words = sg_pipe_vrec_words(pa.cand_cap);
-    const bool wide = pipe_wide(index, rep);                      // sub-row descriptors of 8 bytes: a store of 2^26 chunks and more
-    const uint32_t dpr = 64u >> pa.sub_log2, nw = pipe_nw;
-    // a stream workgroup's LDS (pipeline.inc): counters | sub-row descriptors of the query's groups + a dead one
-    const size_t cnt_bytes = 4 * std::max<size_t>((size_t)1 << pa.log2_cnt, SG_PIPE_REC_WORDS);
-    const size_t lds_pipe = std::min<size_t>((cnt_bytes + pipe_dt_bytes + 1279) / 1280 * 1280, 65536);   // (whole allocation granules: 40 960 B = four workgroups per CU with the defaults; a workgroup's limit is 64 KB)
-    pa.dt_rows = (uint32_t)((lds_pipe - cnt_bytes - 16) / (wide ? 8 : 4) / dpr);     // (behind the table: a dead descriptor)
-    // [r6] the batch goes through in pieces of at most SG_PIPE_PIECE queries (positions of the ordered list, or of the batch):
-    // ~5.2 KB of records per query of a piece (4 KB + 0.64 KB + an eighth of a 4 KB overflow block), so the block stays below
-    // ~345 MB whatever the batch (round 5: 8.5 KB per query of the batch, 17 GB for 2 M queries)
-    const uint32_t piece = pipe_piece;
-    pa.ovf_cap = pipe_ovf_cap;
-    char* pb = (char*)pipe_block;
-    pa.rec = (uint32_t*)(pb + o_rec); pa.vrec = (uint32_t*)(pb + o_vrec); pa.ovf = (uint32_t*)(pb + o_ovf); pa.cand_n = (uint32_t*)(pb + o_cn);
-    pa.fb_list = (uint32_t*)(pb + o_fb);
-    if (order_ctl) { pa.fb_n = order_ctl + 1; pa.ovf_n = order_ctl + 2; }     // (zeroed by the ordering launch)
-    else { pa.fb_n = (uint32_t*)pb; pa.ovf_n = (uint32_t*)pb + 1; HIP_TRY(hipMemsetAsync(pb, 0, 8, stream)); }
-    // [r6] two queries per plan wavefront (plan2.inc) where the description allows.  Its LDS — hence its wavefronts per SIMD — follows
-    // the largest table of chunk offsets a query of <= 32 n-grams can need under this metric and similarity: n-grams x (segments of
-    // the window + 1); queries beyond are planned one per wavefront inside the same launch.
-    const bool two = plan2_usable(index, rep, metric);
-    Plan2Args p2{};
-    if (two) {
-      uint32_t need = 0;
-      const int S_i = (int)rep->dix.S;
-      for (int A_i = 1; A_i <= 32; A_i++) {
-        const int lo = std::max(metric_min_y(metric, similarity, A_i), 0), hi = std::min(metric_max_y(metric, similarity, A_i), S_i - 1), W_i = hi - lo + 1;
-        if (W_i >= 1 && W_i <= 32) need = std::max<uint32_t>(need, (uint32_t)A_i * (uint32_t)(W_i + 1));
-      }
-      p2.rows_cap = std::min<uint32_t>(std::max<uint32_t>(need, 64u), SG_PLAN2_ROWS_MAX);
-      p2.half_words = std::max<uint32_t>(p2.rows_cap + 32u, SG_PIPE_ROWS_WORDS / 2u);
-      p2.half_words = std::max<uint32_t>(p2.half_words, SG_PLAN2_RUNES + 96u);
-    }
-    for (uint32_t b0 = 0; b0 < n_q; b0 += piece) {
-      pa.b0 = b0; pa.n = std::min(piece, n_q - b0);
-      if (two) hipLaunchKernelGGL(sg_plan2_kernel, dim3((pa.n + 1u) / 2u), dim3(64), (size_t)p2.half_words * 8, stream, a, pa, p2);
-      else hipLaunchKernelGGL(sg_plan_kernel, dim3(pa.n), dim3(64), 0, stream, a, pa);
-      if (wide) {
-        if (nw == 8) hipLaunchKernelGGL((sg_stream_kernel<8, true>), dim3(pa.n), dim3(512), lds_pipe, stream, a, pa);
-        else if (nw == 4) hipLaunchKernelGGL((sg_stream_kernel<4, true>), dim3(pa.n), dim3(256), lds_pipe, stream, a, pa);
-        else hipLaunchKernelGGL((sg_stream_kernel<2, true>), dim3(pa.n), dim3(128), lds_pipe, stream, a, pa);
-      } else {
-        if (nw == 8) hipLaunchKernelGGL((sg_stream_kernel<8, false>), dim3(pa.n), dim3(512), lds_pipe, stream, a, pa);
-        else if (nw == 4) hipLaunchKernelGGL((sg_stream_kernel<4, false>), dim3(pa.n), dim3(256), lds_pipe, stream, a, pa);
-        else hipLaunchKernelGGL((sg_stream_kernel<2, false>), dim3(pa.n), dim3(128), lds_pipe, stream, a, pa);
-      }
-      if (k > SG_K_LDS) hipLaunchKernelGGL(sg_verify_kernel_bigk, dim3(pa.n), dim3(64), 0, stream, a, pa);
-      else hipLaunchKernelGGL(sg_verify_kernel, dim3(pa.n), dim3(64), 0, stream, a, pa);
-      if (b0 + piece < n_q) HIP_TRY(hipMemsetAsync(pa.ovf_n, 0, 4, stream));       // (the next piece's overflow blocks)
-    }
-    BatchArgs fa = a;                                       // the queries left to the fused kernel: its full LDS layout
-    fa.q_sel = pa.fb_list; fa.q_sel_n = pa.fb_n;
-    fa.cq_cap = sg_queue_cap(a.log2_cnt, k, roomy, false);
-    hipLaunchKernelGGL(sg_search_kernel_loop, dim3(std::min<uint32_t>(n_q, 3072u)), dim3(64), lds_bytes(a.log2_cnt, k, roomy, false), stream, fa);
-  }
-  else if (g8) {
-    if (lm) hipLaunchKernelGGL(sg_lm_kernel_g8, dim3(n_q), dim3(64), lds, stream, a);
-    else if (tight) hipLaunchKernelGGL(sg_search_kernel_tight_g8, dim3(n_q), dim3(64), lds, stream, a);
-    else hipLaunchKernelGGL(sg_search_kernel_g8, dim3(n_q), dim3(64), lds, stream, a);
-  }
-  else if (lm && slim) hipLaunchKernelGGL(sg_lm_kernel_slim, dim3(n_q), dim3(64), lds, stream, a);
-  else if (lm) hipLaunchKernelGGL(sg_lm_kernel, dim3(n_q), dim3(64), lds, stream, a);
-  else if (tight) hipLaunchKernelGGL(sg_search_kernel_tight, dim3(n_q), dim3(64), lds, stream, a);
-  else if (slim) hipLaunchKernelGGL(sg_search_kernel_slim, dim3(n_q), dim3(64), lds, stream, a);
-  else hipLaunchKernelGGL(sg_search_kernel, dim3(n_q), dim3(64), lds, stream, a);
+  if (p.pipe) {
+    if (int rc = enqueue_pipeline(index, rep, a, p, P, (char*)pipe_blk, order_ctl, stream)) return rc;
+  } else hipLaunchKernelGGL(fused_kernel(r.lm != nullptr, p.tight, p.slim, p.g8), dim3(n_q), dim3(64), lds_bytes(a.log2_cnt, k, p.roomy, p.slim), stream, a);
   HIP_TRY(hipGetLastError());
   if (a.split_ctl) {     // the queued parts of split queries: persistent wavefronts, which leave at once if there are none
     // the parts of a small batch are long streams on a machine they cannot fill anyway: they get 4x the counters (fewer
     // docID-range passes; the launch has its own LDS size).  q=2: one query 0.57 -> 0.43 ms, 256 queries +30 %.
     a.log2_cnt = std::min<uint32_t>(index->log2_cnt + (n_q <= 4096u ? index->parts_cnt_bonus : 0u), 14u);
-    a.cq_cap = sg_queue_cap(a.log2_cnt, k, roomy, false);
-    const bool g8p = g8;
-    if (g8p && tight) hipLaunchKernelGGL(sg_parts_kernel_tight_g8, dim3(index->parts_grid), dim3(64), lds_bytes(a.log2_cnt, k, roomy), stream, a);
-    else if (g8p) hipLaunchKernelGGL(sg_parts_kernel_g8, dim3(index->parts_grid), dim3(64), lds_bytes(a.log2_cnt, k, roomy), stream, a);
-    else if (tight) hipLaunchKernelGGL(sg_parts_kernel_tight, dim3(index->parts_grid), dim3(64), lds_bytes(a.log2_cnt, k, roomy), stream, a);
-    else hipLaunchKernelGGL(sg_parts_kernel, dim3(index->parts_grid), dim3(64), lds_bytes(a.log2_cnt, k, roomy), stream, a);
+    a.cq_cap = sg_queue_cap(a.log2_cnt, k, p.roomy, false);
+    hipLaunchKernelGGL(parts_kernel(p.tight, p.g8), dim3(index->parts_grid), dim3(64), lds_bytes(a.log2_cnt, k, p.roomy), stream, a);
     HIP_TRY(hipGetLastError());
   }
   if (a.long_list) {   // queries the wavefront kernel listed as beyond its tables: a few workgroups answer them (none listed: they leave at once)
     hipLaunchKernelGGL(sg_long_kernel, dim3(std::min<uint32_t>(n_q, 8u)), dim3(64), 0, stream, a);
     HIP_TRY(hipGetLastError());
   }
-  static const int fill_every = getenv("SG_FILL_EVERY") ? atoi(getenv("SG_FILL_EVERY")) : 4;      // (experiment knob)
-  if ((a.fill_stat || pipe) && fill_every > 0 && (rep->launches.fetch_add(1, std::memory_order_relaxed) % (uint32_t)fill_every) == 0u)
-    // (not hipMemcpyAsync: a 16-byte device-to-host copy blocks the calling thread until the stream has drained — every fourth
-    //  submit of a pipelined host stalled for three batches, 5 ms, and the GPU idled behind it; a store from a kernel into
-    //  mapped host memory is just another launch)
-    { hipLaunchKernelGGL(fill_stat_copy_kernel, dim3(1), dim3(64), 0, stream, (const uint32_t*)rep->d_fill, rep->h_fill_dev); HIP_TRY(hipGetLastError()); }
+  // every fourth launch that fed the statistics block copies it to the host for the controllers (not hipMemcpyAsync: a 16-byte
+  // device-to-host copy blocks the calling thread until the stream has drained — every fourth submit of a pipelined host stalled
+  // for three batches, 5 ms, and the GPU idled behind it; a store from a kernel into mapped host memory is just another launch)
+  if ((a.fill_stat || p.pipe) && (rep->launches.fetch_add(1, std::memory_order_relaxed) % 4u) == 0u) {
+    hipLaunchKernelGGL(fill_stat_copy_kernel, dim3(1), dim3(64), 0, stream, (const uint32_t*)rep->d_fill, rep->h_fill_dev);
+    HIP_TRY(hipGetLastError());
+  }
   return SG_OK;
 }
 
@@ -783,10 +857,10 @@ int fill_replica(sg_index* ix, Replica* r, int device) {
   }
   if ((rc = to_device(r, h.slots.data(), h.slots.size(), &d.slots))) return rc;
   if ((rc = upload_description(h, r, d))) return rc;
-  if ((rc = dev_alloc(r, (size_t)16, &r->d_fill))) return rc;     // the sampler's counters (words 0 .. 5: u32s + the 8-byte aligned u64 chunk counter) and the pipeline's own (PipeArgs::stat)
-  HIP_TRY(hipMemset(r->d_fill, 0, 64));
-  HIP_TRY(hipHostMalloc((void**)&r->h_fill, 64, hipHostMallocMapped));
-  for (int i = 0; i < 16; i++) r->h_fill[i] = 0;
+  if ((rc = dev_alloc(r, (size_t)SG_STAT_WORDS, &r->d_fill))) return rc;     // the statistics block (StatWord: the 64-bit chunk counter 8-byte aligned)
+  HIP_TRY(hipMemset(r->d_fill, 0, SG_STAT_WORDS * 4));
+  HIP_TRY(hipHostMalloc((void**)&r->h_fill, SG_STAT_WORDS * 4, hipHostMallocMapped));
+  for (int i = 0; i < SG_STAT_WORDS; i++) r->h_fill[i] = 0;
   HIP_TRY(hipHostGetDevicePointer((void**)&r->h_fill_dev, r->h_fill, 0));
   if (!h.dups.empty()) {   // documents that repeat a term: side tables for the secondary-entry path
     const uint32_t S32 = h.n_segments;
@@ -1079,7 +1153,10 @@ int sg_suggest_batch_device(sg_index* index, const void* d_q, const void* d_offs
   SG_GUARD_BEGIN
   int rc = check_search_args(index, k, true, similarity, metric);
   if (rc) return rc;
-  return launch(index, replica_of_pointer(index, d_offs), d_q, d_offs, n_q, metric, similarity, k, 0, d_ids, d_scores, d_counts, (hipStream_t)stream);
+  LaunchReq r;
+  r.q = d_q; r.offs = d_offs; r.n_q = n_q; r.metric = metric; r.similarity = similarity; r.k = k;
+  r.ids = d_ids; r.scores = d_scores; r.counts = d_counts; r.stream = (hipStream_t)stream;
+  return launch(index, replica_of_pointer(index, d_offs), r);
   SG_GUARD_END(SG_RC)
 }
 
@@ -1088,7 +1165,10 @@ int sg_autocomplete_batch_device(sg_index* index, const void* d_q, const void* d
   SG_GUARD_BEGIN
   int rc = check_search_args(index, limit, false, 0, 0);
   if (rc) return rc;
-  return launch(index, replica_of_pointer(index, d_offs), d_q, d_offs, n_q, 0, 0, limit, 1, d_ids, nullptr, d_counts, (hipStream_t)stream);
+  LaunchReq r;
+  r.q = d_q; r.offs = d_offs; r.n_q = n_q; r.k = limit; r.autocomplete = 1;
+  r.ids = d_ids; r.counts = d_counts; r.stream = (hipStream_t)stream;
+  return launch(index, replica_of_pointer(index, d_offs), r);
   SG_GUARD_END(SG_RC)
 }
 
@@ -1239,71 +1319,81 @@ static void thread_contexts_release() {
 // the copy back — all asynchronous on the calling thread's stream for that device; finish() waits and hands the rows to the
 // caller's buffers.  A single-replica call is begin + finish; sg_*_batch_multi begins every slice before finishing any, so
 // the GPUs work side by side.
+// The device block of a host-buffer call (slice_begin, async_submit): [scores | ids | counts | aux] — the results, one copy back —
+// then, from the next 16 bytes on, [offsets | queries] — the inputs, one copy in.  Offsets and sizes in bytes.
+struct IoLayout {
+  size_t sc_bytes = 0, id_bytes = 0, cnt_bytes = 0, aux_bytes = 0, off_bytes = 0, q_bytes = 0;
+  size_t ids = 0, cnt = 0, aux = 0, out_bytes = 0, offs = 0, q = 0, in_bytes = 0, total = 0;   // (the scores start the block)
+};
+static IoLayout io_layout(uint32_t n_q, uint32_t k, bool scores, bool aux, size_t q_bytes) {
+  IoLayout L;
+  L.sc_bytes = scores ? (size_t)n_q * k * 8 : 0; L.id_bytes = (size_t)n_q * k * 4; L.cnt_bytes = (size_t)n_q * 4;
+  L.aux_bytes = aux ? (size_t)n_q * k * 4 : 0; L.off_bytes = (size_t)(n_q + 1) * 8; L.q_bytes = q_bytes;
+  Carve c;
+  c.take(L.sc_bytes);
+  L.ids = c.take(L.id_bytes, 4); L.cnt = c.take(L.cnt_bytes, 4); L.aux = c.take(L.aux_bytes, 4);
+  L.out_bytes = c.off;
+  L.offs = c.take(L.off_bytes); L.q = c.take(q_bytes, 8);
+  L.in_bytes = c.off - L.offs; L.total = c.off + 16;
+  return L;
+}
+
 struct HostSlice {
   HostCtx* ctx = nullptr;
   char* dev = nullptr;
   bool staged = false;
-  uint32_t n_q = 0, k = 0;
-  int autocomplete = 0;
-  size_t sc_bytes = 0, id_bytes = 0, cnt_bytes = 0, aux_bytes = 0;
+  IoLayout io{};
   uint32_t* ids = nullptr; double* scores = nullptr; uint32_t* counts = nullptr; uint32_t* aux = nullptr;
 };
 
-static int slice_begin(sg_index* index, Replica* rep, const uint8_t* q, const uint64_t* offs, uint32_t n_q, int metric, double sim,
-                       uint32_t k, int autocomplete, uint32_t* ids, double* scores, uint32_t* counts, HostSlice* s, uint32_t ac_first = 0,
-                       const LaunchExtra* ex = nullptr, uint32_t* aux = nullptr) {
-  s->n_q = n_q; s->k = k; s->autocomplete = autocomplete; s->ids = ids; s->scores = scores; s->counts = counts; s->aux = aux;
+// r: what to search for (metric, similarity, k, autocomplete / by_doc, ac_first, mt); slice_begin adds the buffers and the stream
+static int slice_begin(sg_index* index, Replica* rep, const uint8_t* q, const uint64_t* offs, uint32_t n_q, LaunchReq r,
+                       uint32_t* ids, double* scores, uint32_t* counts, uint32_t* aux, HostSlice* s) {
+  s->ids = ids; s->scores = scores; s->counts = counts; s->aux = aux; s->io = IoLayout{};
   if (n_q == 0) return SG_OK;
   const uint64_t q0 = offs[0];
   if (!q && offs[n_q] != q0) { set_error("null query buffer"); return SG_E_INVALID; }
   HIP_TRY(hipSetDevice(rep->device));
-  // one device block: [scores | ids | counts] (results, one copy back) then [offsets | queries] (inputs, one copy in)
-  const size_t qbytes = (size_t)(offs[n_q] - q0);
-  s->sc_bytes = autocomplete ? 0 : (size_t)n_q * k * 8; s->id_bytes = (size_t)n_q * k * 4; s->cnt_bytes = (size_t)n_q * 4;
-  s->aux_bytes = aux ? (size_t)n_q * k * 4 : 0;
-  const size_t out_bytes = s->sc_bytes + s->id_bytes + s->cnt_bytes + s->aux_bytes, off_bytes = (size_t)(n_q + 1) * 8;
-  const size_t o_in = (out_bytes + 15) & ~(size_t)15, in_bytes = off_bytes + qbytes, total = o_in + in_bytes + 16;
+  const IoLayout& io = s->io = io_layout(n_q, r.k, !r.autocomplete, aux != nullptr, (size_t)(offs[n_q] - q0));
   // a slice of a larger batch starts at a non-zero offset: the offsets are rebased in the staging buffer
   const bool rebase = q0 != 0;
-  int rc = host_ctx(rep->device, rebase ? std::max(in_bytes, std::min(out_bytes, kPinnedMax)) : std::max(in_bytes, out_bytes), &s->ctx);
+  int rc = host_ctx(rep->device, rebase ? std::max(io.in_bytes, std::min(io.out_bytes, kPinnedMax)) : std::max(io.in_bytes, io.out_bytes), &s->ctx);
   if (rc) return rc;
   HostCtx* ctx = s->ctx;
-  s->staged = std::max(in_bytes, out_bytes) <= ctx->pinned_cap;
-  const bool in_staged = s->staged || (rebase && in_bytes <= ctx->pinned_cap);
+  s->staged = std::max(io.in_bytes, io.out_bytes) <= ctx->pinned_cap;
+  const bool in_staged = s->staged || (rebase && io.in_bytes <= ctx->pinned_cap);
   if (rebase && !in_staged) { set_error("batch slice too large to stage"); return SG_E_INVALID; }
   hipStream_t st = ctx->stream;
-  if ((rc = ctx_device_block(ctx, total, &s->dev))) { s->dev = nullptr; return rc; }
+  if ((rc = ctx_device_block(ctx, io.total, &s->dev))) { s->dev = nullptr; return rc; }
   char* dev = s->dev;
 #define TRY2(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { set_error(std::string(#expr) + ": " + hipGetErrorString(e_)); (void)hipStreamSynchronize(st); s->dev = nullptr; return SG_E_HIP; } } while (0)
-  char* d_sc = dev; char* d_ids = dev + s->sc_bytes; char* d_cnt = d_ids + s->id_bytes; char* d_aux = d_cnt + s->cnt_bytes; char* d_offs = dev + o_in; char* d_q = d_offs + off_bytes;
-  LaunchExtra lex;
-  if (ex) { lex = *ex; lex.out_aux = aux ? (uint32_t*)d_aux : nullptr; }
   if (in_staged) {
     uint64_t* po = (uint64_t*)ctx->pinned;
-    if (rebase) for (uint32_t i = 0; i <= n_q; i++) po[i] = offs[i] - q0; else memcpy(po, offs, off_bytes);
-    if (qbytes) memcpy((char*)ctx->pinned + off_bytes, q + q0, qbytes);
-    TRY2(hipMemcpyAsync(d_offs, ctx->pinned, in_bytes, hipMemcpyHostToDevice, st));
+    if (rebase) for (uint32_t i = 0; i <= n_q; i++) po[i] = offs[i] - q0; else memcpy(po, offs, io.off_bytes);
+    if (io.q_bytes) memcpy((char*)ctx->pinned + io.off_bytes, q + q0, io.q_bytes);
+    TRY2(hipMemcpyAsync(dev + io.offs, ctx->pinned, io.in_bytes, hipMemcpyHostToDevice, st));
     if (!s->staged) TRY2(hipStreamSynchronize(st));       // the pinned buffer is not reused for the results, but be explicit
   } else {
-    TRY2(hipMemcpyAsync(d_offs, offs, off_bytes, hipMemcpyHostToDevice, st));
-    if (qbytes) TRY2(hipMemcpyAsync(d_q, q, qbytes, hipMemcpyHostToDevice, st));
+    TRY2(hipMemcpyAsync(dev + io.offs, offs, io.off_bytes, hipMemcpyHostToDevice, st));
+    if (io.q_bytes) TRY2(hipMemcpyAsync(dev + io.q, q, io.q_bytes, hipMemcpyHostToDevice, st));
   }
-  TRY2(hipMemsetAsync(dev, 0, s->sc_bytes + s->id_bytes, st));       // rows of queries with fewer than k results stay zero
+  TRY2(hipMemsetAsync(dev, 0, io.sc_bytes + io.id_bytes, st));       // rows of queries with fewer than k results stay zero
   // (a caller with host buffers knows its longest query: at most 112 bytes + the wrap runes stay within the wavefront
   //  kernel's 144 runes / 128 n-grams, and the long-query launch — a few microseconds of a single query's latency — is left out)
   uint64_t max_len = 0;
   for (uint32_t i = 0; i < n_q; i++) max_len = std::max<uint64_t>(max_len, offs[i + 1] - offs[i]);
-  if (aux) TRY2(hipMemsetAsync(d_aux, 0, s->aux_bytes, st));
-  rc = launch(index, rep, d_q, d_offs, n_q, metric, sim, k, autocomplete, d_ids, autocomplete ? nullptr : d_sc, d_cnt, st, nullptr, nullptr, nullptr, nullptr, ac_first,
-              max_len <= 112, ex ? &lex : nullptr);
+  if (aux) TRY2(hipMemsetAsync(dev + io.aux, 0, io.aux_bytes, st));
+  r.q = dev + io.q; r.offs = dev + io.offs; r.n_q = n_q; r.stream = st; r.no_long_queries = max_len <= 112;
+  r.ids = dev + io.ids; r.scores = r.autocomplete ? nullptr : dev; r.counts = dev + io.cnt; r.out_aux = aux ? (uint32_t*)(dev + io.aux) : nullptr;
+  rc = launch(index, rep, r);
   if (rc) { (void)hipStreamSynchronize(st); s->dev = nullptr; return rc; }
   if (s->staged) {
-    TRY2(hipMemcpyAsync(ctx->pinned, dev, out_bytes, hipMemcpyDeviceToHost, st));
+    TRY2(hipMemcpyAsync(ctx->pinned, dev, io.out_bytes, hipMemcpyDeviceToHost, st));
   } else {
-    if (!autocomplete) TRY2(hipMemcpyAsync(scores, d_sc, s->sc_bytes, hipMemcpyDeviceToHost, st));
-    TRY2(hipMemcpyAsync(ids, d_ids, s->id_bytes, hipMemcpyDeviceToHost, st));
-    TRY2(hipMemcpyAsync(counts, d_cnt, s->cnt_bytes, hipMemcpyDeviceToHost, st));
-    if (aux) TRY2(hipMemcpyAsync(aux, d_aux, s->aux_bytes, hipMemcpyDeviceToHost, st));
+    if (!r.autocomplete) TRY2(hipMemcpyAsync(scores, dev, io.sc_bytes, hipMemcpyDeviceToHost, st));
+    TRY2(hipMemcpyAsync(ids, dev + io.ids, io.id_bytes, hipMemcpyDeviceToHost, st));
+    TRY2(hipMemcpyAsync(counts, dev + io.cnt, io.cnt_bytes, hipMemcpyDeviceToHost, st));
+    if (aux) TRY2(hipMemcpyAsync(aux, dev + io.aux, io.aux_bytes, hipMemcpyDeviceToHost, st));
   }
 #undef TRY2
   return SG_OK;
@@ -1323,19 +1413,26 @@ static int slice_finish(HostSlice* s) {
         memcpy((char*)dst + b, src + b, e - b);
       });
     };
-    if (!s->autocomplete) copy_out(s->scores, h, s->sc_bytes);
-    copy_out(s->ids, h + s->sc_bytes, s->id_bytes);
-    memcpy(s->counts, h + s->sc_bytes + s->id_bytes, s->cnt_bytes);
-    if (s->aux) copy_out(s->aux, h + s->sc_bytes + s->id_bytes + s->cnt_bytes, s->aux_bytes);
+    const IoLayout& io = s->io;
+    if (io.sc_bytes) copy_out(s->scores, h, io.sc_bytes);
+    copy_out(s->ids, h + io.ids, io.id_bytes);
+    memcpy(s->counts, h + io.cnt, io.cnt_bytes);
+    if (s->aux) copy_out(s->aux, h + io.aux, io.aux_bytes);
   }
   return SG_OK;
 }
 
-static int run_host(sg_index* index, Replica* rep, const uint8_t* q, const uint64_t* offs, uint32_t n_q, int metric, double sim,
-                    uint32_t k, int autocomplete, uint32_t* ids, double* scores, uint32_t* counts, uint32_t ac_first = 0,
-                    const LaunchExtra* ex = nullptr, uint32_t* aux = nullptr) {
+// a host-buffer search: metric, similarity, k, autocomplete, ac_first of r (launch() takes the rest from the slice)
+static LaunchReq search_req(int metric, double sim, uint32_t k, int autocomplete, uint32_t ac_first = 0) {
+  LaunchReq r;
+  r.metric = metric; r.similarity = sim; r.k = k; r.autocomplete = autocomplete; r.ac_first = ac_first;
+  return r;
+}
+
+static int run_host(sg_index* index, Replica* rep, const uint8_t* q, const uint64_t* offs, uint32_t n_q, const LaunchReq& r,
+                    uint32_t* ids, double* scores, uint32_t* counts, uint32_t* aux = nullptr) {
   HostSlice s;
-  int rc = slice_begin(index, rep, q, offs, n_q, metric, sim, k, autocomplete, ids, scores, counts, &s, ac_first, ex, aux);
+  int rc = slice_begin(index, rep, q, offs, n_q, r, ids, scores, counts, aux, &s);
   if (rc) return rc;
   return slice_finish(&s);
 }
@@ -1346,7 +1443,7 @@ int sg_suggest_batch(sg_index* index, const uint8_t* q, const uint64_t* offs, ui
   int rc = check_search_args(index, k, true, similarity, metric);
   if (rc) return rc;
   if (!offs || !ids || !scores || !counts) { set_error("null argument"); return SG_E_INVALID; }
-  return run_host(index, find_replica(index, -1), q, offs, n_q, metric, similarity, k, 0, ids, scores, counts);
+  return run_host(index, find_replica(index, -1), q, offs, n_q, search_req(metric, similarity, k, 0), ids, scores, counts);
   SG_GUARD_END(SG_RC)
 }
 
@@ -1356,7 +1453,7 @@ int sg_autocomplete_batch(sg_index* index, const uint8_t* q, const uint64_t* off
   int rc = check_search_args(index, limit, false, 0, 0);
   if (rc) return rc;
   if (!offs || !ids || !counts) { set_error("null argument"); return SG_E_INVALID; }
-  return run_host(index, find_replica(index, -1), q, offs, n_q, 0, 0, limit, 1, ids, nullptr, counts);
+  return run_host(index, find_replica(index, -1), q, offs, n_q, search_req(0, 0, limit, 1), ids, nullptr, counts);
   SG_GUARD_END(SG_RC)
 }
 
@@ -1369,7 +1466,7 @@ int sg_autocomplete_batch_from(sg_index* index, const uint8_t* q, const uint64_t
   int rc = check_search_args(index, limit, false, 0, 0);
   if (rc) return rc;
   if (!offs || !ids || !counts) { set_error("null argument"); return SG_E_INVALID; }
-  return run_host(index, find_replica(index, -1), q, offs, n_q, 0, 0, limit, 1, ids, nullptr, counts, first_doc);
+  return run_host(index, find_replica(index, -1), q, offs, n_q, search_req(0, 0, limit, 1, first_doc), ids, nullptr, counts);
   SG_GUARD_END(SG_RC)
 }
 
@@ -1449,9 +1546,9 @@ int sg_suggest_batch_tables(sg_index* index, const uint8_t* q, const uint64_t* o
   if (rc) return rc;
   if (!offs || !ids || !scores || !counts || !tables) { set_error("null argument"); return SG_E_INVALID; }
   if ((rc = check_tables(index, tables))) return rc;
-  LaunchExtra ex;
-  ex.mt = &tables->tab;
-  return run_host(index, find_replica(index, -1), q, offs, n_q, SG_JACCARD, 0.5, k, 0, ids, scores, counts, 0, &ex);
+  LaunchReq r = search_req(SG_JACCARD, 0.5, k, 0);
+  r.mt = &tables->tab;
+  return run_host(index, find_replica(index, -1), q, offs, n_q, r, ids, scores, counts);
   SG_GUARD_END(SG_RC)
 }
 
@@ -1469,10 +1566,10 @@ int sg_suggest_batch_from(sg_index* index, const uint8_t* q, const uint64_t* off
   if (rc) return rc;
   if (!offs || !ids || !scores || !counts) { set_error("null argument"); return SG_E_INVALID; }
   if ((rc = check_tables(index, tables))) return rc;
-  LaunchExtra ex;
-  ex.by_doc = 1;
-  if (tables) { ex.mt = &tables->tab; metric = SG_JACCARD; similarity = 0.5; }
-  return run_host(index, find_replica(index, -1), q, offs, n_q, metric, similarity, limit, 0, ids, scores, counts, first_doc, &ex, aux);
+  LaunchReq r = tables ? search_req(SG_JACCARD, 0.5, limit, 0, first_doc) : search_req(metric, similarity, limit, 0, first_doc);
+  r.by_doc = true;
+  if (tables) r.mt = &tables->tab;
+  return run_host(index, find_replica(index, -1), q, offs, n_q, r, ids, scores, counts, aux);
   SG_GUARD_END(SG_RC)
 }
 
@@ -1623,10 +1720,9 @@ static int async_submit(sg_index* index, const uint8_t* q, const uint64_t* offs,
     HIP_TRY(hipEventCreateWithFlags(&sl->ev_out, hipEventDisableTiming));
   }
   // ---- the slot's device block: [scores | ids | counts] then [offsets | queries], as the synchronous path lays it out ----
-  const size_t qbytes = (size_t)(offs[n_q] - q0);
-  t->sc_bytes = autocomplete ? 0 : (size_t)n_q * k * 8; t->id_bytes = (size_t)n_q * k * 4; t->cnt_bytes = (size_t)n_q * 4;
-  const size_t out_bytes = t->sc_bytes + t->id_bytes + t->cnt_bytes, off_bytes = (size_t)(n_q + 1) * 8;
-  const size_t o_in = (out_bytes + 15) & ~(size_t)15, in_bytes = off_bytes + qbytes, total = o_in + in_bytes + 16;
+  const IoLayout io = io_layout(n_q, k, !autocomplete, false, (size_t)(offs[n_q] - q0));
+  const size_t qbytes = io.q_bytes, out_bytes = io.out_bytes, off_bytes = io.off_bytes, in_bytes = io.in_bytes, total = io.total;
+  t->sc_bytes = io.sc_bytes; t->id_bytes = io.id_bytes; t->cnt_bytes = io.cnt_bytes;
   if (total > sl->dev_cap) {      // (the slot is free: nothing of an earlier ticket is in flight on it)
     if (sl->dev) (void)hipFree(sl->dev);
     sl->dev = nullptr; sl->dev_cap = 0;
@@ -1635,7 +1731,7 @@ static int async_submit(sg_index* index, const uint8_t* q, const uint64_t* offs,
     sl->dev_cap = cap;
   }
   char* dev = sl->dev;
-  char* d_sc = dev; char* d_ids = dev + t->sc_bytes; char* d_cnt = d_ids + t->id_bytes; char* d_offs = dev + o_in; char* d_q = d_offs + off_bytes;
+  char* d_sc = dev; char* d_ids = dev + io.ids; char* d_cnt = dev + io.cnt; char* d_offs = dev + io.offs; char* d_q = dev + io.q;
   mark(0);
   // ---- copy in: straight from pinned caller memory, else through the slot's staging buffer ----
   const bool in_direct = q0 == 0 && is_pinned_host(offs, off_bytes) && (qbytes == 0 || is_pinned_host(q, qbytes));
@@ -1658,8 +1754,10 @@ static int async_submit(sg_index* index, const uint8_t* q, const uint64_t* offs,
   HIP_TRY(hipStreamWaitEvent(pool->s_run, sl->ev_in, 0));
   uint64_t max_len = 0;
   for (uint32_t i = 0; i < n_q; i++) max_len = std::max<uint64_t>(max_len, offs[i + 1] - offs[i]);
-  int rc = launch(index, rep, d_q, d_offs, n_q, metric, sim, k, autocomplete, d_ids, autocomplete ? nullptr : d_sc, d_cnt, pool->s_run, nullptr, nullptr,
-                  nullptr, nullptr, ac_first, max_len <= 112);
+  LaunchReq r = search_req(metric, sim, k, autocomplete, ac_first);
+  r.q = d_q; r.offs = d_offs; r.n_q = n_q; r.stream = pool->s_run; r.no_long_queries = max_len <= 112;
+  r.ids = d_ids; r.scores = autocomplete ? nullptr : d_sc; r.counts = d_cnt;
+  int rc = launch(index, rep, r);
   if (rc) { (void)hipStreamSynchronize(pool->s_run); return rc; }
   mark(2);
   HIP_TRY(hipEventRecord(sl->ev_run, pool->s_run));
@@ -1844,14 +1942,14 @@ static int run_multi(sg_index* index, const uint8_t* q, const uint64_t* offs, ui
   std::vector<Replica*> reps;
   { std::lock_guard<std::mutex> lock(index->mu); for (auto& r : index->replicas) reps.push_back(r.get()); }
   const uint32_t R = (uint32_t)reps.size();
-  if (R <= 1 || n_q < 2 * R) return run_host(index, reps[0], q, offs, n_q, metric, sim, k, autocomplete, ids, scores, counts);
+  if (R <= 1 || n_q < 2 * R) return run_host(index, reps[0], q, offs, n_q, search_req(metric, sim, k, autocomplete), ids, scores, counts);
   MultiPool* pool = multi_pool_of(index, R);
   std::vector<MultiTask> tasks(R);
   for (uint32_t r = 0; r < R; r++) {
     const uint32_t lo = (uint32_t)((uint64_t)n_q * r / R), hi = (uint32_t)((uint64_t)n_q * (r + 1) / R);
     Replica* rep = reps[r];
     tasks[r].fn = [=]() {
-      return run_host(index, rep, q, offs + lo, hi - lo, metric, sim, k, autocomplete, ids + (size_t)lo * k,
+      return run_host(index, rep, q, offs + lo, hi - lo, search_req(metric, sim, k, autocomplete), ids + (size_t)lo * k,
                       scores ? scores + (size_t)lo * k : nullptr, counts + lo);
     };
     MultiWorker* w = pool->workers[r].get();
@@ -1961,8 +2059,8 @@ static void coalescer_lane(Coalescer* c, Replica* rep) {
       for (OneReq* r : batch) { blob.insert(blob.end(), r->q, r->q + r->len); offs.push_back(blob.size()); }
       ids.resize((size_t)n * k); counts.resize(n);
       if (!f.autocomplete) scores.resize((size_t)n * k);
-      rc = run_host(c->index, rep, blob.data(), offs.data(), n, f.metric, f.sim, k, f.autocomplete, ids.data(),
-                    f.autocomplete ? nullptr : scores.data(), counts.data(), f.ac_first);
+      rc = run_host(c->index, rep, blob.data(), offs.data(), n, search_req(f.metric, f.sim, k, f.autocomplete, f.ac_first), ids.data(),
+                    f.autocomplete ? nullptr : scores.data(), counts.data());
       if (rc) err = g_err;
     } catch (const std::exception& e) { rc = SG_E_NOMEM; err = e.what(); }
     for (uint32_t i = 0; i < n; i++) {
@@ -2305,15 +2403,14 @@ static int lm_upload(sg_lm* lm, int device) {
 static int predict_on_device(sg_index* index, sg_lm* lm, Replica* rep, const uint8_t* d_q, const uint64_t* d_offs, uint32_t n_q, uint64_t q_bytes,
                              uint32_t top_k, double similarity, uint32_t* d_out_ids, uint32_t* d_out_counts, hipStream_t st) {
   const HostLM& h = lm->host;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { const size_t at = off; off = (off + bytes + 15) & ~(size_t)15; return at; };
-  const size_t o_aids = take((size_t)n_q * top_k * 4), o_acnt = take((size_t)n_q * 4), o_fids = take((size_t)n_q * top_k * 4), o_fcnt = take((size_t)n_q * 4),
-               o_zero_end = off,
-               o_from = take((size_t)n_q * 4), o_to = take((size_t)n_q * 4), o_sel = take((size_t)n_q * 4), o_stat = take(n_q),
-               o_ctx = take((size_t)n_q * 32), o_clen = take(n_q), o_hasw = take(n_q), o_wlen = take((size_t)n_q * 4),
-               o_woff = take((size_t)(n_q + 1) * 8), o_words = take((size_t)q_bytes * 2 + 16);
+  Carve c;
+  const size_t o_aids = c.take((size_t)n_q * top_k * 4), o_acnt = c.take((size_t)n_q * 4), o_fids = c.take((size_t)n_q * top_k * 4), o_fcnt = c.take((size_t)n_q * 4),
+               o_zero_end = c.size(),
+               o_from = c.take((size_t)n_q * 4), o_to = c.take((size_t)n_q * 4), o_sel = c.take((size_t)n_q * 4), o_stat = c.take(n_q),
+               o_ctx = c.take((size_t)n_q * 32), o_clen = c.take(n_q), o_hasw = c.take(n_q), o_wlen = c.take((size_t)n_q * 4),
+               o_woff = c.take((size_t)(n_q + 1) * 8), o_words = c.take((size_t)q_bytes * 2 + 16);
   void* blk = nullptr;
-  if (int rc = stream_scratch(rep->device, st, off, &blk, 1)) return rc;
+  if (int rc = stream_scratch(rep->device, st, c.size(), &blk, SCRATCH_PREDICT)) return rc;
   char* dev = (char*)blk;
   HIP_TRY(hipMemsetAsync(dev, 0, o_zero_end, st));                 // autocomplete / fuzzy rows and counts, the selection counter
   SpellArgs p{};
@@ -2343,12 +2440,16 @@ static int predict_on_device(sg_index* index, sg_lm* lm, Replica* rep, const uin
   HIP_TRY(hipGetLastError());
   const LmRanges ranges{lm->d_values, p.lm_from, p.lm_to};
   // (the launch orders its queries itself — shortest last words first: they match the most — from the lengths in w_len)
-  int rc = launch(index, rep, p.w_blob, p.w_off, n_q, 0, 0, top_k, 1, dev + o_aids, nullptr, dev + o_acnt, st, &ranges, nullptr, nullptr, p.w_len);
+  LaunchReq r;
+  r.q = p.w_blob; r.offs = p.w_off; r.n_q = n_q; r.k = top_k; r.autocomplete = 1;
+  r.ids = dev + o_aids; r.counts = dev + o_acnt; r.stream = st; r.lm = &ranges; r.len = p.w_len;
+  int rc = launch(index, rep, r);
   if (rc) return rc;
   hipLaunchKernelGGL(spell_select_kernel, dim3(gb), dim3(256), 0, st, p);
   HIP_TRY(hipGetLastError());
-  rc = launch(index, rep, p.w_blob, p.w_off, n_q, SG_COSINE, similarity, top_k, 0, dev + o_fids, nullptr, dev + o_fcnt, st, nullptr, nullptr, nullptr, p.w_len, 0, false,
-              nullptr, p.sel_flag);
+  r.metric = SG_COSINE; r.similarity = similarity; r.autocomplete = 0;     // (the same queries: the Cosine search of those the selection flagged)
+  r.ids = dev + o_fids; r.counts = dev + o_fcnt; r.lm = nullptr; r.flag = p.sel_flag;
+  rc = launch(index, rep, r);
   if (rc) return rc;
   hipLaunchKernelGGL(spell_merge_kernel, dim3(n_q), dim3(64), (size_t)top_k * 24, st, p);
   HIP_TRY(hipGetLastError());
@@ -2468,11 +2569,11 @@ int sg_index_launch_stats(sg_index* index, uint64_t out[4]) {
   HIP_TRY(hipGetDevice(&prev_dev));
   struct Restore { int d; ~Restore() { if (d >= 0) (void)hipSetDevice(d); } } restore{prev_dev};
   HIP_TRY(hipSetDevice(rep->device));
-  uint32_t w[6] = {0, 0, 0, 0, 0, 0};
+  uint32_t w[SG_STAT_WORDS] = {0};
   HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(w, rep->d_fill, 24, hipMemcpyDeviceToHost));
-  for (int i = 0; i < 3; i++) out[i] = w[i];
-  out[3] = (uint64_t)w[4] | ((uint64_t)w[5] << 32);               // (the chunk counter is 64 bits wide: a long-list batch streams 10^8 chunks per launch over its sampled queries)
+  HIP_TRY(hipMemcpy(w, rep->d_fill, sizeof w, hipMemcpyDeviceToHost));
+  out[0] = w[SG_STAT_FULL]; out[1] = w[SG_STAT_SAMPLED]; out[2] = w[SG_STAT_RESULTS];
+  out[3] = (uint64_t)w[SG_STAT_CHUNKS] | ((uint64_t)w[SG_STAT_CHUNKS + 1] << 32);               // (the chunk counter is 64 bits wide: a long-list batch streams 10^8 chunks per launch over its sampled queries)
   return SG_OK;
   SG_GUARD_END(SG_RC)
 }
@@ -2490,10 +2591,10 @@ int sg_index_pipe_stats(sg_index* index, uint64_t out[4]) {
   HIP_TRY(hipGetDevice(&prev_dev));
   struct Restore { int d; ~Restore() { if (d >= 0) (void)hipSetDevice(d); } } restore{prev_dev};
   HIP_TRY(hipSetDevice(rep->device));
-  uint32_t w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  uint32_t w[SG_STAT_WORDS] = {0};
   HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(w, rep->d_fill, 32, hipMemcpyDeviceToHost));
-  out[0] = w[3]; out[1] = w[6]; out[2] = w[7]; out[3] = rep->pipe_queries.load(std::memory_order_relaxed);
+  HIP_TRY(hipMemcpy(w, rep->d_fill, sizeof w, hipMemcpyDeviceToHost));
+  out[0] = w[SG_STAT_UNPLANNED]; out[1] = w[SG_STAT_OVERFLOW]; out[2] = w[SG_STAT_REPEATS]; out[3] = rep->pipe_queries.load(std::memory_order_relaxed);
   return SG_OK;
   SG_GUARD_END(SG_RC)
 }
@@ -2512,12 +2613,12 @@ int sg_index_pipe_volumes(sg_index* index, uint64_t out[8]) {
   HIP_TRY(hipGetDevice(&prev_dev));
   struct Restore { int d; ~Restore() { if (d >= 0) (void)hipSetDevice(d); } } restore{prev_dev};
   HIP_TRY(hipSetDevice(rep->device));
-  uint32_t w[16] = {0};
+  uint32_t w[SG_STAT_WORDS] = {0};
   HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(w, rep->d_fill, 64, hipMemcpyDeviceToHost));
-  for (int i = 0; i < 5; i++) out[i] = w[8 + i];
+  HIP_TRY(hipMemcpy(w, rep->d_fill, sizeof w, hipMemcpyDeviceToHost));
+  for (int i = 0; i < 5; i++) out[i] = w[SG_STAT_PLANNED + i];
   out[5] = rep->packed_chunks; out[6] = pipe_wide(index, rep) ? 1u : 0u;
-  out[7] = index->pipe_shape_fixed ? 3u : rep->pipe_last_shape.load(std::memory_order_relaxed);   // the stream workgroup of the latest launch: 0 / 1 / 2 = 2 / 4 / 8 wavefronts, 3 = the knobs' own
+  out[7] = index->pipe_shape_fixed ? 3u : rep->shape_floor.last.load(std::memory_order_relaxed);   // the stream workgroup of the latest launch: 0 / 1 / 2 = 2 / 4 / 8 wavefronts, 3 = the knobs' own
   return SG_OK;
   SG_GUARD_END(SG_RC)
 }
@@ -2532,9 +2633,11 @@ int sg_debug_tune_choice(double est_query_chunks, double max_term_chunks, int32_
   return SG_OK;
 }
 int sg_debug_pipe_shape(double est_query_chunks, double terms_per_doc, int32_t t_floor, int32_t metric, double similarity, int32_t* out_shape) {
+  SG_GUARD_BEGIN
   if (!out_shape || metric < SG_JACCARD || metric > SG_OVERLAP || !(similarity > 0 && similarity <= 1)) { set_error("bad argument"); return SG_E_INVALID; }
   *out_shape = (int32_t)pipe_shape_model(est_query_chunks, terms_per_doc, t_floor, metric, similarity);
   return SG_OK;
+  SG_GUARD_END(SG_RC)
 }
 int sg_debug_tune_index(sg_index* ix, double out_stats[2], int32_t out[6]) {
   SG_GUARD_BEGIN

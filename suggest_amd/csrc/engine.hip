@@ -133,6 +133,25 @@ struct MetricTab {   // [a] = query cardinality 0..a_max, [b] = segment 0..S-1, 
   uint32_t a_max, S;
 };
 
+// The words of a replica's statistics block (Replica::d_fill = BatchArgs::fill_stat = PipeArgs::stat), cumulative, wrapping at
+// 2^32.  0 .. 5 are the tightening sampler's (one fuzzy query in 32 of a large batch), 3 / 6 / 7 what the pipeline handed back to the
+// fused kernel, 8 .. 12 the pipeline's sampled volumes (one query in 256).  fill_stat_copy_kernel mirrors all of it to the host.
+enum StatWord : uint32_t {
+  SG_STAT_FULL = 0,          // sampled fuzzy queries whose top-k ended full
+  SG_STAT_SAMPLED = 1,       // sampled fuzzy queries
+  SG_STAT_RESULTS = 2,       // their results
+  SG_STAT_UNPLANNED = 3,     // queries the plan handed back
+  SG_STAT_CHUNKS = 4,        // u64 (words 4 and 5): 16-byte chunks of postings the sampled queries streamed
+  SG_STAT_OVERFLOW = 6,      // queries whose candidates overflowed their slots
+  SG_STAT_REPEATS = 7,       // queries with a matching document that repeats a term
+  SG_STAT_PLANNED = 8,       // sampled queries the plan expressed ...
+  SG_STAT_GROUPS = 9,        // ... their groups (plan items)
+  SG_STAT_LISTS = 10,        // ... streamed lists
+  SG_STAT_ROWS = 11,         // ... rows of 64 lanes
+  SG_STAT_CANDS = 12,        // ... candidates the stream launch pushed
+  SG_STAT_WORDS = 16,        // words of the block
+};
+
 struct BatchArgs {
   DeviceIndex ix;
   const uint8_t* q_blob;
@@ -184,7 +203,7 @@ struct BatchArgs {
   // ---- the tokeniser as a launch of its own (sg_terms_kernel, big batches): the search kernel then starts from the term ids ----
   int32_t* pre_A;         // [n_q] d_tokenize's result per query (null: the search kernel tokenises itself)
   uint32_t* pre_terms;    // [n_q][SG_MAX_A] its term ids
-  uint32_t* fill_stat;    // {sampled fuzzy queries whose top-k ended full, sampled fuzzy queries, their results, -, u64: 16-byte chunks of postings they streamed}: cumulative
+  uint32_t* fill_stat;    // the replica's statistics block (StatWord: words SG_STAT_FULL .. SG_STAT_CHUNKS here); null: no sampling
   uint32_t fill_mask;     // ... sampled: queries with (index & fill_mask) == 0 — one in 32 of a large batch, every one of a small
   unsigned long long* prof;  // phase cycle counters (only read by SG_PHASE_TIMING builds)
   uint32_t dbg_skip;         // ablation bits (SG_PHASE_TIMING builds only; results are wrong when set)
@@ -2012,7 +2031,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kG8 ? 2 : 3,
     const bool sampled = !kLM && !a.autocomplete && a.fill_stat && (qi & a.fill_mask) == 0u;
     if (!kParts) {                                         // the queued parts all run later: count this one as finished
       if (lane == 0) { a.slot_ctl[2 * qi] = 1u; a.slot_ctl[2 * qi + 1] = pushed + 1u; }
-      if (sampled && lane == 0) atomicAdd((unsigned long long*)(a.fill_stat + 4), (unsigned long long)q_chunks);
+      if (sampled && lane == 0) atomicAdd((unsigned long long*)(a.fill_stat + SG_STAT_CHUNKS), (unsigned long long)q_chunks);
       break;
     }
     // release: this part's rows are visible device-wide (across the XCDs' L2s) before it is counted; acquire: the
@@ -2021,7 +2040,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kG8 ? 2 : 3,
     if (lane == 0) fin = __hip_atomic_fetch_add(a.slot_ctl + 2 * my_slot, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) + 1u;
     fin = __builtin_amdgcn_readfirstlane(fin);
     const uint32_t n_parts = __builtin_amdgcn_readfirstlane(a.slot_ctl[2 * my_slot + 1]);   // written by the first launch
-    if (fin != n_parts) { if (sampled && lane == 0) atomicAdd((unsigned long long*)(a.fill_stat + 4), (unsigned long long)q_chunks); break; }   // somebody else finishes later and merges
+    if (fin != n_parts) { if (sampled && lane == 0) atomicAdd((unsigned long long*)(a.fill_stat + SG_STAT_CHUNKS), (unsigned long long)q_chunks); break; }   // somebody else finishes later and merges
     for (uint32_t pp = 0; pp < n_parts; pp++) {
       if (pp == my_part) continue;
       const uint32_t np = __builtin_amdgcn_readfirstlane(__hip_atomic_load(a.part_n + pbase + pp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
@@ -2058,10 +2077,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kG8 ? 2 : 3,
   }
   if (lane == 0) a.out_counts[qi] = n;
   if (!kLM && !a.autocomplete && a.fill_stat && lane == 0 && (qi & a.fill_mask) == 0u) {
-    atomicAdd(a.fill_stat + 1, 1u);
-    if (n == k) atomicAdd(a.fill_stat, 1u);
-    if (n) atomicAdd(a.fill_stat + 2, n);
-    atomicAdd((unsigned long long*)(a.fill_stat + 4), (unsigned long long)q_chunks);
+    atomicAdd(a.fill_stat + SG_STAT_SAMPLED, 1u);
+    if (n == k) atomicAdd(a.fill_stat + SG_STAT_FULL, 1u);
+    if (n) atomicAdd(a.fill_stat + SG_STAT_RESULTS, n);
+    atomicAdd((unsigned long long*)(a.fill_stat + SG_STAT_CHUNKS), (unsigned long long)q_chunks);
   }
   if (DBG_SKIP(8192u) && lane == 0 && k >= 6) { out_ids[k - 1] = (uint32_t)A; out_ids[k - 3] = qi; }
   PH(7)
@@ -2854,9 +2873,9 @@ __global__ __launch_bounds__(256) void host_store_kernel(const HostStoreArgs h) 
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < h.n16[sgm]; i += stride) h.dst[sgm][i] = h.src[sgm][i];
 }
 
-// the sampled fill counters (BatchArgs::fill_stat) -> mapped host memory (see launch())
+// the statistics block (StatWord) -> mapped host memory, where the launch controllers read it (capi.inc)
 __global__ void fill_stat_copy_kernel(const uint32_t* src, uint32_t* dst_host) {
-  if (threadIdx.x < 16u) dst_host[threadIdx.x] = src[threadIdx.x];    // (words 3, 6, 7: what the pipeline left to the fused kernel; 8 .. 12: its sampled volumes)
+  if (threadIdx.x < SG_STAT_WORDS) dst_host[threadIdx.x] = src[threadIdx.x];
 }
 
 // test hook (sg_debug_pairsort): the device's restatement of Go 1.14 sort.Sort on arbitrary keys — a differential fuzz

@@ -95,9 +95,9 @@ struct PipeArgs {
                       // behind the end of a list idles for 2^sub_log2 - 1 chunks at most
   uint32_t log2_cnt;  // u32 counters of a stream workgroup = buckets a group may use
   uint32_t dt_rows;   // rows (of 64 >> sub_log2 sub-row descriptors) a stream workgroup's LDS table holds: a query's groups together
-  // the pipeline's own counters (the replica's d_fill block; always on, whatever the tightening sampler does): words 3 / 6 / 7
-  // queries the plan could not express / whose candidates overflowed their slots / with a matching document that repeats a term;
-  // words 8 .. 12 over the sampled queries ((query & stat_mask) == 0): planned queries, their groups, lists, rows, candidates
+  // the pipeline's own counters in the replica's statistics block (always on, whatever the tightening sampler does): what it
+  // handed back (SG_STAT_UNPLANNED / _OVERFLOW / _REPEATS) and its volumes over the sampled queries ((query & stat_mask) == 0),
+  // SG_STAT_PLANNED .. SG_STAT_CANDS
   uint32_t* stat;
   uint32_t stat_mask;
 };
@@ -143,7 +143,7 @@ __device__ __forceinline__ void plan_one_query(const BatchArgs& a, const PipeArg
     if (lane == 0) { a.out_counts[qi] = status; p.cand_n[s] = SG_PIPE_SKIP; *(uint4*)vrec = make_uint4(0u, qi, 0u, 0u); *(uint4*)rec = make_uint4(0u, 0u, SG_PIPE_NO_OVF, 0u); }
   };
   auto fallback = [&]() {                                   // the fused kernel answers this query
-    if (lane == 0) { p.fb_list[atomicAdd(p.fb_n, 1u)] = qi; p.cand_n[s] = SG_PIPE_SKIP; *(uint4*)vrec = make_uint4(0u, qi, 0u, 0u); *(uint4*)rec = make_uint4(0u, 0u, SG_PIPE_NO_OVF, 0u); atomicAdd(p.stat + 3, 1u); }
+    if (lane == 0) { p.fb_list[atomicAdd(p.fb_n, 1u)] = qi; p.cand_n[s] = SG_PIPE_SKIP; *(uint4*)vrec = make_uint4(0u, qi, 0u, 0u); *(uint4*)rec = make_uint4(0u, 0u, SG_PIPE_NO_OVF, 0u); atomicAdd(p.stat + SG_STAT_UNPLANNED, 1u); }
   };
   PLAN_STAGE(1u)
   if (A < 0) {                                               // beyond the wavefront kernels' tables: sg_long_kernel
@@ -335,8 +335,8 @@ __device__ __forceinline__ void plan_one_query(const BatchArgs& a, const PipeArg
     *(uint4*)rec = make_uint4(n_items, doff, ovf_blk, rows_total);
     *(uint4*)vrec = make_uint4(0u, qi, (uint32_t)A, 0u);
     p.cand_n[s] = 0u;
-    if (a.fill_stat && (qi & a.fill_mask) == 0u) atomicAdd((unsigned long long*)(a.fill_stat + 4), (unsigned long long)q_chunks);
-    if ((qi & p.stat_mask) == 0u) { atomicAdd(p.stat + 8, 1u); atomicAdd(p.stat + 9, n_items); atomicAdd(p.stat + 10, doff); atomicAdd(p.stat + 11, rows_total); }
+    if (a.fill_stat && (qi & a.fill_mask) == 0u) atomicAdd((unsigned long long*)(a.fill_stat + SG_STAT_CHUNKS), (unsigned long long)q_chunks);
+    if ((qi & p.stat_mask) == 0u) { atomicAdd(p.stat + SG_STAT_PLANNED, 1u); atomicAdd(p.stat + SG_STAT_GROUPS, n_items); atomicAdd(p.stat + SG_STAT_LISTS, doff); atomicAdd(p.stat + SG_STAT_ROWS, rows_total); }
   }
 }
 
@@ -597,13 +597,13 @@ __device__ __forceinline__ void verify_one_query(const BatchArgs& a, const PipeA
   const uint32_t n_c = rfl(n_c_v), qi = readlane(f.h, 1);
   if (n_c >= SG_PIPE_SKIP) return;                            // status written by the plan / the fused kernel answers
   if (n_c > p.cand_cap) {                                     // more flagged postings than the slots hold: the fused kernel answers
-    if (lane == 0) { p.fb_list[atomicAdd(p.fb_n, 1u)] = qi; atomicAdd(p.stat + 6, 1u); }
+    if (lane == 0) { p.fb_list[atomicAdd(p.fb_n, 1u)] = qi; atomicAdd(p.stat + SG_STAT_OVERFLOW, 1u); }
     return;
   }
   const bool sampled = a.fill_stat && (qi & a.fill_mask) == 0u;
-  if (lane == 0 && n_c && (qi & p.stat_mask) == 0u) atomicAdd(p.stat + 12, n_c);
+  if (lane == 0 && n_c && (qi & p.stat_mask) == 0u) atomicAdd(p.stat + SG_STAT_CANDS, n_c);
   if (n_c == 0u) {
-    if (lane == 0) { a.out_counts[qi] = 0u; if (sampled) atomicAdd(a.fill_stat + 1, 1u); }
+    if (lane == 0) { a.out_counts[qi] = 0u; if (sampled) atomicAdd(a.fill_stat + SG_STAT_SAMPLED, 1u); }
     return;
   }
   VERIFY_STAGE(1u)
@@ -735,7 +735,7 @@ __device__ __forceinline__ void verify_one_query(const BatchArgs& a, const PipeA
     __syncthreads();
   }
   if (give_up) {
-    if (lane == 0) { p.fb_list[atomicAdd(p.fb_n, 1u)] = qi; atomicAdd(p.stat + 7, 1u); }
+    if (lane == 0) { p.fb_list[atomicAdd(p.fb_n, 1u)] = qi; atomicAdd(p.stat + SG_STAT_REPEATS, 1u); }
     return;
   }
   VERIFY_STAGE(4u)
@@ -758,7 +758,7 @@ __device__ __forceinline__ void verify_one_query(const BatchArgs& a, const PipeA
   }
   if (lane == 0) {
     a.out_counts[qi] = n;
-    if (sampled) { atomicAdd(a.fill_stat + 1, 1u); if (n == k) atomicAdd(a.fill_stat, 1u); if (n) atomicAdd(a.fill_stat + 2, n); }
+    if (sampled) { atomicAdd(a.fill_stat + SG_STAT_SAMPLED, 1u); if (n == k) atomicAdd(a.fill_stat + SG_STAT_FULL, 1u); if (n) atomicAdd(a.fill_stat + SG_STAT_RESULTS, n); }
   }
 }
 

@@ -69,7 +69,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8), amdgp
     if (which && first) { a.out_counts[qi] = status; p.cand_n[s] = SG_PIPE_SKIP; *(uint4*)vrec = make_uint4(0u, qi, 0u, 0u); *(uint4*)rec = make_uint4(0u, 0u, SG_PIPE_NO_OVF, 0u); }
   };
   auto to_fused = [&](bool which) {                          // the fused kernel answers
-    if (which && first) { p.fb_list[atomicAdd(p.fb_n, 1u)] = qi; p.cand_n[s] = SG_PIPE_SKIP; *(uint4*)vrec = make_uint4(0u, qi, 0u, 0u); *(uint4*)rec = make_uint4(0u, 0u, SG_PIPE_NO_OVF, 0u); atomicAdd(p.stat + 3, 1u); }
+    if (which && first) { p.fb_list[atomicAdd(p.fb_n, 1u)] = qi; p.cand_n[s] = SG_PIPE_SKIP; *(uint4*)vrec = make_uint4(0u, qi, 0u, 0u); *(uint4*)rec = make_uint4(0u, 0u, SG_PIPE_NO_OVF, 0u); atomicAdd(p.stat + SG_STAT_UNPLANNED, 1u); }
   };
 
   // ---- tokenise (pkg/suggest/tokenizer.go:9-34), the ASCII path of d_tokenize for two queries side by side ----
@@ -310,8 +310,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8), amdgp
     *(uint4*)rec = make_uint4(n_items, doff, ovf_blk, rows_total);
     *(uint4*)vrec = make_uint4(0u, qi, (uint32_t)A, 0u);
     p.cand_n[s] = 0u;
-    if (a.fill_stat && (qi & a.fill_mask) == 0u) atomicAdd((unsigned long long*)(a.fill_stat + 4), (unsigned long long)q_chunks);
-    if ((qi & p.stat_mask) == 0u) { atomicAdd(p.stat + 8, 1u); atomicAdd(p.stat + 9, n_items); atomicAdd(p.stat + 10, doff); atomicAdd(p.stat + 11, rows_total); }
+    if (a.fill_stat && (qi & a.fill_mask) == 0u) atomicAdd((unsigned long long*)(a.fill_stat + SG_STAT_CHUNKS), (unsigned long long)q_chunks);
+    if ((qi & p.stat_mask) == 0u) { atomicAdd(p.stat + SG_STAT_PLANNED, 1u); atomicAdd(p.stat + SG_STAT_GROUPS, n_items); atomicAdd(p.stat + SG_STAT_LISTS, doff); atomicAdd(p.stat + SG_STAT_ROWS, rows_total); }
   }
   }
   // ---- the queries that were not simple (non-ASCII text, more than 32 n-grams or segments, a larger table, text to trim): one at
