@@ -324,6 +324,20 @@ int sg_debug_tune_choice(double est_query_chunks, double max_term_chunks, int32_
  * 2^11 / 2^12 / 2^13 counters.  No GPU needed; no reference counterpart. */
 int sg_debug_pipe_shape(double est_query_chunks, double terms_per_doc, int32_t t_floor, int32_t metric, double similarity, int32_t* out_shape);
 int sg_debug_tune_index(sg_index* index, double out_stats[2], int32_t out[6]);
+/* Test hook, off by default: with on = 1 or 2 every call of the process first fills the working memory and result rows it is meant to
+ * write before it reads with a pattern (1: 0xA5 bytes, 2: 0x5A bytes; item queue, part counts, query lists and term ids take values a
+ * kernel can read safely — capi.inc, "Test-only poison"), so that a read of a word the call did not write shows as a wrong row.
+ * Rows past a query's count then hold the pattern instead of zeros.  on = 0: off (the default).  sg_debug_poison_stats: bytes poisoned
+ * by the calling thread since its last call, per region — out = {split queue / HBM top-k rows / ordered list (SCRATCH_ROWS),
+ * pipeline fb_list, tokeniser launch, long-query list, Predict rows, result ids + aux, result scores, result counts}; clears them. */
+int sg_debug_poison(uint32_t on);
+int sg_debug_poison_stats(uint64_t out[8]);
+/* Test hooks (no GPU needed): the carving of a launch's SCRATCH_ROWS block for n_q queries, top-k k, split queries on / off and the
+ * query order off (0), with atomics (1) or with per-block histograms (2): out = {s, id, split, items, slot, part_n, part_s, part_id, ord,
+ * ord_ctl, bytes, slot_cap, item_cap, ord_blocks, SG_MAX_PARTS, SG_ORDER_CTL_WORDS}; and of its SCRATCH_PIPE block: out = {rec, vrec,
+ * ovf, cand_n, fb_list, bytes, piece, vrec_words, ovf_cap, SG_PIPE_REC_STRIDE, SG_PIPE_OVF_WORDS, SG_PIPE_PIECE}.  Offsets in bytes. */
+int sg_debug_rows_layout(uint32_t n_q, uint32_t k, int32_t split, int32_t reorder, uint64_t out[16]);
+int sg_debug_pipe_layout(uint32_t n_q, uint32_t cand_cap, uint64_t out[12]);
 /* [r6] Test hook: out[0] = the device ordinal of replica number `replica`, out[1..7] = the device its posting store, seg_off, orig_of,
  * forward-index records and terms, term table and counter block are resident on (-1: null).  All must equal out[0]. */
 int sg_debug_replica_devices(sg_index* index, uint32_t replica, int32_t out[8]);

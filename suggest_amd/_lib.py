@@ -24,6 +24,7 @@ EXPORTS = [
     "sg_lm_score_word_ids", "sg_lm_next_score", "sg_lm_tokenize", "sg_spell_index_build", "sg_spell_predict_batch", "sg_spell_predict_batch_device",
     "sg_index_replicate", "sg_index_replicas", "sg_suggest_batch_multi", "sg_autocomplete_batch_multi", "sg_suggest_one", "sg_autocomplete_one", "sg_autocomplete_one_from", "sg_autocomplete_batch_from",
     "sg_lm_load_google_ex", "sg_lm_load_binary", "sg_lm_level", "sg_lm_order", "sg_index_tune", "sg_index_forward", "sg_autocomplete_algorithmic_bytes", "sg_debug_pairsort", "sg_debug_tune_choice", "sg_debug_pipe_shape", "sg_debug_tune_index", "sg_debug_replica_devices",
+    "sg_debug_poison", "sg_debug_poison_stats", "sg_debug_rows_layout", "sg_debug_pipe_layout",
     "sg_host_alloc", "sg_host_free", "sg_suggest_submit", "sg_suggest_submit_on", "sg_autocomplete_submit", "sg_ticket_wait",
     "sg_metric_tables_create", "sg_metric_tables_retain", "sg_metric_tables_release", "sg_suggest_batch_tables", "sg_suggest_batch_from", "sg_index_launch_stats", "sg_index_pipe_stats", "sg_index_pipe_volumes",
 ]
@@ -71,6 +72,10 @@ def lib():
     if hasattr(L, "sg_debug_pipe_shape"): L.sg_debug_pipe_shape.argtypes = [dbl, dbl, i32, i32, dbl, vp]
     if hasattr(L, "sg_debug_tune_index"): L.sg_debug_tune_index.argtypes = [vp, vp, vp]
     if hasattr(L, "sg_debug_replica_devices"): L.sg_debug_replica_devices.argtypes = [vp, u32, vp]
+    if hasattr(L, "sg_debug_poison"): L.sg_debug_poison.argtypes = [u32]
+    if hasattr(L, "sg_debug_poison_stats"): L.sg_debug_poison_stats.argtypes = [vp]
+    if hasattr(L, "sg_debug_rows_layout"): L.sg_debug_rows_layout.argtypes = [u32, u32, i32, i32, vp]
+    if hasattr(L, "sg_debug_pipe_layout"): L.sg_debug_pipe_layout.argtypes = [u32, u32, vp]
     if hasattr(L, "sg_autocomplete_algorithmic_bytes"): L.sg_autocomplete_algorithmic_bytes.argtypes = [vp, vp, vp, u32, u32, C.POINTER(u64)]
     if hasattr(L, "sg_index_forward"): L.sg_index_forward.argtypes = [vp, u32, u32, u32, vp, vp, vp]
     if hasattr(L, "sg_index_replicas"): L.sg_index_replicas.argtypes = [vp, vp, u32]
@@ -147,3 +152,32 @@ def check(rc):
     if rc < 0:
         raise SuggestHipError(rc, lib().sg_last_error().decode("utf-8", "replace"))
     return rc
+
+
+POISON_REGIONS = ("rows", "pipe", "pretok", "long_list", "predict", "out_ids", "out_scores", "out_counts")
+POISON_WORD = {1: 0xA5A5A5A5, 2: 0x5A5A5A5A}
+
+
+def poison_stats():
+    """Bytes the calling thread's calls poisoned per region since the last call of this function (sg_debug_poison_stats)."""
+    out = (C.c_uint64 * 8)()
+    check(lib().sg_debug_poison_stats(out))
+    return dict(zip(POISON_REGIONS, (int(x) for x in out)))
+
+
+class poisoned:
+    """Test hook: `with poisoned(1):` every call first fills the scratch and result rows it is meant to write with a pattern
+    (family 1: 0xA5 bytes, 2: 0x5A bytes; include/suggest_hip.h, sg_debug_poison).  Rows past a query's count then hold the
+    pattern instead of zeros.  Process-wide: off again on leaving."""
+
+    def __init__(self, family=1):
+        self.family = family
+
+    def __enter__(self):
+        check(lib().sg_debug_poison(self.family))
+        poison_stats()
+        return self
+
+    def __exit__(self, *exc):
+        check(lib().sg_debug_poison(0))
+        return False

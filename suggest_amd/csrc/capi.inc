@@ -410,6 +410,12 @@ struct LaunchPlan {
   bool two = false; Plan2Args p2{};    // sg_plan2_kernel (two queries per wavefront) and its LDS
 };
 
+// the split-query queue's sizes: a slot per query (the parts' rows of all slots below 1 GiB), four items per query
+void split_caps(LaunchPlan& p, uint32_t n_q, uint32_t k) {
+  p.slot_cap = (uint32_t)std::min<size_t>(n_q, ((size_t)1 << 30) / ((size_t)SG_MAX_PARTS * k * 12));
+  p.item_cap = std::min<uint32_t>(std::max<uint32_t>(n_q * 4u, 4096u), 262144u);
+}
+
 LaunchPlan plan_launch(sg_index* index, Replica* rep, const LaunchReq& r) {
   const uint32_t n_q = r.n_q, k = r.k;
   const volatile uint32_t* h = rep->h_fill;
@@ -441,10 +447,7 @@ LaunchPlan plan_launch(sg_index* index, Replica* rep, const LaunchReq& r) {
     // an index whose queries do not come near the threshold (4x the expected volume) pays nothing for the machinery
     if (4.0 * index->est_query_chunks * pk < (double)p.split_min) p.split_min = 0;
   }
-  if (p.split_min) {
-    p.slot_cap = (uint32_t)std::min<size_t>(n_q, ((size_t)1 << 30) / ((size_t)SG_MAX_PARTS * k * 12));
-    p.item_cap = std::min<uint32_t>(std::max<uint32_t>(n_q * 4u, 4096u), 262144u);
-  }
+  if (p.split_min) split_caps(p, n_q, k);
   if (!r.lm && p.mode == 0) {
     p.tight = index->tighten == 1;
     if (index->tighten == 2 && h) { p.tight = rep->tighten.step(h, r.similarity); p.sample = true; }
@@ -533,6 +536,37 @@ PipeLayout pipe_layout(uint32_t n_q, uint32_t cand_cap) {
   return L;
 }
 
+// ---- Test-only poison (sg_debug_poison; off by default).  While it is on, every region a call is meant to write before it reads —
+// its share of the per-stream scratch blocks and the result rows of a host-buffer call — is filled first, on the call's stream, so that
+// a read of a word this call did not write returns a pattern instead of an earlier call's leftover.  Regions launch() zeroes stay
+// zeroed.  A value is chosen region by region so that a stale read can only make a row wrong, never send a kernel out of its arrays:
+//   docIDs, score bits, slot words, aux words: the family's byte pattern (0xA5... / 0x5A...) — ids are copied and compared, never
+//     indexed with; a slot's part total of 0xA5A5A5A5 never equals the finished count (<= SG_MAX_PARTS): no merge, the count shows it;
+//   queue items: 0xFFFFFFFF, the hole marker (the parts launch skips it);
+//   part_n: k, the largest count a part's row has: a stale count reads k entries of that part's poisoned row, inside the block;
+//   lists of query numbers (the ordered list, the pipeline's fb_list, the long-query list's entries): 0, a query of every batch;
+//   the tokeniser launch's n-gram counts: 0 (an empty query), its term ids: kNoTerm, which every reader skips.
+// Left alone: the pipeline's records, verify records, overflow blocks and candidate counts (offsets and loop bounds of the stream /
+// verify launches, with no value that is safe whatever a stale word meets), the ordering launch's control words and histograms.
+// Cost when off: one load of the switch and a few untaken branches per call; nothing more is enqueued. ----
+std::atomic<uint32_t> g_poison{0};             // 0 off, 1 the 0xA5 family, 2 the 0x5A family
+enum PoisonRegion { PZ_ROWS = 0, PZ_PIPE = 1, PZ_PRETOK = 2, PZ_LONG_LIST = 3, PZ_PREDICT = 4, PZ_OUT_IDS = 5, PZ_OUT_SCORES = 6, PZ_OUT_COUNTS = 7 };
+thread_local uint64_t t_poisoned[8];           // bytes poisoned per region by this thread's calls since sg_debug_poison_stats
+inline uint32_t poison_mode() { return g_poison.load(std::memory_order_relaxed); }
+inline uint32_t poison_word() { return poison_mode() == 2 ? 0x5A5A5A5Au : 0xA5A5A5A5u; }
+int poison_fill(void* p, size_t bytes, PoisonRegion r, hipStream_t st) {       // the family's byte pattern
+  if (!bytes) return SG_OK;
+  HIP_TRY(hipMemsetAsync(p, (int)(poison_word() & 0xFFu), bytes, st));
+  t_poisoned[r] += bytes;
+  return SG_OK;
+}
+int poison_words(void* p, size_t n, uint32_t v, PoisonRegion r, hipStream_t st) {   // n 32-bit words of v
+  if (!n) return SG_OK;
+  HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)p, (int)v, n, st));
+  t_poisoned[r] += n * 4;
+  return SG_OK;
+}
+
 BatchArgs batch_args(const sg_index* index, const Replica* rep, const LaunchReq& r, const LaunchPlan& p) {
   BatchArgs a{};
   a.ix = rep->dix;
@@ -608,6 +642,27 @@ BatchKernel parts_kernel(bool tight, bool g8) {
   return g8 ? (tight ? sg_parts_kernel_tight_g8 : sg_parts_kernel_g8) : (tight ? sg_parts_kernel_tight : sg_parts_kernel);
 }
 
+// sg_debug_poison: the SCRATCH_ROWS block's regions (see poison_fill) — HBM top-k rows, the split-query queue but its zeroed control
+// head, the ordered list of the queries but its control words.  by_doc_tables: a docID-ordered launch under a tabulated metric
+// turns a row's score bits into table positions, so its HBM score rows are left alone.
+int poison_rows(const LaunchPlan& p, const RowsLayout& R, char* b, uint32_t n_q, uint32_t k, bool by_doc_tables, hipStream_t st) {
+  int rc = SG_OK;
+  if (k > SG_K_LDS) {
+    if (!by_doc_tables && (rc = poison_fill(b + R.s, (size_t)n_q * k * 8, PZ_ROWS, st))) return rc;
+    if ((rc = poison_fill(b + R.id, (size_t)n_q * k * 4, PZ_ROWS, st))) return rc;
+  } else if (p.split_min) {
+    const size_t parts = (size_t)p.slot_cap * SG_MAX_PARTS;
+    HIP_TRY(hipMemsetAsync(b + R.items, 0xFF, (size_t)p.item_cap * 16, st));
+    t_poisoned[PZ_ROWS] += (size_t)p.item_cap * 16;
+    if ((rc = poison_fill(b + R.slot, (size_t)p.slot_cap * 8, PZ_ROWS, st))) return rc;
+    if ((rc = poison_words(b + R.part_n, parts, k, PZ_ROWS, st))) return rc;
+    if ((rc = poison_fill(b + R.part_s, parts * k * 8, PZ_ROWS, st))) return rc;
+    if ((rc = poison_fill(b + R.part_id, parts * k * 4, PZ_ROWS, st))) return rc;
+  }
+  if (p.reorder && (rc = poison_words(b + R.ord, n_q, 0u, PZ_ROWS, st))) return rc;
+  return SG_OK;
+}
+
 // Every batch goes through here: plan, allocate, enqueue.
 int launch(sg_index* index, Replica* rep, const LaunchReq& r) {
   const uint32_t n_q = r.n_q, k = r.k;
@@ -642,11 +697,14 @@ int launch(sg_index* index, Replica* rep, const LaunchReq& r) {
     if (int rc = stream_scratch(rep->device, stream, ((size_t)n_q + 1) * 4, &blk, SCRATCH_LONG_LIST)) return rc;
     a.long_list = (uint32_t*)blk;
   }
+  const bool poison = poison_mode() != 0;
+  if (poison && a.long_list) if (int rc = poison_words(a.long_list + 1, n_q, 0u, PZ_LONG_LIST, stream)) return rc;   // (not the count)
   const RowsLayout R = rows_layout(p, n_q, k);
   uint32_t* order_ctl = nullptr;            // (ctl[1], ctl[2]: the pipeline's counts of queries handed back and overflow blocks — zeroed with it)
   if (R.bytes) {
     if (int rc = stream_scratch(rep->device, stream, R.bytes, &blk, SCRATCH_ROWS)) return rc;
     char* b = (char*)blk;
+    if (poison) if (int rc = poison_rows(p, R, b, n_q, k, r.mt != nullptr && p.mode == 2, stream)) return rc;
     if (k > SG_K_LDS) { a.scratch_s = (uint64_t*)(b + R.s); a.scratch_id = (uint32_t*)(b + R.id); }
     if (p.split_min) {
       HIP_TRY(hipMemsetAsync(b + R.split, 0, 64, stream));    // queue control words
@@ -672,6 +730,7 @@ int launch(sg_index* index, Replica* rep, const LaunchReq& r) {
   const PipeLayout P = pipe_layout(n_q, index->pipe_cand_cap);
   void* pipe_blk = nullptr;
   if (p.pipe && stream_scratch(rep->device, stream, P.bytes, &pipe_blk, SCRATCH_PIPE) != SG_OK) { p.pipe = false; (void)hipGetLastError(); }
+  if (p.pipe && poison) if (int rc = poison_words((char*)pipe_blk + P.fb_list, (size_t)n_q + 1, 0u, PZ_PIPE, stream)) return rc;
   if (p.pipe) rep->pipe_queries.fetch_add(n_q, std::memory_order_relaxed);
   else if (p.pretok) {   // every query of the batch in the caller's numbering (the search launch may run them in another order), or the caller's subset
     Carve c;
@@ -679,6 +738,10 @@ int launch(sg_index* index, Replica* rep, const LaunchReq& r) {
     void* pt = nullptr;
     if (int rc = stream_scratch(rep->device, stream, c.size(), &pt, SCRATCH_PRETOK)) return rc;
     a.pre_A = (int32_t*)((char*)pt + o_A); a.pre_terms = (uint32_t*)((char*)pt + o_terms);
+    if (poison) {
+      if (int rc = poison_words(a.pre_A, n_q, 0u, PZ_PRETOK, stream)) return rc;
+      if (int rc = poison_words(a.pre_terms, (size_t)n_q * SG_MAX_A, kNoTerm, PZ_PRETOK, stream)) return rc;
+    }
     BatchArgs ta = a;
     if (!r.flag) { ta.q_sel = r.sel; ta.q_sel_n = r.sel_n; }      // (the caller's subset; a flagged subset: the list just made)
     hipLaunchKernelGGL(sg_terms_kernel, dim3(n_q), dim3(64), 0, stream, ta);
@@ -1338,6 +1401,15 @@ static IoLayout io_layout(uint32_t n_q, uint32_t k, bool scores, bool aux, size_
   return L;
 }
 
+// sg_debug_poison: a host-buffer call's result rows — scores, ids, counts, aux — in place of the zeroed rows
+static int poison_results(char* dev, const IoLayout& io, hipStream_t st) {
+  int rc;
+  if ((rc = poison_fill(dev, io.sc_bytes, PZ_OUT_SCORES, st))) return rc;
+  if ((rc = poison_fill(dev + io.ids, io.id_bytes, PZ_OUT_IDS, st))) return rc;
+  if ((rc = poison_fill(dev + io.cnt, io.cnt_bytes, PZ_OUT_COUNTS, st))) return rc;
+  return poison_fill(dev + io.aux, io.aux_bytes, PZ_OUT_IDS, st);
+}
+
 struct HostSlice {
   HostCtx* ctx = nullptr;
   char* dev = nullptr;
@@ -1377,12 +1449,13 @@ static int slice_begin(sg_index* index, Replica* rep, const uint8_t* q, const ui
     TRY2(hipMemcpyAsync(dev + io.offs, offs, io.off_bytes, hipMemcpyHostToDevice, st));
     if (io.q_bytes) TRY2(hipMemcpyAsync(dev + io.q, q, io.q_bytes, hipMemcpyHostToDevice, st));
   }
-  TRY2(hipMemsetAsync(dev, 0, io.sc_bytes + io.id_bytes, st));       // rows of queries with fewer than k results stay zero
+  if (poison_mode()) { if ((rc = poison_results(dev, io, st))) { (void)hipStreamSynchronize(st); s->dev = nullptr; return rc; } }
+  else TRY2(hipMemsetAsync(dev, 0, io.sc_bytes + io.id_bytes, st));   // rows of queries with fewer than k results stay zero
   // (a caller with host buffers knows its longest query: at most 112 bytes + the wrap runes stay within the wavefront
   //  kernel's 144 runes / 128 n-grams, and the long-query launch — a few microseconds of a single query's latency — is left out)
   uint64_t max_len = 0;
   for (uint32_t i = 0; i < n_q; i++) max_len = std::max<uint64_t>(max_len, offs[i + 1] - offs[i]);
-  if (aux) TRY2(hipMemsetAsync(dev + io.aux, 0, io.aux_bytes, st));
+  if (aux && !poison_mode()) TRY2(hipMemsetAsync(dev + io.aux, 0, io.aux_bytes, st));
   r.q = dev + io.q; r.offs = dev + io.offs; r.n_q = n_q; r.stream = st; r.no_long_queries = max_len <= 112;
   r.ids = dev + io.ids; r.scores = r.autocomplete ? nullptr : dev; r.counts = dev + io.cnt; r.out_aux = aux ? (uint32_t*)(dev + io.aux) : nullptr;
   rc = launch(index, rep, r);
@@ -1747,7 +1820,8 @@ static int async_submit(sg_index* index, const uint8_t* q, const uint64_t* offs,
   }
   // (rows of queries with fewer than k results stay zero: cleared here, beside the previous ticket's search launch — on the
   //  run stream the 8 MB fill was 0.09 ms between two search launches)
-  HIP_TRY(hipMemsetAsync(dev, 0, t->sc_bytes + t->id_bytes, pool->s_in));
+  if (poison_mode()) { if (int rc = poison_results(dev, io, pool->s_in)) return rc; }
+  else HIP_TRY(hipMemsetAsync(dev, 0, t->sc_bytes + t->id_bytes, pool->s_in));
   HIP_TRY(hipEventRecord(sl->ev_in, pool->s_in));
   mark(1);
   // ---- run: every search launch of the replica's tickets on ONE stream ----
@@ -2413,6 +2487,10 @@ static int predict_on_device(sg_index* index, sg_lm* lm, Replica* rep, const uin
   if (int rc = stream_scratch(rep->device, st, c.size(), &blk, SCRATCH_PREDICT)) return rc;
   char* dev = (char*)blk;
   HIP_TRY(hipMemsetAsync(dev, 0, o_zero_end, st));                 // autocomplete / fuzzy rows and counts, the selection counter
+  if (poison_mode()) {   // (sg_debug_poison: the two launches' id rows — the merge reads a row up to its count and compares the ids)
+    if (int rc = poison_fill(dev + o_aids, (size_t)n_q * top_k * 4, PZ_PREDICT, st)) return rc;
+    if (int rc = poison_fill(dev + o_fids, (size_t)n_q * top_k * 4, PZ_PREDICT, st)) return rc;
+  }
   SpellArgs p{};
   p.values = lm->d_values; p.child_begin = lm->d_child_begin;
   for (size_t l = 0; l < h.level.size(); l++) {
@@ -2636,6 +2714,43 @@ int sg_debug_pipe_shape(double est_query_chunks, double terms_per_doc, int32_t t
   SG_GUARD_BEGIN
   if (!out_shape || metric < SG_JACCARD || metric > SG_OVERLAP || !(similarity > 0 && similarity <= 1)) { set_error("bad argument"); return SG_E_INVALID; }
   *out_shape = (int32_t)pipe_shape_model(est_query_chunks, terms_per_doc, t_floor, metric, similarity);
+  return SG_OK;
+  SG_GUARD_END(SG_RC)
+}
+int sg_debug_poison(uint32_t on) {
+  SG_GUARD_BEGIN
+  if (on > 2u) { set_error("poison: 0 off, 1 or 2 a pattern family"); return SG_E_INVALID; }
+  g_poison.store(on, std::memory_order_relaxed);
+  return SG_OK;
+  SG_GUARD_END(SG_RC)
+}
+int sg_debug_poison_stats(uint64_t out[8]) {
+  SG_GUARD_BEGIN
+  if (!out) { set_error("null argument"); return SG_E_INVALID; }
+  for (int i = 0; i < 8; i++) { out[i] = t_poisoned[i]; t_poisoned[i] = 0; }
+  return SG_OK;
+  SG_GUARD_END(SG_RC)
+}
+int sg_debug_rows_layout(uint32_t n_q, uint32_t k, int32_t split, int32_t reorder, uint64_t out[16]) {
+  SG_GUARD_BEGIN
+  if (!out || n_q == 0 || k == 0 || reorder < 0 || reorder > 2) { set_error("bad argument"); return SG_E_INVALID; }
+  LaunchPlan p;
+  if (split && k <= SG_K_LDS) { p.split_min = 1; split_caps(p, n_q, k); }
+  p.reorder = reorder != 0; p.ord_blocks = (n_q + 1023u) / 1024u; p.ord_direct = reorder == 2;
+  const RowsLayout L = rows_layout(p, n_q, k);
+  const uint64_t v[16] = {L.s, L.id, L.split, L.items, L.slot, L.part_n, L.part_s, L.part_id, L.ord, L.ord_ctl, L.bytes,
+                          p.slot_cap, p.item_cap, p.ord_blocks, SG_MAX_PARTS, SG_ORDER_CTL_WORDS};
+  for (int i = 0; i < 16; i++) out[i] = v[i];
+  return SG_OK;
+  SG_GUARD_END(SG_RC)
+}
+int sg_debug_pipe_layout(uint32_t n_q, uint32_t cand_cap, uint64_t out[12]) {
+  SG_GUARD_BEGIN
+  if (!out || n_q == 0 || cand_cap == 0) { set_error("bad argument"); return SG_E_INVALID; }
+  const PipeLayout L = pipe_layout(n_q, cand_cap);
+  const uint64_t v[12] = {L.rec, L.vrec, L.ovf, L.cand_n, L.fb_list, L.bytes, L.piece, L.vrec_words, L.ovf_cap,
+                          SG_PIPE_REC_STRIDE, SG_PIPE_OVF_WORDS, SG_PIPE_PIECE};
+  for (int i = 0; i < 12; i++) out[i] = v[i];
   return SG_OK;
   SG_GUARD_END(SG_RC)
 }

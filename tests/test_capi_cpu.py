@@ -241,3 +241,84 @@ def test_tuner_choices_are_pinned(cars_lines, words_lines):
     blob, offs = synth.make_dict(200000, seed=1)      # uniform strings: the longest term a tenth of a query's volume, like the headline
     (est, longest), got = built(NGramIndex(blob=blob, offs=offs, description=IndexDescription(**synth.DESCRIPTION), upload=False))
     assert 450 < est < 800 and longest < 0.25 * est and got == dict(log2_cnt=11, level=4, pipe=1, stream=SMALL), (est, longest, got)
+
+
+def _rows_layout(n_q, k, split, reorder):
+    import ctypes as C
+    from suggest_amd import _lib
+    out = (C.c_uint64 * 16)()
+    _lib.check(_lib.lib().sg_debug_rows_layout(n_q, k, split, reorder, out))
+    return dict(zip(("s", "id", "split", "items", "slot", "part_n", "part_s", "part_id", "ord", "ord_ctl", "bytes",
+                     "slot_cap", "item_cap", "ord_blocks", "max_parts", "ctl_words"), (int(x) for x in out)))
+
+
+def _assert_carved(regions, total):
+    """regions: name -> (offset, bytes, alignment).  Every region aligned, inside the block, no two overlapping."""
+    live = sorted((off, off + size, name) for name, (off, size, align) in regions.items() if size)
+    for name, (off, size, align) in regions.items():
+        assert off % align == 0, (name, off, align)
+        assert off + size <= total, (name, off, size, total)
+    for (_, e0, a), (b1, _, b) in zip(live, live[1:]):
+        assert e0 <= b1, ("overlap", a, b)
+
+
+def test_scratch_rows_layout_is_disjoint_and_sized():
+    """The SCRATCH_ROWS block as launch() carves it (capi.inc rows_layout): the HBM top-k rows (k > SG_K_LDS = 64) or the
+    split-query queue — a 64-byte control head, items, slot words, the parts' counts, score rows and id rows, slot_cap x
+    SG_MAX_PARTS x k entries — then the ordered list of the queries and its control words (+ block histograms on the direct
+    path).  Regions pairwise disjoint, aligned for their widest access, inside the block's size."""
+    for n_q in (1, 2, 63, 1000, 4096, 8191, 8192, 65536, 131073, 1 << 21):
+        for k in (1, 64, 65, 65536):
+            for split in (0, 1):
+                for reorder in (0, 1, 2):
+                    L = _rows_layout(n_q, k, split, reorder)
+                    ctx = (n_q, k, split, reorder)
+                    reg = {}
+                    if k > 64:
+                        assert L["split"] == L["items"] == 0 and L["slot_cap"] == 0, ctx
+                        reg["s"] = (L["s"], n_q * k * 8, 8)
+                        reg["id"] = (L["id"], n_q * k * 4, 4)
+                    elif split:
+                        P, sc, ic = L["max_parts"], L["slot_cap"], L["item_cap"]
+                        assert P == 32 and 1 <= sc <= n_q and sc * P * k * 12 <= 1 << 30, ctx
+                        assert ic == min(max(n_q * 4, 4096), 262144), ctx
+                        reg["split"] = (L["split"], 64, 16)
+                        reg["items"] = (L["items"], ic * 16, 16)
+                        reg["slot"] = (L["slot"], sc * 8, 8)
+                        reg["part_n"] = (L["part_n"], sc * P * 4, 4)
+                        reg["part_s"] = (L["part_s"], sc * P * k * 8, 8)
+                        reg["part_id"] = (L["part_id"], sc * P * k * 4, 4)
+                    else:
+                        assert L["bytes"] == 0 or reorder, ctx
+                    if reorder:
+                        blocks = (n_q + 1023) // 1024
+                        assert L["ord_blocks"] == blocks, ctx
+                        reg["ord"] = (L["ord"], n_q * 4, 4)
+                        # control words, then (direct path) a 1024-byte histogram per block of the ordering launch
+                        reg["ord_ctl"] = (L["ord_ctl"], L["ctl_words"] * 4 + (blocks * 1024 if reorder == 2 else 0), 16)
+                    else:
+                        assert L["ord"] == L["ord_ctl"] == 0, ctx
+                    assert L["bytes"] % 16 == 0, ctx
+                    _assert_carved(reg, L["bytes"])
+                    # nothing but these regions: the block ends within 16 bytes (+ alignment) of the last one
+                    if reg:
+                        assert L["bytes"] - max(o + s for o, s, _ in reg.values()) < 16, ctx
+
+
+def test_scratch_pipe_layout_is_disjoint_and_sized():
+    """The SCRATCH_PIPE block (capi.inc pipe_layout): fb_n / ovf_n, then a piece's records (256-byte aligned), verify records,
+    overflow blocks, candidate counts, and the batch's list of the queries handed back — n_q + 1 words, whatever the piece."""
+    import ctypes as C
+    from suggest_amd import _lib
+    for n_q in (1, 2, 63, 1000, 65535, 65536, 65537, 1 << 21):
+        for cand_cap in (1, 2, 16, 64, 512, 4096):
+            out = (C.c_uint64 * 12)()
+            _lib.check(_lib.lib().sg_debug_pipe_layout(n_q, cand_cap, out))
+            rec, vrec, ovf, cand_n, fb_list, total, piece, vrec_words, ovf_cap, rec_stride, ovf_words, piece_max = (int(x) for x in out)
+            ctx = (n_q, cand_cap)
+            assert piece == min(n_q, piece_max) and ovf_cap == max(piece // 8, 64), ctx
+            assert vrec_words >= 32 and vrec_words % 32 == 0, ctx          # whole 128-byte lines
+            reg = {"counters": (0, 8, 4), "rec": (rec, piece * rec_stride * 4, 256), "vrec": (vrec, piece * vrec_words * 4, 16),
+                   "ovf": (ovf, ovf_cap * ovf_words * 4, 16), "cand_n": (cand_n, piece * 4, 16), "fb_list": (fb_list, (n_q + 1) * 4, 16)}
+            assert total % 16 == 0, ctx
+            _assert_carved(reg, total)

@@ -623,18 +623,39 @@ def test_long_queries_are_answered_on_the_device():
     assert int(g_cnt.sum()) >= len(prefixes) - 2
 
 
-@pytest.mark.parametrize("seed", [300004, 700812])
+@pytest.mark.parametrize("seed", [300004, 700812, 610200998, 77700102924])
 def test_fuzz_regressions(seed, monkeypatch):
     """Trials of tools/fuzz_parity.py that found bugs: 300004 — device builder and the empty term (empty pad); 700812 — a u8
-    counter wrapping within one batch (a query repeating one term 33 times, 2 KB of counters) went unnoticed."""
+    counter wrapping within one batch (a query repeating one term 33 times, 2 KB of counters) went unnoticed.  610200998 and
+    77700102924: the two reports nobody could replay — run as their hunts ran, behind pipeline launches on the
+    same thread and stream, and with the scratch and result rows poisoned (sg_debug_poison), so that a word no launch of the
+    trial wrote shows as a wrong row instead of an earlier call's leftover."""
     import importlib.util
+    from suggest_amd import _lib
     spec = importlib.util.spec_from_file_location("fuzz_parity", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools", "fuzz_parity.py"))
     fz = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(fz)
     t = fz.make_trial(seed)
-    for name, value in t["env"].items():
+    with _lib.poisoned(1):
+        _pipeline_launches_first(monkeypatch)
+        for name, value in t["env"].items():
+            monkeypatch.setenv(name, value)
+        assert fz.run_trial(t) == []
+
+
+def _pipeline_launches_first(monkeypatch):
+    """a pipeline trial on this thread's stream: its SCRATCH_ROWS / PIPE blocks are what the next launches inherit"""
+    from suggest_amd import NGramIndex, IndexDescription, synth
+    blob, offs = synth.make_dict(12000, seed=5)
+    qb, qo = synth.make_queries(300, blob, offs, seed=6)
+    for name, value in dict(SG_PIPE="1", SG_PRETOK="1", SG_ORDER="64", SG_TIGHTEN="0", SG_SPLIT_CHUNKS="0", SG_G8="0").items():
         monkeypatch.setenv(name, value)
-    assert fz.run_trial(t) == []
+    gpu = NGramIndex(blob=blob, offs=offs, description=IndexDescription(**synth.DESCRIPTION))
+    ora = oracle.OracleIndex(blob=blob, offs=offs, **synth.DESCRIPTION)
+    for metric, a, k in (("jaccard", 0.5, 64), ("cosine", 0.3, 10), ("dice", 0.9, 300)):
+        assert_same(gpu.suggest_batch(blob=qb, offs=qo, metric=metric, similarity=a, k=k), ora.suggest_batch(qb, qo, metric, a, k))
+    assert gpu.pipe_stats()["queries"] >= 3 * 300
+    gpu.close()
 
 
 def test_low_similarity_over_near_duplicates_stays_fast():
