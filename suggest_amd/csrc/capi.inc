@@ -27,6 +27,24 @@ using namespace sg;
   catch (const std::exception& e_) { set_error(std::string("internal error: ") + e_.what()); return on_fail(SG_E_INVALID); }
 #define SG_RC(x) (x)
 
+// Makes a device the calling thread's current one for the rest of a scope and puts the previous one back at its end:
+// `DeviceGuard dg; HIP_TRY(dg.set(device));`
+struct DeviceGuard {
+  int prev = -1, cur = -1;
+  hipError_t set(int device) {
+    if (prev < 0) {
+      const hipError_t e = hipGetDevice(&prev);
+      if (e != hipSuccess) { prev = -1; return e; }
+      cur = prev;
+    }
+    if (device == cur) return hipSuccess;
+    const hipError_t e = hipSetDevice(device);
+    if (e == hipSuccess) cur = device;
+    return e;
+  }
+  ~DeviceGuard() { if (prev >= 0 && cur != prev) (void)hipSetDevice(prev); }
+};
+
 // ---- the launch controllers (plan_launch): each reads the words of the replica's statistics block it needs from the host's copy,
 // and keeps what it saw last ----
 
@@ -290,6 +308,32 @@ struct LaunchReq {
   const uint8_t* flag = nullptr;      // only the queries this [n_q] array marks (Predict's fuzzy launch)
 };
 
+size_t block_capacity(size_t bytes) {
+  if (bytes > ((size_t)64 << 20)) return (bytes + ((size_t)64 << 20) - 1) & ~(((size_t)64 << 20) - 1);
+  size_t cap = (size_t)1 << 16;
+  while (cap < bytes) cap <<= 1;
+  return cap;
+}
+// A grow-only block of device memory (hipMalloc) or pinned host memory (hipHostMalloc) of block_capacity bytes — a power of two
+// from 64 KiB on, a multiple of 64 MiB above that: growing frees the old block (its contents are lost) and allocates a larger one
+struct GrowBlock {
+  bool host = false;
+  void* p = nullptr;
+  size_t cap = 0;
+  void release() {
+    if (p) (void)(host ? hipHostFree(p) : hipFree(p));
+    p = nullptr; cap = 0;
+  }
+  int grow(size_t bytes) {
+    if (bytes <= cap) return SG_OK;
+    release();
+    const size_t c = block_capacity(bytes);
+    if (host) HIP_TRY(hipHostMalloc(&p, c, hipHostMallocDefault)); else HIP_TRY(hipMalloc(&p, c));
+    cap = c;
+    return SG_OK;
+  }
+};
+
 // Working memory of a launch (top-k rows above SG_K_LDS, the split-query queue): one grow-only buffer per calling thread
 // and (device, stream), reused by that thread's next launch on the stream — which is ordered behind this one.  No
 // stream-ordered pool: its blocks were seen handed to a second stream while the first still used them (callers on
@@ -298,26 +342,20 @@ struct LaunchReq {
 // A block per tag: one launch holds SCRATCH_ROWS, SCRATCH_LONG_LIST and one of SCRATCH_PRETOK / SCRATCH_PIPE of its stream at
 // once, and Predict's block besides when Predict is the caller — four at most.
 enum ScratchTag { SCRATCH_ROWS = 0, SCRATCH_PREDICT = 1, SCRATCH_LONG_LIST = 2, SCRATCH_PRETOK = 3, SCRATCH_PIPE = 4 };
-struct ScratchSlot { int device; hipStream_t stream; int tag; void* p; size_t cap; };
+struct ScratchSlot { int device; hipStream_t stream; int tag; GrowBlock blk; };
 inline bool on_main_thread() { return (long)getpid() == (long)syscall(SYS_gettid); }
 // (a thread that ends hands its buffers back; the main thread's are left to process exit, when the HIP runtime may already
 //  be going down)
 struct ThreadScratch {
   std::vector<ScratchSlot> slots;
   void release() {
-    for (auto& x : slots) if (x.p && hipSetDevice(x.device) == hipSuccess) (void)hipFree(x.p);
+    for (auto& x : slots) if (x.blk.p && hipSetDevice(x.device) == hipSuccess) x.blk.release();
     slots.clear();
   }
   ~ThreadScratch() { if (!slots.empty() && !on_main_thread()) release(); }
 };
 thread_local ThreadScratch t_scratch_owner;
 #define t_scratch (t_scratch_owner.slots)
-size_t block_capacity(size_t bytes) {
-  if (bytes > ((size_t)64 << 20)) return (bytes + ((size_t)64 << 20) - 1) & ~(((size_t)64 << 20) - 1);
-  size_t cap = (size_t)1 << 16;
-  while (cap < bytes) cap <<= 1;
-  return cap;
-}
 int stream_scratch(int device, hipStream_t stream, size_t bytes, void** out, ScratchTag tag) {
   ScratchSlot* sl = nullptr;
   for (auto& x : t_scratch) if (x.device == device && x.stream == stream && x.tag == tag) sl = &x;
@@ -327,22 +365,16 @@ int stream_scratch(int device, hipStream_t stream, size_t bytes, void** out, Scr
     if (t_scratch.size() >= 16) {
       for (size_t i = 0; i < t_scratch.size(); i++) {
         if (t_scratch[i].device == device && t_scratch[i].stream == stream) continue;
-        if (t_scratch[i].p) { (void)hipSetDevice(t_scratch[i].device); (void)hipFree(t_scratch[i].p); (void)hipSetDevice(device); }
+        if (t_scratch[i].blk.p) { (void)hipSetDevice(t_scratch[i].device); t_scratch[i].blk.release(); (void)hipSetDevice(device); }
         t_scratch.erase(t_scratch.begin() + (long)i);
         break;
       }
     }
-    t_scratch.push_back(ScratchSlot{device, stream, tag, nullptr, 0});
+    t_scratch.push_back(ScratchSlot{device, stream, tag, GrowBlock{}});
     sl = &t_scratch.back();
   }
-  if (bytes > sl->cap) {
-    if (sl->p) (void)hipFree(sl->p);
-    sl->p = nullptr; sl->cap = 0;
-    const size_t cap = block_capacity(bytes);
-    HIP_TRY(hipMalloc(&sl->p, cap));
-    sl->cap = cap;
-  }
-  *out = sl->p;
+  if (int rc = sl->blk.grow(bytes)) return rc;
+  *out = sl->blk.p;
   return SG_OK;
 }
 
@@ -688,10 +720,8 @@ int launch(sg_index* index, Replica* rep, const LaunchReq& r) {
   }
   LaunchPlan p = plan_launch(index, rep, r);
   BatchArgs a = batch_args(index, rep, r, p);
-  int prev_dev = -1;   // the launch goes to the replica's device whatever the calling thread's current device is
-  HIP_TRY(hipGetDevice(&prev_dev));
-  if (prev_dev != rep->device) HIP_TRY(hipSetDevice(rep->device));
-  struct Restore { int d, want; ~Restore() { if (d != want) (void)hipSetDevice(d); } } restore{prev_dev, rep->device};
+  DeviceGuard dg;   // the launch goes to the replica's device whatever the calling thread's current device is
+  HIP_TRY(dg.set(rep->device));
   void* blk = nullptr;
   if (p.long_list) {   // the list of queries beyond the wavefront kernel's tables (its count is zeroed below: by the ordering launch when there is one)
     if (int rc = stream_scratch(rep->device, stream, ((size_t)n_q + 1) * 4, &blk, SCRATCH_LONG_LIST)) return rc;
@@ -1298,22 +1328,19 @@ struct HostPool {
 };
 static HostPool& host_pool() { static HostPool pool; return pool; }
 
-// Per-thread, per-device context of the host-buffer entry points: a stream and a pinned staging buffer that are made once
-// and reused (a request-per-call service pays ~60 us per call instead of ~450 us of hipMalloc / hipFree / stream
-// creation).  Contexts live as long as their thread.
+// Per-thread, per-device context of the synchronous host-buffer entry points (sg_*_batch, the coalescer, the workers of
+// sg_*_batch_multi, sg_spell_predict_batch): a stream, a pinned staging buffer and a device block that are made once and
+// reused (a request-per-call service pays ~60 us per call instead of ~450 us of hipMalloc / hipFree / stream creation).
+// Contexts live as long as their thread.
 struct HostCtx {
   int device = -1;
   hipStream_t stream = nullptr;
-  void* pinned = nullptr;
-  size_t pinned_cap = 0;
-  char* dblock = nullptr;          // the device side of a call: inputs + result rows (grow-only, like the staging buffer)
-  size_t dblock_cap = 0;
-  hipStream_t stream2 = nullptr;   // Predict alternates its slices between two streams (made on first use)
+  GrowBlock pinned{true};          // staging of a call's inputs and results (kPinnedMax at most)
+  GrowBlock dblock;                // the device side of a call: inputs + result rows
 };
-// The calling thread's contexts, one per device.  A std::deque: push_back never moves the elements, and HostSlice keeps a
-// pointer to its context while the slices of the other devices are begun (a std::vector reallocated under it: the first
-// sg_*_batch_multi call of a thread over two GPUs read a freed context).  A thread that ends (cgo / pthread pools) hands
-// its streams, staging and device blocks back; the main thread's are left to process exit, when the HIP runtime may
+// The calling thread's contexts, one per device (a std::deque: push_back never moves a context, and a call keeps a pointer to
+// its own from begin to finish).  A thread that ends (cgo / pthread pools, the coalescer's dispatchers, the multi workers)
+// hands its streams, staging and device blocks back; the main thread's are left to process exit, when the HIP runtime may
 // already be going down.
 struct ThreadContexts {
   std::deque<HostCtx> ctx;
@@ -1322,42 +1349,16 @@ struct ThreadContexts {
 };
 static thread_local ThreadContexts t_ctx_owner;
 #define t_ctx (t_ctx_owner.ctx)
-static const size_t kPinnedMax = (size_t)64 << 20;   // bigger batches copy straight from / to the caller's (pageable) buffers
+static const size_t kPinnedMax = (size_t)64 << 20;   // bigger synchronous calls copy straight from / to the caller's (pageable) buffers
 
-static int host_ctx(int device, size_t want_pinned, HostCtx** out) {
-  HostCtx* c = nullptr;
-  for (auto& x : t_ctx) if (x.device == device) c = &x;
-  if (!c) {
-    hipStream_t st = nullptr;
-    HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    t_ctx.push_back(HostCtx{});
-    c = &t_ctx.back();
-    c->device = device;
-    c->stream = st;
-  }
-  if (want_pinned > c->pinned_cap && want_pinned <= kPinnedMax) {
-    if (c->pinned) (void)hipHostFree(c->pinned);
-    c->pinned = nullptr; c->pinned_cap = 0;
-    size_t cap = (size_t)1 << 16;
-    while (cap < want_pinned) cap <<= 1;
-    HIP_TRY(hipHostMalloc(&c->pinned, cap, hipHostMallocDefault));
-    c->pinned_cap = cap;
-  }
-  *out = c;
-  return SG_OK;
-}
-
-// the context's device block, at least `bytes` long (the stream is idle between calls: every entry point ends synchronised)
-static int ctx_device_block(HostCtx* c, size_t bytes, char** out) {
-  if (bytes > c->dblock_cap) {
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (c->dblock) (void)hipFree(c->dblock);
-    c->dblock = nullptr; c->dblock_cap = 0;
-    const size_t cap = block_capacity(bytes);
-    HIP_TRY(hipMalloc((void**)&c->dblock, cap));
-    c->dblock_cap = cap;
-  }
-  *out = c->dblock;
+static int host_ctx(int device, HostCtx** out) {
+  for (auto& x : t_ctx) if (x.device == device) { *out = &x; return SG_OK; }
+  hipStream_t st = nullptr;
+  HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+  t_ctx.push_back(HostCtx{});
+  t_ctx.back().device = device;
+  t_ctx.back().stream = st;
+  *out = &t_ctx.back();
   return SG_OK;
 }
 
@@ -1366,10 +1367,9 @@ void ThreadContexts::release() {
   for (auto& c : ctx) {
     if (hipSetDevice(c.device) != hipSuccess) continue;
     if (c.stream) (void)hipStreamSynchronize(c.stream);
-    if (c.dblock) (void)hipFree(c.dblock);
-    if (c.pinned) (void)hipHostFree(c.pinned);
+    c.dblock.release();
+    c.pinned.release();
     if (c.stream) (void)hipStreamDestroy(c.stream);
-    if (c.stream2) { (void)hipStreamSynchronize(c.stream2); (void)hipStreamDestroy(c.stream2); }
   }
   ctx.clear();
 }
@@ -1378,12 +1378,8 @@ static void thread_contexts_release() {
   t_scratch_owner.release();
 }
 
-// One slice of a host-buffer call in flight on one replica: begin() stages the inputs, copies them in, launches and starts
-// the copy back — all asynchronous on the calling thread's stream for that device; finish() waits and hands the rows to the
-// caller's buffers.  A single-replica call is begin + finish; sg_*_batch_multi begins every slice before finishing any, so
-// the GPUs work side by side.
-// The device block of a host-buffer call (slice_begin, async_submit): [scores | ids | counts | aux] — the results, one copy back —
-// then, from the next 16 bytes on, [offsets | queries] — the inputs, one copy in.  Offsets and sizes in bytes.
+// The device block of a host-buffer call: [scores | ids | counts | aux] — the results, one copy back — then, from the next 16
+// bytes on, [offsets | queries] — the inputs, one copy in.  Offsets and sizes in bytes.  Predict: id rows of topK + 1, counts.
 struct IoLayout {
   size_t sc_bytes = 0, id_bytes = 0, cnt_bytes = 0, aux_bytes = 0, off_bytes = 0, q_bytes = 0;
   size_t ids = 0, cnt = 0, aux = 0, out_bytes = 0, offs = 0, q = 0, in_bytes = 0, total = 0;   // (the scores start the block)
@@ -1410,104 +1406,198 @@ static int poison_results(char* dev, const IoLayout& io, hipStream_t st) {
   return poison_fill(dev + io.aux, io.aux_bytes, PZ_OUT_IDS, st);
 }
 
-struct HostSlice {
-  HostCtx* ctx = nullptr;
-  char* dev = nullptr;
-  bool staged = false;
-  IoLayout io{};
+// Blocks handed out by sg_host_alloc: pinned by construction, looked up without a HIP call (hipPointerGetAttributes costs
+// tens of microseconds per pointer, six pointers per submit).
+static std::mutex g_pinned_mu;
+static std::map<uintptr_t, size_t> g_pinned;       // start -> bytes
+// Is [p, p + bytes) memory the device can read and write where it lies?  Only blocks handed out by sg_host_alloc qualify, and only
+// when the WHOLE range lies inside one: the row store kernel dereferences the host pointer itself, so a range that runs past
+// the block — or memory the caller pinned some other way (hipHostRegister: not necessarily mapped, its device alias may differ)
+// — takes the staged path instead.
+static bool is_pinned_host(const void* p, size_t bytes) {
+  if (!p) return false;
+  std::lock_guard<std::mutex> lock(g_pinned_mu);
+  auto it = g_pinned.upper_bound((uintptr_t)p);
+  if (it == g_pinned.begin()) return false;
+  --it;
+  return (uintptr_t)p >= it->first && (uintptr_t)p + bytes <= it->first + it->second;
+}
+
+// ---- one host-buffer call: begin_host_call stages the inputs, copies them in, enqueues the kind's work and the copy back,
+// all asynchronous; finish_host_call waits and hands the rows to the caller's arrays ----
+
+// The caller's side: n_q queries (blob + n_q + 1 offsets, which may start anywhere) and the result arrays — [n_q][row] ids,
+// [n_q][row] scores (null: none), [n_q] counts, [n_q][row] aux (null: none).
+struct HostBufs {
+  const uint8_t* q = nullptr; const uint64_t* offs = nullptr; uint32_t n_q = 0, row = 0;
   uint32_t* ids = nullptr; double* scores = nullptr; uint32_t* counts = nullptr; uint32_t* aux = nullptr;
 };
+// What a call runs on.  A synchronous call: the calling thread's HostCtx — one stream for everything, no events, one staging
+// buffer both ways, staging up to kPinnedMax.  A ticket: its AsyncSlot — the copy-in, run and copy-out streams of the replica's
+// pool tied by the slot's events, a staging buffer each way of any size, and caller memory from sg_host_alloc read and written
+// where it lies.
+struct IoCtx {
+  hipStream_t in = nullptr, run = nullptr, out = nullptr;
+  hipEvent_t ev_in = nullptr, ev_run = nullptr, ev_out = nullptr;
+  GrowBlock *dev = nullptr, *pin_in = nullptr, *pin_out = nullptr;
+  bool ticket = false;
+};
+// A call in flight: what finish_host_call needs
+struct HostCall {
+  HostBufs b;
+  IoLayout io;
+  const char* staged = nullptr;      // the results in pinned staging (null: they went to the caller's arrays)
+  hipStream_t out = nullptr;
+  hipEvent_t done = nullptr;         // finish waits for this event if there is one, else for `out`
+};
+// The kind's enqueue step (launch() for search, autocomplete and tables, predict_on_device for Predict): the device block's
+// inputs -> its result rows, on stream `st`
+using Enqueue = std::function<int(char* dev, const IoLayout& io, hipStream_t st)>;
 
-// r: what to search for (metric, similarity, k, autocomplete / by_doc, ac_first, mt); slice_begin adds the buffers and the stream
-static int slice_begin(sg_index* index, Replica* rep, const uint8_t* q, const uint64_t* offs, uint32_t n_q, LaunchReq r,
-                       uint32_t* ids, double* scores, uint32_t* counts, uint32_t* aux, HostSlice* s) {
-  s->ids = ids; s->scores = scores; s->counts = counts; s->aux = aux; s->io = IoLayout{};
-  if (n_q == 0) return SG_OK;
-  const uint64_t q0 = offs[0];
-  if (!q && offs[n_q] != q0) { set_error("null query buffer"); return SG_E_INVALID; }
-  HIP_TRY(hipSetDevice(rep->device));
-  const IoLayout& io = s->io = io_layout(n_q, r.k, !r.autocomplete, aux != nullptr, (size_t)(offs[n_q] - q0));
-  // a slice of a larger batch starts at a non-zero offset: the offsets are rebased in the staging buffer
-  const bool rebase = q0 != 0;
-  int rc = host_ctx(rep->device, rebase ? std::max(io.in_bytes, std::min(io.out_bytes, kPinnedMax)) : std::max(io.in_bytes, io.out_bytes), &s->ctx);
-  if (rc) return rc;
-  HostCtx* ctx = s->ctx;
-  s->staged = std::max(io.in_bytes, io.out_bytes) <= ctx->pinned_cap;
-  const bool in_staged = s->staged || (rebase && io.in_bytes <= ctx->pinned_cap);
-  if (rebase && !in_staged) { set_error("batch slice too large to stage"); return SG_E_INVALID; }
-  hipStream_t st = ctx->stream;
-  if ((rc = ctx_device_block(ctx, io.total, &s->dev))) { s->dev = nullptr; return rc; }
-  char* dev = s->dev;
-#define TRY2(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { set_error(std::string(#expr) + ": " + hipGetErrorString(e_)); (void)hipStreamSynchronize(st); s->dev = nullptr; return SG_E_HIP; } } while (0)
+// b.n_q > 0.  clear_rows: the result rows are zeroed (sg_debug_poison: poisoned) before the enqueue step.
+static int begin_host_call(const HostBufs& b, bool clear_rows, const Enqueue& enqueue, const IoCtx& x, HostCall* c) {
+  const uint64_t q0 = b.offs[0];
+  if (!b.q && b.offs[b.n_q] != q0) { set_error("null query buffer"); return SG_E_INVALID; }
+  const IoLayout io = io_layout(b.n_q, b.row, b.scores != nullptr, b.aux != nullptr, (size_t)(b.offs[b.n_q] - q0));
+  // the routes.  A ticket: caller memory from sg_host_alloc where it lies, the rest staged.  A synchronous call: staged both ways
+  // while it fits kPinnedMax, else straight from / to the caller's memory — but offsets that do not start at zero (a slice of a
+  // larger batch) are rebased in the staging buffer.
+  bool in_staged, out_staged, out_pinned = false;
+  if (x.ticket) {
+    in_staged = q0 != 0 || !is_pinned_host(b.offs, io.off_bytes) || (io.q_bytes && !is_pinned_host(b.q, io.q_bytes));
+    out_pinned = is_pinned_host(b.ids, io.id_bytes) && is_pinned_host(b.counts, io.cnt_bytes) && (!b.scores || is_pinned_host(b.scores, io.sc_bytes));
+    out_staged = !out_pinned;
+  } else {
+    out_staged = std::max(io.in_bytes, io.out_bytes) <= kPinnedMax;
+    in_staged = out_staged || q0 != 0;
+    if (in_staged && io.in_bytes > kPinnedMax) { set_error("batch slice too large to stage"); return SG_E_INVALID; }
+  }
+  const size_t pin_in = in_staged ? io.in_bytes : 0, pin_out = out_staged ? io.out_bytes : 0;
+  if (int rc = x.pin_in->grow(x.pin_in == x.pin_out ? std::max(pin_in, pin_out) : pin_in)) return rc;
+  if (int rc = x.pin_out->grow(pin_out)) return rc;
+  if (io.total > x.dev->cap && x.dev->p) HIP_TRY(hipStreamSynchronize(x.run));   // (hipFree would wait for the device anyway)
+  if (int rc = x.dev->grow(io.total)) return rc;
+  char* dev = (char*)x.dev->p;
+  // (a call that fails half way waits for what it enqueued: its buffers are reused by the next call)
+  struct Drain {
+    const IoCtx& x; bool armed = true;
+    ~Drain() { if (armed) for (hipStream_t st : {x.in, x.run, x.out}) (void)hipStreamSynchronize(st); }
+  } drain{x};
+  // ---- copy in: one copy from staging, the offsets rebased to zero, or two straight from the caller's memory ----
   if (in_staged) {
-    uint64_t* po = (uint64_t*)ctx->pinned;
-    if (rebase) for (uint32_t i = 0; i <= n_q; i++) po[i] = offs[i] - q0; else memcpy(po, offs, io.off_bytes);
-    if (io.q_bytes) memcpy((char*)ctx->pinned + io.off_bytes, q + q0, io.q_bytes);
-    TRY2(hipMemcpyAsync(dev + io.offs, ctx->pinned, io.in_bytes, hipMemcpyHostToDevice, st));
-    if (!s->staged) TRY2(hipStreamSynchronize(st));       // the pinned buffer is not reused for the results, but be explicit
+    char* pin = (char*)x.pin_in->p;
+    uint64_t* po = (uint64_t*)pin;
+    if (q0) for (uint32_t i = 0; i <= b.n_q; i++) po[i] = b.offs[i] - q0; else memcpy(po, b.offs, io.off_bytes);
+    if (io.q_bytes) memcpy(pin + io.off_bytes, b.q + q0, io.q_bytes);
+    HIP_TRY(hipMemcpyAsync(dev + io.offs, pin, io.in_bytes, hipMemcpyHostToDevice, x.in));
   } else {
-    TRY2(hipMemcpyAsync(dev + io.offs, offs, io.off_bytes, hipMemcpyHostToDevice, st));
-    if (io.q_bytes) TRY2(hipMemcpyAsync(dev + io.q, q, io.q_bytes, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(dev + io.offs, b.offs, io.off_bytes, hipMemcpyHostToDevice, x.in));
+    if (io.q_bytes) HIP_TRY(hipMemcpyAsync(dev + io.q, b.q, io.q_bytes, hipMemcpyHostToDevice, x.in));
   }
-  if (poison_mode()) { if ((rc = poison_results(dev, io, st))) { (void)hipStreamSynchronize(st); s->dev = nullptr; return rc; } }
-  else TRY2(hipMemsetAsync(dev, 0, io.sc_bytes + io.id_bytes, st));   // rows of queries with fewer than k results stay zero
-  // (a caller with host buffers knows its longest query: at most 112 bytes + the wrap runes stay within the wavefront
-  //  kernel's 144 runes / 128 n-grams, and the long-query launch — a few microseconds of a single query's latency — is left out)
-  uint64_t max_len = 0;
-  for (uint32_t i = 0; i < n_q; i++) max_len = std::max<uint64_t>(max_len, offs[i + 1] - offs[i]);
-  if (aux && !poison_mode()) TRY2(hipMemsetAsync(dev + io.aux, 0, io.aux_bytes, st));
-  r.q = dev + io.q; r.offs = dev + io.offs; r.n_q = n_q; r.stream = st; r.no_long_queries = max_len <= 112;
-  r.ids = dev + io.ids; r.scores = r.autocomplete ? nullptr : dev; r.counts = dev + io.cnt; r.out_aux = aux ? (uint32_t*)(dev + io.aux) : nullptr;
-  rc = launch(index, rep, r);
-  if (rc) { (void)hipStreamSynchronize(st); s->dev = nullptr; return rc; }
-  if (s->staged) {
-    TRY2(hipMemcpyAsync(ctx->pinned, dev, io.out_bytes, hipMemcpyDeviceToHost, st));
+  // (rows of queries with fewer than k results stay zero; a ticket clears them on its copy-in stream, beside the previous
+  //  ticket's search launch — on the run stream the 8 MB fill was 0.09 ms between two search launches)
+  if (clear_rows) {
+    if (poison_mode()) { if (int rc = poison_results(dev, io, x.in)) return rc; }
+    else {
+      HIP_TRY(hipMemsetAsync(dev, 0, io.sc_bytes + io.id_bytes, x.in));
+      if (io.aux_bytes) HIP_TRY(hipMemsetAsync(dev + io.aux, 0, io.aux_bytes, x.in));
+    }
+  }
+  if (x.ev_in) { HIP_TRY(hipEventRecord(x.ev_in, x.in)); HIP_TRY(hipStreamWaitEvent(x.run, x.ev_in, 0)); }
+  if (int rc = enqueue(dev, io, x.run)) return rc;
+  if (x.ev_run) { HIP_TRY(hipEventRecord(x.ev_run, x.run)); HIP_TRY(hipStreamWaitEvent(x.out, x.ev_run, 0)); }
+  // ---- copy out: one copy to staging, or into the caller's arrays ----
+  const bool al16 = ((uintptr_t)b.scores | (uintptr_t)b.ids | (uintptr_t)b.counts | io.sc_bytes | io.id_bytes | io.cnt_bytes |
+                     (uintptr_t)(dev + io.ids) | (uintptr_t)(dev + io.cnt)) % 16 == 0;
+  if (out_staged) {
+    HIP_TRY(hipMemcpyAsync(x.pin_out->p, dev, io.out_bytes, hipMemcpyDeviceToHost, x.out));
+  } else if (out_pinned && al16 && !b.aux) {
+    // (sg_host_alloc memory: a kernel's stores, not hipMemcpyAsync — see host_store_kernel; 16-byte pieces — the device block's
+    //  regions are, the caller's pinned arrays usually are; anything else takes the runtime's copies)
+    HostStoreArgs h{};
+    h.src[0] = (const uint4*)dev; h.dst[0] = (uint4*)b.scores; h.n16[0] = io.sc_bytes / 16;
+    h.src[1] = (const uint4*)(dev + io.ids); h.dst[1] = (uint4*)b.ids; h.n16[1] = io.id_bytes / 16;
+    h.src[2] = (const uint4*)(dev + io.cnt); h.dst[2] = (uint4*)b.counts; h.n16[2] = io.cnt_bytes / 16;
+    hipLaunchKernelGGL(host_store_kernel, dim3(128), dim3(256), 0, x.out, h);
+    HIP_TRY(hipGetLastError());
   } else {
-    if (!r.autocomplete) TRY2(hipMemcpyAsync(scores, dev, io.sc_bytes, hipMemcpyDeviceToHost, st));
-    TRY2(hipMemcpyAsync(ids, dev + io.ids, io.id_bytes, hipMemcpyDeviceToHost, st));
-    TRY2(hipMemcpyAsync(counts, dev + io.cnt, io.cnt_bytes, hipMemcpyDeviceToHost, st));
-    if (aux) TRY2(hipMemcpyAsync(aux, dev + io.aux, io.aux_bytes, hipMemcpyDeviceToHost, st));
+    if (io.sc_bytes) HIP_TRY(hipMemcpyAsync(b.scores, dev, io.sc_bytes, hipMemcpyDeviceToHost, x.out));
+    HIP_TRY(hipMemcpyAsync(b.ids, dev + io.ids, io.id_bytes, hipMemcpyDeviceToHost, x.out));
+    HIP_TRY(hipMemcpyAsync(b.counts, dev + io.cnt, io.cnt_bytes, hipMemcpyDeviceToHost, x.out));
+    if (io.aux_bytes) HIP_TRY(hipMemcpyAsync(b.aux, dev + io.aux, io.aux_bytes, hipMemcpyDeviceToHost, x.out));
   }
-#undef TRY2
+  if (x.ev_out) HIP_TRY(hipEventRecord(x.ev_out, x.out));
+  drain.armed = false;
+  *c = HostCall{b, io, out_staged ? (const char*)x.pin_out->p : nullptr, x.out, x.ev_out};
   return SG_OK;
 }
 
-static int slice_finish(HostSlice* s) {
-  if (!s->dev) return SG_OK;
-  s->dev = nullptr;
-  HIP_TRY(hipStreamSynchronize(s->ctx->stream));
-  if (s->staged) {
-    const char* h = (const char*)s->ctx->pinned;
-    auto copy_out = [](void* dst, const char* src, size_t n) {     // (8 MB of rows for 65 536 queries: one thread takes 0.5 ms)
-      if (n < ((size_t)1 << 20)) { memcpy(dst, src, n); return; }
-      const size_t piece = (size_t)256 << 10;
-      host_pool().run((uint32_t)((n + piece - 1) / piece), 2, [&](uint32_t lo, uint32_t hi) {
-        const size_t b = (size_t)lo * piece, e = std::min(n, (size_t)hi * piece);
-        memcpy((char*)dst + b, src + b, e - b);
-      });
-    };
-    const IoLayout& io = s->io;
-    if (io.sc_bytes) copy_out(s->scores, h, io.sc_bytes);
-    copy_out(s->ids, h + io.ids, io.id_bytes);
-    memcpy(s->counts, h + io.cnt, io.cnt_bytes);
-    if (s->aux) copy_out(s->aux, h + io.aux, io.aux_bytes);
-  }
+static int finish_host_call(const HostCall& c) {
+  if (c.done) HIP_TRY(hipEventSynchronize(c.done));
+  else HIP_TRY(hipStreamSynchronize(c.out));
+  if (!c.staged) return SG_OK;
+  auto copy_out = [](void* dst, const char* src, size_t n) {     // (8 MB of rows for 65 536 queries: one thread takes 0.5 ms)
+    if (n < ((size_t)1 << 20)) { memcpy(dst, src, n); return; }
+    const size_t piece = (size_t)256 << 10;
+    host_pool().run((uint32_t)((n + piece - 1) / piece), 2, [&](uint32_t lo, uint32_t hi) {
+      const size_t b = (size_t)lo * piece, e = std::min(n, (size_t)hi * piece);
+      memcpy((char*)dst + b, src + b, e - b);
+    });
+  };
+  const IoLayout& io = c.io;
+  if (io.sc_bytes) copy_out(c.b.scores, c.staged, io.sc_bytes);
+  copy_out(c.b.ids, c.staged + io.ids, io.id_bytes);
+  memcpy(c.b.counts, c.staged + io.cnt, io.cnt_bytes);
+  if (io.aux_bytes) copy_out(c.b.aux, c.staged + io.aux, io.aux_bytes);
   return SG_OK;
 }
 
-// a host-buffer search: metric, similarity, k, autocomplete, ac_first of r (launch() takes the rest from the slice)
+// A synchronous host-buffer call: begin and finish on the calling thread's context for the replica's device, whose current
+// device is the same afterwards.
+static int run_host_call(Replica* rep, const HostBufs& b, bool clear_rows, const Enqueue& enqueue) {
+  if (b.n_q == 0) return SG_OK;
+  DeviceGuard dg;
+  HIP_TRY(dg.set(rep->device));
+  HostCtx* ctx;
+  if (int rc = host_ctx(rep->device, &ctx)) return rc;
+  IoCtx x;
+  x.in = x.run = x.out = ctx->stream;
+  x.dev = &ctx->dblock; x.pin_in = x.pin_out = &ctx->pinned;
+  HostCall c;
+  if (int rc = begin_host_call(b, clear_rows, enqueue, x, &c)) return rc;
+  return finish_host_call(c);
+}
+
+// a host-buffer search: metric, similarity, k, autocomplete, ac_first of r (by_doc and mt are set by the caller)
 static LaunchReq search_req(int metric, double sim, uint32_t k, int autocomplete, uint32_t ac_first = 0) {
   LaunchReq r;
   r.metric = metric; r.similarity = sim; r.k = k; r.autocomplete = autocomplete; r.ac_first = ac_first;
   return r;
 }
 
+// the enqueue step of a search: launch() on the device block, with what the caller's buffers say
+static Enqueue search_enqueue(sg_index* index, Replica* rep, const LaunchReq& req, const HostBufs& b) {
+  return [=](char* dev, const IoLayout& io, hipStream_t st) {
+    // (a caller with host buffers knows its longest query: at most 112 bytes + the wrap runes stay within the wavefront
+    //  kernel's 144 runes / 128 n-grams, and the long-query launch — a few microseconds of a single query's latency — is left out)
+    uint64_t max_len = 0;
+    for (uint32_t i = 0; i < b.n_q; i++) max_len = std::max<uint64_t>(max_len, b.offs[i + 1] - b.offs[i]);
+    LaunchReq r = req;
+    r.q = dev + io.q; r.offs = dev + io.offs; r.n_q = b.n_q; r.stream = st; r.no_long_queries = max_len <= 112;
+    r.ids = dev + io.ids; r.scores = r.autocomplete ? nullptr : dev; r.counts = dev + io.cnt;
+    r.out_aux = b.aux ? (uint32_t*)(dev + io.aux) : nullptr;
+    return launch(index, rep, r);
+  };
+}
+static HostBufs search_bufs(const uint8_t* q, const uint64_t* offs, uint32_t n_q, const LaunchReq& r, uint32_t* ids, double* scores,
+                            uint32_t* counts, uint32_t* aux) {
+  return HostBufs{q, offs, n_q, r.k, ids, r.autocomplete ? nullptr : scores, counts, aux};
+}
+
 static int run_host(sg_index* index, Replica* rep, const uint8_t* q, const uint64_t* offs, uint32_t n_q, const LaunchReq& r,
                     uint32_t* ids, double* scores, uint32_t* counts, uint32_t* aux = nullptr) {
-  HostSlice s;
-  int rc = slice_begin(index, rep, q, offs, n_q, r, ids, scores, counts, aux, &s);
-  if (rc) return rc;
-  return slice_finish(&s);
+  const HostBufs b = search_bufs(q, offs, n_q, r, ids, scores, counts, aux);
+  return run_host_call(rep, b, true, search_enqueue(index, rep, r, b));
 }
 
 int sg_suggest_batch(sg_index* index, const uint8_t* q, const uint64_t* offs, uint32_t n_q, int metric, double similarity,
@@ -1569,10 +1659,8 @@ int sg_metric_tables_create(sg_index* index, uint32_t a_max, const int32_t* min_
   const size_t n_a = (size_t)a_max + 1, n_thr = n_a * S, n_sc = n_thr * n_a;
   if (n_sc * 8 > ((size_t)4 << 30)) { set_error("metric tables above 4 GiB"); return SG_E_INVALID; }
   Replica* rep = find_replica(index, -1);
-  int prev_dev = -1;
-  HIP_TRY(hipGetDevice(&prev_dev));
-  struct Restore { int d; ~Restore() { if (d >= 0) (void)hipSetDevice(d); } } restore{prev_dev};
-  HIP_TRY(hipSetDevice(rep->device));
+  DeviceGuard dg;
+  HIP_TRY(dg.set(rep->device));
   const size_t o_max = (n_a * 4 + 15) & ~(size_t)15, o_thr = 2 * o_max, o_sc = (o_thr + n_thr * 4 + 15) & ~(size_t)15, total = o_sc + n_sc * 8;
   std::unique_ptr<sg_metric_tables> t(new sg_metric_tables());
   HIP_TRY(hipMalloc(&t->block, total));
@@ -1598,10 +1686,10 @@ int sg_metric_tables_create(sg_index* index, uint32_t a_max, const int32_t* min_
 void sg_metric_tables_retain(sg_metric_tables* t) { if (t) t->refs.fetch_add(1); }
 void sg_metric_tables_release(sg_metric_tables* t) {
   if (!t || t->refs.fetch_sub(1) != 1) return;
-  int prev_dev = -1;
-  (void)hipGetDevice(&prev_dev);
-  if (hipSetDevice(t->device) == hipSuccess) (void)hipFree(t->block);
-  if (prev_dev >= 0) (void)hipSetDevice(prev_dev);
+  {
+    DeviceGuard dg;
+    if (dg.set(t->device) == hipSuccess) (void)hipFree(t->block);
+  }
   sg_index_release(t->index);
   delete t;
 }
@@ -1657,16 +1745,14 @@ int sg_suggest_batch_from(sg_index* index, const uint8_t* q, const uint64_t* off
 //     serialised on ONE stream (two search launches side by side undo the L2 sharing the query order sets up: DESIGN.md §5)
 //     while the H2D of the next ticket and the D2H of the previous one overlap it;
 //   * a ring of slots (device block + pinned staging + events) per replica; a ticket holds one until it is waited for;
-//   * buffers the caller got from sg_host_alloc (or registered itself) are pinned: the DMA engine reads / writes them
-//     directly and nothing is staged; pageable buffers are staged through the slot's pinned memory (one memcpy at submit,
-//     one at wait).
+//   * buffers the caller got from sg_host_alloc are pinned: they are read / written where they lie and nothing is staged;
+//     other buffers are staged through the slot's pinned memory (one memcpy at submit, one at wait).
+// Submit is begin_host_call on the slot, wait is finish_host_call: the routines of the synchronous calls.
 // Tickets are plain heap objects: submit and wait may run on different OS threads (goroutines migrate).
 // ------------------------------------------------------------------------------------------
 #define SG_ASYNC_SLOTS 8
 struct AsyncSlot {
-  char* dev = nullptr; size_t dev_cap = 0;
-  void* pin_in = nullptr; size_t pin_in_cap = 0;
-  void* pin_out = nullptr; size_t pin_out_cap = 0;
+  GrowBlock dev, pin_in{true}, pin_out{true};
   hipEvent_t ev_in = nullptr, ev_run = nullptr, ev_out = nullptr;
   bool busy = false;
 };
@@ -1678,9 +1764,7 @@ struct AsyncPool {
     if (device < 0 || hipSetDevice(device) != hipSuccess) return;
     for (hipStream_t st : {s_in, s_run, s_out}) if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
     for (auto& x : slot) {
-      if (x.dev) (void)hipFree(x.dev);
-      if (x.pin_in) (void)hipHostFree(x.pin_in);
-      if (x.pin_out) (void)hipHostFree(x.pin_out);
+      x.dev.release(); x.pin_in.release(); x.pin_out.release();
       for (hipEvent_t e : {x.ev_in, x.ev_run, x.ev_out}) if (e) (void)hipEventDestroy(e);
     }
   }
@@ -1695,39 +1779,8 @@ struct sg_ticket {
   sg_index* index = nullptr;
   Replica* rep = nullptr;
   int slot = -1;
-  bool out_staged = false;
-  int autocomplete = 0;
-  size_t sc_bytes = 0, id_bytes = 0, cnt_bytes = 0;
-  uint32_t* ids = nullptr; double* scores = nullptr; uint32_t* counts = nullptr;
+  HostCall call;
 };
-
-// Blocks handed out by sg_host_alloc: pinned by construction, looked up without a HIP call (hipPointerGetAttributes costs
-// tens of microseconds per pointer, six pointers per submit).
-static std::mutex g_pinned_mu;
-static std::map<uintptr_t, size_t> g_pinned;       // start -> bytes
-// Is [p, p + bytes) memory the device can read and write where it lies?  Only blocks handed out by sg_host_alloc qualify, and only
-// when the WHOLE range lies inside one: the row store kernel dereferences the host pointer itself, so a range that runs past
-// the block — or memory the caller pinned some other way (hipHostRegister: not necessarily mapped, its device alias may differ)
-// — takes the staged path instead.
-static bool is_pinned_host(const void* p, size_t bytes) {
-  if (!p) return false;
-  std::lock_guard<std::mutex> lock(g_pinned_mu);
-  auto it = g_pinned.upper_bound((uintptr_t)p);
-  if (it == g_pinned.begin()) return false;
-  --it;
-  return (uintptr_t)p >= it->first && (uintptr_t)p + bytes <= it->first + it->second;
-}
-
-static int async_grow_pinned(void** p, size_t* cap, size_t want) {
-  if (want <= *cap) return SG_OK;
-  if (*p) (void)hipHostFree(*p);
-  *p = nullptr; *cap = 0;
-  size_t c = (size_t)1 << 16;
-  while (c < want) c <<= 1;
-  HIP_TRY(hipHostMalloc(p, c, hipHostMallocDefault));
-  *cap = c;
-  return SG_OK;
-}
 
 static int async_submit(sg_index* index, const uint8_t* q, const uint64_t* offs, uint32_t n_q, int metric, double sim, uint32_t k,
                         int autocomplete, uint32_t* ids, double* scores, uint32_t* counts, uint32_t ac_first, sg_ticket** out, uint32_t replica = 0) {
@@ -1739,19 +1792,11 @@ static int async_submit(sg_index* index, const uint8_t* q, const uint64_t* offs,
     if (replica < index->replicas.size()) rep = index->replicas[replica].get();
   }
   if (!rep) { set_error("no such replica"); return SG_E_INVALID; }
-  const uint64_t q0 = n_q ? offs[0] : 0;
-  if (n_q && !q && offs[n_q] != q0) { set_error("null query buffer"); return SG_E_INVALID; }
-  int prev_dev = -1;
-  HIP_TRY(hipGetDevice(&prev_dev));
-  struct Restore { int d; ~Restore() { if (d >= 0) (void)hipSetDevice(d); } } restore{prev_dev};
-  HIP_TRY(hipSetDevice(rep->device));
-  static const bool trace = getenv("SG_ASYNC_TRACE") != nullptr;      // where a submit's host time goes (stderr)
-  const auto tr0 = std::chrono::steady_clock::now();
-  double tr[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  auto mark = [&](int i) { if (trace) tr[i] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tr0).count(); };
   std::unique_ptr<sg_ticket> t(new sg_ticket());
-  t->index = index; t->rep = rep; t->autocomplete = autocomplete; t->ids = ids; t->scores = scores; t->counts = counts;
+  t->index = index; t->rep = rep;
   if (n_q == 0) { sg_index_retain(index); *out = t.release(); return SG_OK; }
+  DeviceGuard dg;
+  HIP_TRY(dg.set(rep->device));
   // ---- a slot of the replica's ring ----
   AsyncPool* pool;
   AsyncSlot* sl = nullptr;
@@ -1766,11 +1811,9 @@ static int async_submit(sg_index* index, const uint8_t* q, const uint64_t* offs,
       // to queues of their own.
       int prio_lo = 0, prio_hi = 0;
       (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-      const char* pe = getenv("SG_ASYNC_PRIO");
-      const int copy_prio = (pe && atoi(pe) == 0) ? prio_lo : prio_hi;
-      HIP_TRY(hipStreamCreateWithPriority(&np->s_in, hipStreamNonBlocking, copy_prio));
+      HIP_TRY(hipStreamCreateWithPriority(&np->s_in, hipStreamNonBlocking, prio_hi));
       HIP_TRY(hipStreamCreateWithPriority(&np->s_run, hipStreamNonBlocking, prio_lo));
-      HIP_TRY(hipStreamCreateWithPriority(&np->s_out, hipStreamNonBlocking, copy_prio));
+      HIP_TRY(hipStreamCreateWithPriority(&np->s_out, hipStreamNonBlocking, prio_hi));
       rep->async_pool = np.release();
     }
     pool = rep->async_pool;
@@ -1778,97 +1821,25 @@ static int async_submit(sg_index* index, const uint8_t* q, const uint64_t* offs,
     if (!sl) { set_error("too many tickets in flight on this replica: wait for one first (SG_ASYNC_SLOTS = 8)"); return SG_E_INVALID; }
     sl->busy = true;
   }
-  // (a submit that fails half way: whatever it enqueued is awaited before the slot is handed back)
+  // (a submit that fails hands the slot back; begin_host_call has waited for whatever it enqueued)
   struct Unbusy {
-    Replica* r; AsyncPool* p; AsyncSlot* s; bool keep = false;
-    ~Unbusy() {
-      if (keep) return;
-      for (hipStream_t st : {p->s_in, p->s_run, p->s_out}) (void)hipStreamSynchronize(st);
-      std::lock_guard<std::mutex> lock(r->async_mu); s->busy = false;
-    }
-  } unbusy{rep, pool, sl};
+    Replica* r; AsyncSlot* s; bool keep = false;
+    ~Unbusy() { if (!keep) { std::lock_guard<std::mutex> lock(r->async_mu); s->busy = false; } }
+  } unbusy{rep, sl};
   if (!sl->ev_in) {
     HIP_TRY(hipEventCreateWithFlags(&sl->ev_in, hipEventDisableTiming));
     HIP_TRY(hipEventCreateWithFlags(&sl->ev_run, hipEventDisableTiming));
     HIP_TRY(hipEventCreateWithFlags(&sl->ev_out, hipEventDisableTiming));
   }
-  // ---- the slot's device block: [scores | ids | counts] then [offsets | queries], as the synchronous path lays it out ----
-  const IoLayout io = io_layout(n_q, k, !autocomplete, false, (size_t)(offs[n_q] - q0));
-  const size_t qbytes = io.q_bytes, out_bytes = io.out_bytes, off_bytes = io.off_bytes, in_bytes = io.in_bytes, total = io.total;
-  t->sc_bytes = io.sc_bytes; t->id_bytes = io.id_bytes; t->cnt_bytes = io.cnt_bytes;
-  if (total > sl->dev_cap) {      // (the slot is free: nothing of an earlier ticket is in flight on it)
-    if (sl->dev) (void)hipFree(sl->dev);
-    sl->dev = nullptr; sl->dev_cap = 0;
-    const size_t cap = block_capacity(total);
-    HIP_TRY(hipMalloc((void**)&sl->dev, cap));
-    sl->dev_cap = cap;
-  }
-  char* dev = sl->dev;
-  char* d_sc = dev; char* d_ids = dev + io.ids; char* d_cnt = dev + io.cnt; char* d_offs = dev + io.offs; char* d_q = dev + io.q;
-  mark(0);
-  // ---- copy in: straight from pinned caller memory, else through the slot's staging buffer ----
-  const bool in_direct = q0 == 0 && is_pinned_host(offs, off_bytes) && (qbytes == 0 || is_pinned_host(q, qbytes));
-  if (in_direct) {
-    HIP_TRY(hipMemcpyAsync(d_offs, offs, off_bytes, hipMemcpyHostToDevice, pool->s_in));
-    if (qbytes) HIP_TRY(hipMemcpyAsync(d_q, q, qbytes, hipMemcpyHostToDevice, pool->s_in));
-  } else {
-    if (int rc = async_grow_pinned(&sl->pin_in, &sl->pin_in_cap, in_bytes)) return rc;
-    uint64_t* po = (uint64_t*)sl->pin_in;
-    if (q0) for (uint32_t i = 0; i <= n_q; i++) po[i] = offs[i] - q0; else memcpy(po, offs, off_bytes);
-    if (qbytes) memcpy((char*)sl->pin_in + off_bytes, q + q0, qbytes);
-    HIP_TRY(hipMemcpyAsync(d_offs, sl->pin_in, in_bytes, hipMemcpyHostToDevice, pool->s_in));
-  }
-  // (rows of queries with fewer than k results stay zero: cleared here, beside the previous ticket's search launch — on the
-  //  run stream the 8 MB fill was 0.09 ms between two search launches)
-  if (poison_mode()) { if (int rc = poison_results(dev, io, pool->s_in)) return rc; }
-  else HIP_TRY(hipMemsetAsync(dev, 0, t->sc_bytes + t->id_bytes, pool->s_in));
-  HIP_TRY(hipEventRecord(sl->ev_in, pool->s_in));
-  mark(1);
-  // ---- run: every search launch of the replica's tickets on ONE stream ----
-  HIP_TRY(hipStreamWaitEvent(pool->s_run, sl->ev_in, 0));
-  uint64_t max_len = 0;
-  for (uint32_t i = 0; i < n_q; i++) max_len = std::max<uint64_t>(max_len, offs[i + 1] - offs[i]);
-  LaunchReq r = search_req(metric, sim, k, autocomplete, ac_first);
-  r.q = d_q; r.offs = d_offs; r.n_q = n_q; r.stream = pool->s_run; r.no_long_queries = max_len <= 112;
-  r.ids = d_ids; r.scores = autocomplete ? nullptr : d_sc; r.counts = d_cnt;
-  int rc = launch(index, rep, r);
-  if (rc) { (void)hipStreamSynchronize(pool->s_run); return rc; }
-  mark(2);
-  HIP_TRY(hipEventRecord(sl->ev_run, pool->s_run));
-  mark(4);
-  // ---- copy out ----
-  HIP_TRY(hipStreamWaitEvent(pool->s_out, sl->ev_run, 0));
-  mark(5);
-  const bool out_direct = is_pinned_host(ids, t->id_bytes) && is_pinned_host(counts, t->cnt_bytes) && (autocomplete || is_pinned_host(scores, t->sc_bytes));
-  t->out_staged = !out_direct;
-  if (out_direct) {
-    // (a kernel's stores, not hipMemcpyAsync: see host_store_kernel; 16-byte pieces — the device block's regions are, the
-    //  caller's pinned arrays usually are; anything else takes the runtime's copy)
-    const bool al16 = ((uintptr_t)scores | (uintptr_t)ids | (uintptr_t)counts | t->sc_bytes | t->id_bytes | t->cnt_bytes | (uintptr_t)d_ids | (uintptr_t)d_cnt) % 16 == 0;
-    static const bool store_kernel = !(getenv("SG_ASYNC_MEMCPY") && atoi(getenv("SG_ASYNC_MEMCPY")) == 1);
-    if (al16 && store_kernel) {
-      HostStoreArgs h{};
-      h.src[0] = (const uint4*)d_sc; h.dst[0] = (uint4*)scores; h.n16[0] = t->sc_bytes / 16;
-      h.src[1] = (const uint4*)d_ids; h.dst[1] = (uint4*)ids; h.n16[1] = t->id_bytes / 16;
-      h.src[2] = (const uint4*)d_cnt; h.dst[2] = (uint4*)counts; h.n16[2] = t->cnt_bytes / 16;
-      hipLaunchKernelGGL(host_store_kernel, dim3(128), dim3(256), 0, pool->s_out, h);
-      HIP_TRY(hipGetLastError());
-      mark(6);
-    } else {
-    if (!autocomplete) HIP_TRY(hipMemcpyAsync(scores, d_sc, t->sc_bytes, hipMemcpyDeviceToHost, pool->s_out));
-    mark(6);
-    HIP_TRY(hipMemcpyAsync(ids, d_ids, t->id_bytes, hipMemcpyDeviceToHost, pool->s_out));
-    HIP_TRY(hipMemcpyAsync(counts, d_cnt, t->cnt_bytes, hipMemcpyDeviceToHost, pool->s_out));
-    }
-    mark(7);
-  } else {
-    if (int rc2 = async_grow_pinned(&sl->pin_out, &sl->pin_out_cap, out_bytes)) { (void)hipStreamSynchronize(pool->s_run); return rc2; }
-    HIP_TRY(hipMemcpyAsync(sl->pin_out, dev, out_bytes, hipMemcpyDeviceToHost, pool->s_out));
-  }
-  HIP_TRY(hipEventRecord(sl->ev_out, pool->s_out));
-  mark(3);
-  if (trace) fprintf(stderr, "[sg async] slot %d: setup %.3f  copy-in enqueued %.3f  launch() %.3f  copy-out enqueued %.3f ms (event record %.3f, wait-event %.3f, first copy %.3f, two more %.3f)\n",
-                     t->slot, tr[0], tr[1] - tr[0], tr[2] - tr[1], tr[3] - tr[2], tr[4] - tr[2], tr[5] - tr[4], tr[6] - tr[5], tr[7] - tr[6]);
+  // copy in on s_in, every search launch of the replica's tickets on ONE stream (s_run), copy out on s_out
+  IoCtx x;
+  x.in = pool->s_in; x.run = pool->s_run; x.out = pool->s_out;
+  x.ev_in = sl->ev_in; x.ev_run = sl->ev_run; x.ev_out = sl->ev_out;
+  x.dev = &sl->dev; x.pin_in = &sl->pin_in; x.pin_out = &sl->pin_out;
+  x.ticket = true;
+  const LaunchReq r = search_req(metric, sim, k, autocomplete, ac_first);
+  const HostBufs b = search_bufs(q, offs, n_q, r, ids, scores, counts, nullptr);
+  if (int rc = begin_host_call(b, true, search_enqueue(index, rep, r, b), x, &t->call)) return rc;
   unbusy.keep = true;
   sg_index_retain(index);
   *out = t.release();
@@ -1936,14 +1907,7 @@ int sg_ticket_wait(sg_ticket* t) {
   if (t->slot < 0) return SG_OK;                               // an empty batch
   AsyncSlot* sl = &t->rep->async_pool->slot[t->slot];
   struct Unbusy { Replica* r; AsyncSlot* s; ~Unbusy() { std::lock_guard<std::mutex> lock(r->async_mu); s->busy = false; } } unbusy{t->rep, sl};
-  HIP_TRY(hipEventSynchronize(sl->ev_out));
-  if (t->out_staged) {
-    const char* h = (const char*)sl->pin_out;
-    if (!t->autocomplete) memcpy(t->scores, h, t->sc_bytes);
-    memcpy(t->ids, h + t->sc_bytes, t->id_bytes);
-    memcpy(t->counts, h + t->sc_bytes + t->id_bytes, t->cnt_bytes);
-  }
-  return SG_OK;
+  return finish_host_call(t->call);
   SG_GUARD_END(SG_RC)
 }
 
@@ -2390,10 +2354,8 @@ static int lm_upload(sg_lm* lm, int device) {
     cb.insert(cb.end(), lv.child_begin.begin(), lv.child_begin.end());
   }
   if (flat.size() >= 0xFFFFFFF0ull) { set_error("language model too large"); return SG_E_UNSUPPORTED; }
-  int prev_dev = -1;
-  HIP_TRY(hipGetDevice(&prev_dev));
-  struct Restore { int d; ~Restore() { if (d >= 0) (void)hipSetDevice(d); } } restore{prev_dev};
-  HIP_TRY(hipSetDevice(device));
+  DeviceGuard dg;
+  HIP_TRY(dg.set(device));
   struct Owned {                                     // device blocks of an upload in progress
     std::vector<void*> p; bool keep = false;
     ~Owned() { if (!keep) for (void* x : p) (void)hipFree(x); }
@@ -2555,16 +2517,14 @@ int sg_spell_predict_batch_device(sg_index* index, sg_lm* lm, const void* d_q, c
   struct Release { sg_index* i; sg_lm* l; ~Release() { sg_lm_release(l); sg_index_release(i); } } release{index, lm};
   Replica* rep = find_replica(index, -1);
   if ((rc = lm_upload(lm, rep->device))) return rc;
-  int prev_dev = -1;
-  HIP_TRY(hipGetDevice(&prev_dev));
-  if (prev_dev != rep->device) HIP_TRY(hipSetDevice(rep->device));
-  struct Restore { int d, want; ~Restore() { if (d != want) (void)hipSetDevice(d); } } restore{prev_dev, rep->device};
+  DeviceGuard dg;
+  HIP_TRY(dg.set(rep->device));
   return predict_on_device(index, lm, rep, (const uint8_t*)d_q, (const uint64_t*)d_offs, n_q, q_bytes, top_k, similarity, (uint32_t*)d_out_ids,
                            (uint32_t*)d_out_counts, (hipStream_t)stream);
   SG_GUARD_END(SG_RC)
 }
 
-// Host buffers: one copy in (offsets | queries), the device pipeline, one copy out (rows | counts), one synchronisation.
+// Host buffers: a synchronous host-buffer call (run_host_call) around the device pipeline.
 int sg_spell_predict_batch(sg_index* index, sg_lm* lm, const uint8_t* q_utf8, const uint64_t* q_offs, uint32_t n_q, uint32_t top_k,
                            double similarity, uint32_t* out_ids, uint32_t* out_counts) {
   SG_GUARD_BEGIN
@@ -2575,42 +2535,11 @@ int sg_spell_predict_batch(sg_index* index, sg_lm* lm, const uint8_t* q_utf8, co
   struct Release { sg_index* i; sg_lm* l; ~Release() { sg_lm_release(l); sg_index_release(i); } } release{index, lm};
   Replica* rep = find_replica(index, -1);
   if ((rc = lm_upload(lm, rep->device))) return rc;
-  const size_t row = (size_t)top_k + 1;
-  const uint64_t q0 = q_offs[0], q_bytes = q_offs[n_q] - q0;
-  if (!q_utf8 && q_bytes) { set_error("null query buffer"); return SG_E_INVALID; }
-  const size_t off_bytes = (size_t)(n_q + 1) * 8, in_bytes = ((off_bytes + (size_t)q_bytes + 15) & ~(size_t)15);
-  const size_t ids_bytes = ((size_t)n_q * row * 4 + 15) & ~(size_t)15, out_bytes = ids_bytes + (size_t)n_q * 4;
-  if (std::max(in_bytes, out_bytes) > kPinnedMax && n_q > 1) {      // more than the staging buffer takes: two halves
-    const uint32_t half = n_q / 2;
-    if ((rc = sg_spell_predict_batch(index, lm, q_utf8, q_offs, half, top_k, similarity, out_ids, out_counts))) return rc;
-    return sg_spell_predict_batch(index, lm, q_utf8, q_offs + half, n_q - half, top_k, similarity, out_ids + (size_t)half * row, out_counts + half);
-  }
-  int prev_dev = -1;
-  HIP_TRY(hipGetDevice(&prev_dev));
-  HIP_TRY(hipSetDevice(rep->device));
-  struct Restore { int d; ~Restore() { if (d >= 0) (void)hipSetDevice(d); } } restore{prev_dev};
-  HostCtx* hc;
-  if ((rc = host_ctx(rep->device, std::max(in_bytes, out_bytes), &hc))) return rc;
-  if (std::max(in_bytes, out_bytes) > hc->pinned_cap) { set_error("query too large to stage"); return SG_E_INVALID; }
-  char* dev = nullptr;
-  if ((rc = ctx_device_block(hc, in_bytes + out_bytes + 32, &dev))) return rc;
-  hipStream_t st = hc->stream;
-  char* pin = (char*)hc->pinned;
-  uint64_t* po = (uint64_t*)pin;
-  if (q0) for (uint32_t i = 0; i <= n_q; i++) po[i] = q_offs[i] - q0; else memcpy(po, q_offs, off_bytes);
-  if (q_bytes) memcpy(pin + off_bytes, q_utf8 + q0, (size_t)q_bytes);
-#define TRY3(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { set_error(std::string(#expr) + ": " + hipGetErrorString(e_)); (void)hipStreamSynchronize(st); return SG_E_HIP; } } while (0)
-  TRY3(hipMemcpyAsync(dev, pin, off_bytes + (size_t)q_bytes, hipMemcpyHostToDevice, st));
-  char* d_out = dev + in_bytes;
-  rc = predict_on_device(index, lm, rep, (const uint8_t*)(dev + off_bytes), (const uint64_t*)dev, n_q, q_bytes, top_k, similarity, (uint32_t*)d_out,
-                         (uint32_t*)(d_out + ids_bytes), st);
-  if (rc) { (void)hipStreamSynchronize(st); return rc; }
-  TRY3(hipMemcpyAsync(pin, d_out, out_bytes, hipMemcpyDeviceToHost, st));
-  TRY3(hipStreamSynchronize(st));
-#undef TRY3
-  memcpy(out_ids, pin, (size_t)n_q * row * 4);
-  memcpy(out_counts, pin + ids_bytes, (size_t)n_q * 4);
-  return SG_OK;
+  const HostBufs b{q_utf8, q_offs, n_q, top_k + 1, out_ids, nullptr, out_counts, nullptr};
+  return run_host_call(rep, b, false, [&](char* dev, const IoLayout& io, hipStream_t st) {
+    return predict_on_device(index, lm, rep, (const uint8_t*)(dev + io.q), (const uint64_t*)(dev + io.offs), n_q, io.q_bytes, top_k, similarity,
+                             (uint32_t*)(dev + io.ids), (uint32_t*)(dev + io.cnt), st);
+  });
   SG_GUARD_END(SG_RC)
 }
 
@@ -2643,10 +2572,8 @@ int sg_index_launch_stats(sg_index* index, uint64_t out[4]) {
   if (!index || !out) { set_error("null argument"); return SG_E_INVALID; }
   Replica* rep = find_replica(index, -1);
   if (!rep || !rep->d_fill) { set_error("index not uploaded"); return SG_E_NOT_UPLOADED; }
-  int prev_dev = -1;
-  HIP_TRY(hipGetDevice(&prev_dev));
-  struct Restore { int d; ~Restore() { if (d >= 0) (void)hipSetDevice(d); } } restore{prev_dev};
-  HIP_TRY(hipSetDevice(rep->device));
+  DeviceGuard dg;
+  HIP_TRY(dg.set(rep->device));
   uint32_t w[SG_STAT_WORDS] = {0};
   HIP_TRY(hipDeviceSynchronize());
   HIP_TRY(hipMemcpy(w, rep->d_fill, sizeof w, hipMemcpyDeviceToHost));
@@ -2665,10 +2592,8 @@ int sg_index_pipe_stats(sg_index* index, uint64_t out[4]) {
   if (!index || !out) { set_error("null argument"); return SG_E_INVALID; }
   Replica* rep = find_replica(index, -1);
   if (!rep || !rep->d_fill) { set_error("index not uploaded"); return SG_E_NOT_UPLOADED; }
-  int prev_dev = -1;
-  HIP_TRY(hipGetDevice(&prev_dev));
-  struct Restore { int d; ~Restore() { if (d >= 0) (void)hipSetDevice(d); } } restore{prev_dev};
-  HIP_TRY(hipSetDevice(rep->device));
+  DeviceGuard dg;
+  HIP_TRY(dg.set(rep->device));
   uint32_t w[SG_STAT_WORDS] = {0};
   HIP_TRY(hipDeviceSynchronize());
   HIP_TRY(hipMemcpy(w, rep->d_fill, sizeof w, hipMemcpyDeviceToHost));
@@ -2687,10 +2612,8 @@ int sg_index_pipe_volumes(sg_index* index, uint64_t out[8]) {
   if (!index || !out) { set_error("null argument"); return SG_E_INVALID; }
   Replica* rep = find_replica(index, -1);
   if (!rep || !rep->d_fill) { set_error("index not uploaded"); return SG_E_NOT_UPLOADED; }
-  int prev_dev = -1;
-  HIP_TRY(hipGetDevice(&prev_dev));
-  struct Restore { int d; ~Restore() { if (d >= 0) (void)hipSetDevice(d); } } restore{prev_dev};
-  HIP_TRY(hipSetDevice(rep->device));
+  DeviceGuard dg;
+  HIP_TRY(dg.set(rep->device));
   uint32_t w[SG_STAT_WORDS] = {0};
   HIP_TRY(hipDeviceSynchronize());
   HIP_TRY(hipMemcpy(w, rep->d_fill, sizeof w, hipMemcpyDeviceToHost));

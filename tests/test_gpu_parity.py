@@ -731,6 +731,26 @@ def test_rows_do_not_depend_on_how_a_batch_is_cut(synth_small):
     assert_same((ids[pick], sc[pick], cnt[pick]), ora.suggest_batch(pb, po, "jaccard", 0.5, 7))
 
 
+def test_rows_above_the_staging_limit_equal_small_calls(synth_small):
+    """A call whose rows pass the 64 MB staging limit (6 000 queries x k = 1 100: 79 MB, in HBM rows above SG_K_LDS) copies
+    straight to the caller's arrays; a slice of it with offsets that do not start at zero stages only its rebased inputs.
+    Both give the rows of the same queries in staged calls of 1 000."""
+    from suggest_amd import synth
+    gpu, _, _, _ = synth_small
+    blob, offs = synth.make_dict(50000, seed=1)
+    n, k = 6000, 1100
+    qb, qo = synth.make_queries(n, blob, offs, seed=7)
+    assert n * k * 12 > 64 << 20
+    ids, sc, cnt = gpu.suggest_batch(blob=qb, offs=qo, metric="cosine", similarity=0.3, k=k)
+    lo = 500
+    si, ss, sn = gpu.suggest_batch(blob=qb, offs=qo[lo:], metric="cosine", similarity=0.3, k=k)
+    assert_same((si, ss, sn), (ids[lo:], sc[lo:], cnt[lo:]))
+    for a in range(0, n, 1000):
+        b = min(n, a + 1000)
+        i2, s2, c2 = gpu.suggest_batch(blob=qb, offs=qo[a:b + 1], metric="cosine", similarity=0.3, k=k)
+        assert_same((ids[a:b], sc[a:b], cnt[a:b]), (i2, s2, c2))
+
+
 class _OracleBacked:
     """metric.Metric (pkg/metric/metric.go:7-16) as an opaque implementation: the four methods answer from the ORACLE's
     restatement of pkg/metric/*.go, and nothing tells the engine which metric it is (code None) — it is tabulated."""

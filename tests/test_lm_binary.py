@@ -203,12 +203,10 @@ def test_predict_hand_derived_vectors_gpu():
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("slices", ["1", "3"])
-def test_predict_production_ids_vs_oracle_on_a_synthetic_model(tmp_path, monkeypatch, slices):
+def test_predict_production_ids_vs_oracle_on_a_synthetic_model(tmp_path):
     """the device pipeline (Next -> LM-ranked autocomplete -> selection -> fuzzy top-up -> merge / stable re-rank) against
     the oracle on a model in the reference's binary format: ties are broken by word id, so the id order matters"""
     import sys
-    monkeypatch.setenv("SG_SPELL_SLICES", slices)      # (big batches go through in two slices on two streams: the same path, forced)
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
     import make_synthetic_lm
     from suggest_amd.spell import LanguageModel, SpellChecker
@@ -235,3 +233,22 @@ def test_predict_production_ids_vs_oracle_on_a_synthetic_model(tmp_path, monkeyp
         valid &= (oc < 0xFFFFFFF0)[:, None]
         assert np.array_equal(ids[valid], oi[valid]), (k, sim)
     assert (cnt > k).any() or True
+    # one call whose rows pass the 64 MB staging limit (they go straight to the caller's arrays) gives the rows of two staged
+    # half-size calls — the second with offsets that do not start at zero — and of the device-resident entry point
+    import torch
+    k = 1023
+    qb, qo = oracle.pack_strings(qs * 6)
+    n, h = len(qo) - 1, (len(qo) - 1) // 2
+    assert n * (k + 1) * 4 > 64 << 20
+    ids, cnt = sc.predict_batch(blob=qb, offs=qo, top_k=k, similarity=0.5)
+    for lo, hi in ((0, h), (h, n)):
+        i2, c2 = sc.predict_batch(blob=qb, offs=qo[lo:hi + 1], top_k=k, similarity=0.5)
+        assert np.array_equal(c2, cnt[lo:hi]) and np.array_equal(i2, ids[lo:hi]), (lo, hi)
+    dev = torch.device("cuda", 0)
+    d_q = torch.from_numpy(qb).to(dev); d_o = torch.from_numpy(qo.view(np.int64)).to(dev)
+    d_ids = torch.full((n, k + 1), 7, dtype=torch.int32, device=dev); d_cnt = torch.zeros(n, dtype=torch.int32, device=dev)
+    sc.predict_batch_device(d_q.data_ptr(), d_o.data_ptr(), n, int(qo[-1]), k, 0.5, d_ids.data_ptr(), d_cnt.data_ptr(),
+                            stream=torch.cuda.current_stream(dev).cuda_stream)
+    torch.cuda.synchronize(dev)
+    assert np.array_equal(d_cnt.cpu().numpy().view(np.uint32), cnt)
+    assert np.array_equal(d_ids.cpu().numpy().view(np.uint32), ids)
