@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """bench.py — fuzzy queries/sec of the MI355X engine on BASELINE.json's workloads.
 
-  python bench.py --gpus N --steps K --warmup W [--config headline|cfg2|cfg3|cfg4|cfg5] [--mode procs|replicas]
+  python bench.py --gpus N --steps K --warmup W [--config headline|cfg2|cfg3|cfg4|cfg5] [--mode procs|replicas] [--full]
+
+A plain run does only what its headline figure needs: set up, warm up, time the K steps, write --dump-outputs, print the line.
+--full adds everything else, all of it outside the timed region: the CPU baseline and its parity check against the oracle, the
+host-buffer legs, the live PMC pass behind the roofline's traffic (a plain run takes the committed figure), the sub-configs of
+the default run, and at N > 1 the result-gather check, the per-rank oracle parity and the single-process replica leg.
 
 A "step" is one pass of the hot path (tokenise -> posting lookup -> T-occurrence count -> score -> top-k)
 over one batch of synthetic queries per GPU, inputs already resident in HBM.  The default workload is the
@@ -14,16 +19,16 @@ N > 1 (weak scaling: every GPU holds a full index replica and gets its own batch
   --mode procs (default)  one process per GPU under torch.distributed.run.  Started WITHOUT a launcher
                           (`python bench.py --gpus 8`, no WORLD_SIZE) the script runs itself as a child under
                           `python -m torch.distributed.run --nproc-per-node N` — it never measures one GPU and
-                          calls it N.  Rank 0 then also measures the single-process replica path below and
-                          reports it as `replicas_mode`, beside the process-per-GPU number.
+                          calls it N.  With --full, rank 0 then also measures the single-process replica path below
+                          and reports it as `replicas_mode`, beside the process-per-GPU number.
   --mode replicas         ONE process: sg_index_replicate over N devices + sg_suggest_batch_multi on host
                           buffers (a worker thread per replica) — what a Go host behind the C ABI runs.
                           PCIe-inclusive by construction, so its line says so (`config.pcie_inclusive`).
 
 Prints ONE JSON line on rank 0 (contract in the task statement) with
   roofline      achieved / frac = MEASURED memory traffic per call (rocprofv3 --pmc FETCH_SIZE x 1024 x 2 = the 128-byte lines
-                fetched past the L2, calibrated on this box: profiles/r05_membench.txt; live child pass of the same workload,
-                else the committed figure in profiles/traffic.json) / the call's average duration (HIP events on the launch
+                fetched past the L2, calibrated on an MI355X: profiles/r05_membench.txt; with --full a live child pass of the
+                same workload, else the committed figure in profiles/traffic.json) / the call's average duration (HIP events on the launch
                 stream) / the 8 TB/s peak — a physical fraction, always <= 1.  No counter separates Infinity-Cache hits from
                 HBM reads (membench: TCC_EA0_RDREQ_DRAM = TCC_EA0_RDREQ inside the cache as outside), so it is an UPPER
                 bound of the HBM fraction; frac_of_achievable = against the line traffic the memory system delivers for random
@@ -34,9 +39,9 @@ Prints ONE JSON line on rank 0 (contract in the task statement) with
                 query term in every admissible segment once, sg_suggest_algorithmic_bytes) over the same duration: the
                 rate a full ScanCount scan would need to answer as fast.  List skipping and compressed postings read
                 less than that volume, so this figure may exceed the peak; it is not a bandwidth.
-  cpu_baseline  the CPU oracle — a C++ restatement of the Go path, kind "port" — on this host: all hardware
+  cpu_baseline  (--full) the CPU oracle — a C++ restatement of the Go path, kind "port" — on the benchmark's host: all hardware
                 threads, and one thread (`one_thread`), each on a bounded sample of the same batch
-  configs       (default run only) sub-records for BASELINE.json's cfg2 / cfg3 / cfg4 measured the same way in the same
+  configs       (--full default run only) sub-records for BASELINE.json's cfg2 / cfg3 / cfg4 measured the same way in the same
                 process: value, kernel ms, both fractions, bit-exactness against the oracle on a sample
 """
 import argparse
@@ -85,23 +90,26 @@ def parse_args(argv=None):
     ap.add_argument("--build", default="device", choices=["device", "host"],
                     help="index build: on the GPU (sg_index_build_device, 0.4 s at 10M; the posting store stays where it was "
                          "built) or on the host (sg_index_build, then uploaded); same arrays either way")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-host-rate", action="store_true", help="skip the host-buffer legs (the profiler child passes: every call of the run is then a device-resident one)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure, after the timed region: CPU baseline and oracle parity, "
+                         "host-buffer legs, live PMC traffic, the default run's sub-configs; at N>1 the gather check, per-rank parity, replicas leg")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-host-rate", action="store_true", help="--full without the host-buffer legs")
     ap.add_argument("--cpu-sample", type=int, default=0, help="queries timed on the CPU oracle (0 = auto)")
     ap.add_argument("--sub-configs", default="auto",
                     help="comma list of configs measured after the main one and reported under `configs`: BASELINE's cfg2..cfg5, and the "
                          "result-dense workloads families / words / skewed "
-                         "(auto = cfg3,cfg4,skewed,families,cfg2,words,cfg5 for the plain default run at N=1, none otherwise; 'none' = off)")
+                         "(auto = cfg3,cfg4,skewed,families,cfg2,words,cfg5 for the --full default run at N=1, none otherwise; 'none' = off)")
     ap.add_argument("--gather", action="store_true",
                     help="N>1: include the optional RCCL all_gather of the k*(u32,f64) result rows in every timed step "
-                         "(default: results stay sharded — the path has no data-path collective; one untimed gather validates RCCL)")
+                         "(default: results stay sharded — the path has no data-path collective; with --full one untimed gather validates RCCL)")
     ap.add_argument("--traffic-bytes", type=float, default=None,
-                    help="HBM bytes per launch from a rocprofv3 --pmc run, reported as roofline.traffic (default: measured live)")
+                    help="HBM bytes per launch from a rocprofv3 --pmc run, reported as roofline.traffic (default: as --traffic says)")
     ap.add_argument("--require-traffic", action="store_true", help="exit non-zero when no traffic figure could be had for the workload")
-    ap.add_argument("--traffic", default="auto", choices=["auto", "live", "file", "none"],
+    ap.add_argument("--traffic", default=None, choices=["auto", "live", "file", "none"],
                     help="roofline.traffic: live = a rocprofv3 --pmc FETCH_SIZE pass over this same workload in a child process "
                          "(after the timed region; N=1 only); file = the committed measurement in profiles/traffic.json; "
-                         "auto = live when rocprofv3 is there, else file")
+                         "auto = live when rocprofv3 is there, else file (default: auto with --full, else file)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step computed (rank 0's result rows) as DIR/<name>.npy in "
                          "float64, at most 64 MB in all (a fixed, seeded sample of the rows above that): two builds can be compared output for output")
@@ -111,6 +119,10 @@ def parse_args(argv=None):
     if args.dump_outputs and args.mode == "replicas":
         ap.error("--dump-outputs: not available with --mode replicas")
     args.explicit_workload = any(getattr(args, k) is not None for k in WORKLOAD_KEYS)
+    if not args.full:           # a plain run: only what the headline figure needs (the N>1 extras check args.full themselves)
+        args.no_cpu_baseline = args.no_host_rate = True
+    if args.traffic is None:
+        args.traffic = "auto" if args.full else "file"
     return args
 
 
@@ -198,7 +210,7 @@ class Env:
             # The path has no data-path collective: barriers and the max over the ranks' clocks are control plane and go over
             # gloo (CPU) — a rank that waits for another keeps no spinning kernel on its GPU, and an RCCL problem on the node
             # cannot take the measurement with it.  RCCL is only needed for the optional gather of the result rows: a group of
-            # its own, made lazily, checked once outside the timed region (config.rccl_gather_check).
+            # its own, made lazily, checked once outside the timed region by --full (config.rccl_gather_check).
             dist.init_process_group("gloo")
             self.nccl_group = None
             # what became of RCCL in this run, for the line (`config.rccl_status`): a run must not look like an RCCL run when it was not
@@ -361,7 +373,7 @@ def measure(env, args, w, steps, warmup, cpu_baseline=True, host_rate=True, traf
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
     gather_ok, gather_ms = None, None
-    if world > 1:                       # functional check of the optional result gather over RCCL, and its cost per step (outside the timed region)
+    if world > 1 and args.full:         # functional check of the optional result gather over RCCL, and its cost per step (outside the timed region)
         try:
             gather(0, force=True)
             torch.cuda.synchronize(dev)
@@ -398,7 +410,7 @@ def measure(env, args, w, steps, warmup, cpu_baseline=True, host_rate=True, traf
     # ---- N > 1: every rank holds a sample of ITS OWN rows (its own batch, its own GPU, its own replica of the index) against the
     #      CPU oracle, and the ranks the RCCL group really spans are listed: a run nobody can watch checks itself ----
     parity_ranks, rccl_ranks = None, None
-    if world > 1:
+    if world > 1 and args.full:
         ok_n = torch.zeros(2, dtype=torch.float64)
         try:
             import oracle
@@ -776,14 +788,14 @@ def main():
 
     subs = []
     if args.sub_configs == "auto":
-        if env.world == 1 and args.config == "headline" and not args.explicit_workload and args.dict_variant == "uniform":
+        if args.full and env.world == 1 and args.config == "headline" and not args.explicit_workload and args.dict_variant == "uniform":
             subs = ["cfg3", "cfg4", "skewed", "families", "cfg2", "words", "cfg5"]
     elif args.sub_configs != "none":
         subs = [s for s in args.sub_configs.split(",") if s]
         if env.world > 1:
             raise SystemExit("--sub-configs is an N=1 option")
     rec = measure(env, args, w, args.steps, args.warmup, cpu_baseline=not args.no_cpu_baseline, traffic_mode=args.traffic,
-                  replicas_leg=env.world > 1, host_rate=not args.no_host_rate, dump_dir=args.dump_outputs)
+                  replicas_leg=env.world > 1 and args.full, host_rate=not args.no_host_rate, dump_dir=args.dump_outputs)
     sub_recs = {}
     for name in subs:       # cfg3 and cfg4 first: they share the headline's dictionary
         t0 = time.time()

@@ -3,8 +3,8 @@
 
 A "step" is one sg_spell_predict_batch_device call over one batch of 65,536 queries per GPU, queries and result rows resident
 in HBM: six launches on one stream (word tokeniser + word ids, NGramModel.Next, LM-ranked autocomplete, selection, Cosine
-fuzzy top-up, merge + stable re-rank).  The host-buffer entry point (sg_spell_predict_batch, PCIe-inclusive) is timed beside
-it and reported as `host_buffers`, never as `value`.  The model is synthetic
+fuzzy top-up, merge + stable re-rank).  With --full, the host-buffer entry point (sg_spell_predict_batch, PCIe-inclusive) is
+timed beside it and reported as `host_buffers`, never as `value`; so are the CPU baseline and the per-kernel PMC pass.  The model is synthetic
 (tools/make_synthetic_lm.py: Zipf words, 1M-word vocabulary, ~50M tokens incl. sentence markers), written in the
 reference's production formats (<name>.lm + <name>.cdb) and loaded through RetrieveLMFromBinary's twin; per GPU: a
 replica of the vocabulary's fuzzy index and of the LM arrays (weak scaling, no collective).
@@ -129,7 +129,7 @@ def run(args, env=None):
     res = (d_ids[0].cpu().numpy().view(np.uint32), d_cnt[0].cpu().numpy().view(np.uint32))
     # the host-buffer entry point (what a cgo caller uses): PCIe-inclusive, never `value`; same rows
     host_rate = None
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and not args.no_host_rate:
         h_ids, h_cnt = sc.predict_batch(blob=batches[0][0], offs=batches[0][1], top_k=top_k, similarity=sim)
         t0 = time.perf_counter()
         for _ in range(3):
@@ -193,13 +193,13 @@ def run(args, env=None):
         ms = elapsed / args.steps * 1e3
         kernels = None
         under_profiler = any(kk.startswith(("ROCPROF", "ROCP_")) for kk in os.environ)
-        if world == 1 and args.traffic != "none" and not under_profiler:
+        if world == 1 and args.traffic in ("auto", "live") and not under_profiler:      # (no committed figure for this workload: file = none)
             kernels = _live_kernels(args, tokens, n_q, top_k, sim, n_b, log)
         lm_k = (kernels or {}).get("lm_autocomplete")
         roof = {"bound": "hbm", "peak": 8000.0, "unit": "GB/s", "kernel": "sg_search_kernel_t<false, true, ...> (LM-ranked autocomplete: the launch with the most bytes)",
                 "achieved": lm_k["gbps"] if lm_k else None, "frac": lm_k["gbps"] / 8000.0 if lm_k else None,
                 "traffic": lm_k["traffic"] if lm_k else None,
-                "traffic_source": lm_k["source"] if lm_k else "MISSING: no live PMC pass (N > 1, --traffic none, rocprofv3 absent or under a profiler)",
+                "traffic_source": lm_k["source"] if lm_k else "MISSING: no live PMC pass (N > 1, a run without --full, --traffic none or file, rocprofv3 absent or under a profiler)",
                 "effective_gbps": alg_auto / (lm_k["ms"] * 1e-3) / 1e9 if lm_k else None,
                 "effective_frac": alg_auto / (lm_k["ms"] * 1e-3) / 1e9 / 8000.0 if lm_k else None,
                 "algorithmic_bytes_per_launch": alg_auto, "step_gpu_ms_avg": gpu_ms, "kernels": kernels,

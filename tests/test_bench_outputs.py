@@ -47,6 +47,21 @@ def test_dump_outputs_samples_above_the_limit_the_same_rows_every_time(tmp_path,
     assert np.array_equal(np.load(tmp_path / "a" / "scores.npy"), sc[r])
 
 
+def test_plain_run_leaves_the_extras_to_full():
+    """a plain run does only what the headline figure needs; --full brings back the CPU baseline, the host-buffer legs, the live
+    PMC pass and the default run's sub-configs, and its own off switches still hold there"""
+    import bench
+    plain = bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert not plain.full and plain.no_cpu_baseline and plain.no_host_rate and plain.traffic == "file"
+    assert (plain.steps, plain.warmup, plain.dump_outputs) == (20, 5, None)
+    full = bench.parse_args(["--full"])
+    assert full.full and not full.no_cpu_baseline and not full.no_host_rate and full.traffic == "auto"
+    assert plain.sub_configs == full.sub_configs == "auto"          # (main() fills `auto` in a --full run only)
+    some = bench.parse_args(["--full", "--no-cpu-baseline", "--traffic", "none"])
+    assert some.no_cpu_baseline and not some.no_host_rate and some.traffic == "none"
+    assert bench.parse_args(["--traffic", "live"]).traffic == "live"
+
+
 @pytest.mark.gpu
 def test_bench_dumps_the_last_steps_rows(tmp_path):
     """a small workload through bench.py: --steps is the number of timed steps, ms_per_step is on the line, and the dumped rows

@@ -190,7 +190,7 @@ def test_bench_two_ranks_on_one_gpu(tmp_path):
     env = dict(os.environ, SG_BENCH_SINGLE_DEVICE="1", SG_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29533", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--dict-size", "200000", "--queries", "4096", "--build", "host"]
+           "--dict-size", "200000", "--queries", "4096", "--build", "host", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]
@@ -220,7 +220,7 @@ def test_bench_two_ranks_attempt_rccl_and_say_what_happened():
         env["SG_BENCH_SINGLE_DEVICE"] = "1"
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29547", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--dict-size", "200000", "--queries", "4096", "--build", "host"]
+           "--dict-size", "200000", "--queries", "4096", "--build", "host", "--full"]
     import signal
     proc = subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env, cwd=ROOT, start_new_session=True)
     try:
@@ -249,7 +249,7 @@ def test_bench_self_spawns_two_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(SG_BENCH_SINGLE_DEVICE="1", SG_BENCH_BACKEND="gloo")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--dict-size", "100000", "--queries", "2048"]
+           "--dict-size", "100000", "--queries", "2048", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     rec = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])

@@ -72,9 +72,9 @@ PY
   suite)        # suite <tag> [pytest args]: the GPU suite
     tag=$1; shift
     timeout 2400 python -m pytest tests -m gpu -x -q "$@" > $O/${tag}_pytest.log 2>&1; tail -5 $O/${tag}_pytest.log ;;
-  bench)        # bench <tag> [bench args]: the default bench line
+  bench)        # bench <tag> [bench args]: the full bench line (--full: CPU baseline, host legs, live PMC pass, sub-configs)
     tag=$1; shift
-    timeout 1500 python bench.py "$@" > $O/${tag}_bench.json 2> $O/${tag}_bench.err; tail -3 $O/${tag}_bench.err; tail -c 3000 $O/${tag}_bench.json ;;
+    timeout 1500 python bench.py --full "$@" > $O/${tag}_bench.json 2> $O/${tag}_bench.err; tail -3 $O/${tag}_bench.err; tail -c 3000 $O/${tag}_bench.json ;;
   bench_prof)   # bench_prof <tag> [bench args]: rocprofv3 --kernel-trace --stats of a bench.py run (the summary the roofline's kernel time must agree with)
     tag=$1; shift
     cd /tmp && timeout 1500 rocprofv3 --kernel-trace --stats -d $O/${tag}_benchprof -o run -- python $R/bench.py --no-cpu-baseline --traffic none "$@" > $O/${tag}_benchprof.json 2> $O/${tag}_benchprof.err

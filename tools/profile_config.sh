@@ -14,7 +14,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-python $R/bench.py --config $CFG "$@" > $O/${TAG}_bench_$CFG.json 2> $O/${TAG}_bench_$CFG.err
+python $R/bench.py --config $CFG --full "$@" > $O/${TAG}_bench_$CFG.json 2> $O/${TAG}_bench_$CFG.err
 W=3; K=6
 rm -rf $O/${TAG}_trace_$CFG
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${TAG}_trace_$CFG -- python $R/bench.py --config $CFG --steps $K --warmup $W --no-cpu-baseline --traffic none "$@" > $O/${TAG}_trace_$CFG.log 2>&1
