@@ -950,6 +950,7 @@ paging:
 type SpellChecker struct {
 	lm     *C.sg_lm
 	index  *C.sg_index
+	device int
 	mu     sync.RWMutex
 	closed bool
 }
@@ -1005,6 +1006,7 @@ func (sc *SpellChecker) finish(d suggest.IndexDescription, device int) (*SpellCh
 		C.sg_lm_release(sc.lm)
 		return nil, err
 	}
+	sc.device = device
 	runtime.SetFinalizer(sc, func(s *SpellChecker) { s.Close() })
 	return sc, nil
 }
@@ -1068,6 +1070,43 @@ func (s *SpellChecker) Predict(query string, topK int, similarity float64) ([]st
 			return nil, fmt.Errorf("suggest_hip: bad word id %d", uint32(ids[i]))
 		}
 		out = append(out, string(buf[:n]))
+	}
+	return out, nil
+}
+
+// ScoreSentences is `lm eval` for a batch (cmd/language-model/cmd/eval.go:41-61): LanguageModel.ScoreSentence of
+// Tokenize(line) for every line (pkg/lm/language_model.go:72-92), on the GPU that holds the model (sg_lm_score_text_batch).
+func (s *SpellChecker) ScoreSentences(lines []string) ([]float64, error) {
+	if len(lines) == 0 {
+		return nil, nil
+	}
+	var blob []byte
+	offs := make([]C.uint64_t, 1, len(lines)+1)
+	for _, l := range lines {
+		blob = append(blob, l...)
+		offs = append(offs, C.uint64_t(len(blob)))
+	}
+	var bp *C.uint8_t
+	if len(blob) > 0 {
+		bp = (*C.uint8_t)(unsafe.Pointer(&blob[0]))
+	}
+	scores := make([]C.double, len(lines))
+	s.mu.RLock() // the model stays valid while this call is in flight
+	if s.closed {
+		s.mu.RUnlock()
+		return nil, errClosed
+	}
+	C.sg_lm_retain(s.lm)
+	s.mu.RUnlock()
+	defer func() { C.sg_lm_release(s.lm); runtime.KeepAlive(s) }()
+	if err := ccall(func() C.int {
+		return C.sg_lm_score_text_batch(s.lm, C.int(s.device), bp, &offs[0], C.uint32_t(len(lines)), &scores[0], nil, nil)
+	}); err != nil {
+		return nil, err
+	}
+	out := make([]float64, len(lines))
+	for i, v := range scores {
+		out[i] = float64(v)
 	}
 	return out, nil
 }

@@ -258,6 +258,27 @@ int sg_lm_next_score(const sg_lm* lm, const uint32_t* context, uint32_t n, uint3
 /* lm.NewTokenizer(alphabet).Tokenize (pkg/lm/tokenizer.go:26-31): tokens joined by '\n' into out; returns their number */
 int sg_lm_tokenize(const sg_lm* lm, const uint8_t* text, uint32_t len, char* out, uint32_t cap);
 
+/* LanguageModel.ScoreSentence / ScoreWordIDs for a batch, on the GPU `device` (pkg/lm/language_model.go:55-92, ngram_model.go:44-62,
+ * 163-175; generator.go:9-24).  The first call uploads the model to `device` (the lazy upload Predict uses); a model already
+ * resident on another device fails with SG_E_INVALID.  A sentence with fewer than order - 2 words has no window and scores 0.0.
+ * The device evaluates log() with its own math library: scores agree with sg_lm_score_word_ids to about an ulp of the log, not
+ * necessarily to the bit.  n == 0 returns SG_OK without touching a device. */
+/* lm eval / ScoreSentence(Tokenize(line)) for a batch of lines (cmd/language-model/cmd/eval.go:41-61): line i is
+ * text[offs[i] .. offs[i+1]), at most 1 GiB of text in all.  out_scores[i] gets its score, out_words[i] the tokens of
+ * Tokenize(line), out_unknown[i] how many of them have no id (indexer.go:57-71: UnknownWordID, no error); out_words /
+ * out_unknown may be null. */
+int sg_lm_score_text_batch(sg_lm* lm, int device, const uint8_t* text, const uint64_t* offs, uint32_t n,
+                           double* out_scores, uint32_t* out_words, uint32_t* out_unknown);
+/* The same with every buffer in the HBM of `device`, asynchronous on `stream`: d_text = text_bytes bytes, d_offs = n + 1 uint64
+ * offsets starting at 0, d_out_scores = [n] double, d_out_words / d_out_unknown = [n] uint32 or null. */
+int sg_lm_score_text_batch_device(sg_lm* lm, int device, const void* d_text, const void* d_offs, uint32_t n,
+                                  uint64_t text_bytes, void* d_out_scores, void* d_out_words, void* d_out_unknown,
+                                  void* stream);
+/* ScoreWordIDs (language_model.go:83-92) for a batch: sentence i = ids[offs[i] .. offs[i+1]) (offsets in ids, at most 2^30
+ * ids in all); any id is allowed (an id outside the vocabulary scores as an unknown word). */
+int sg_lm_score_word_ids_batch(sg_lm* lm, int device, const uint32_t* ids, const uint64_t* offs, uint32_t n,
+                               double* out_scores);
+
 /* The fuzzy index of the spellchecker: built over the model's vocabulary (docID = word id) and uploaded —
  * internal/spellchecker/dep/spellchecker.go:33-45 (NewRAMBuilder over the LM dictionary). */
 int sg_spell_index_build(const sg_lm* lm, const sg_desc* desc, int device, sg_index** out);

@@ -676,6 +676,29 @@ class LanguageModel {  // language_model.go:8-14 over NewGoogleNGramReader(order
   }
   size_t Size() const { return sg_lm_num_words(h_); }
 
+  // ScoreSentence for a batch of token lists on the GPU `device` (sg_lm_score_word_ids_batch)
+  std::vector<double> ScoreSentences(const std::vector<std::vector<std::string>>& sentences, int device = 0) const {
+    std::vector<WordID> ids;
+    std::vector<uint64_t> offs(1, 0);
+    for (auto& s : sentences) {
+      for (auto& w : s) ids.push_back(GetWordID(w));
+      offs.push_back(ids.size());
+    }
+    std::vector<double> out(sentences.size());
+    NGramIndex::Check(sg_lm_score_word_ids_batch(h_, device, ids.data(), offs.data(), (uint32_t)sentences.size(), out.data()));
+    return out;
+  }
+  // `lm eval` for a batch: ScoreSentence(Tokenize(line)) of every line on the GPU `device` (sg_lm_score_text_batch)
+  std::vector<double> ScoreText(const std::vector<std::string>& lines, int device = 0) const {
+    std::string blob;
+    std::vector<uint64_t> offs(1, 0);
+    for (auto& l : lines) { blob += l; offs.push_back(blob.size()); }
+    std::vector<double> out(lines.size());
+    NGramIndex::Check(sg_lm_score_text_batch(h_, device, (const uint8_t*)blob.data(), offs.data(), (uint32_t)lines.size(), out.data(), nullptr,
+                                             nullptr));
+    return out;
+  }
+
  private:
   sg_lm* h_ = nullptr;
 };

@@ -27,6 +27,7 @@ EXPORTS = [
     "sg_debug_poison", "sg_debug_poison_stats", "sg_debug_rows_layout", "sg_debug_pipe_layout",
     "sg_host_alloc", "sg_host_free", "sg_suggest_submit", "sg_suggest_submit_on", "sg_autocomplete_submit", "sg_ticket_wait",
     "sg_metric_tables_create", "sg_metric_tables_retain", "sg_metric_tables_release", "sg_suggest_batch_tables", "sg_suggest_batch_from", "sg_index_launch_stats", "sg_index_pipe_stats", "sg_index_pipe_volumes",
+    "sg_lm_score_text_batch", "sg_lm_score_text_batch_device", "sg_lm_score_word_ids_batch",
 ]
 SG_COUNT_LM_ERROR = 0xFFFFFFFC
 
@@ -111,6 +112,9 @@ def lib():
         f.restype = dbl
     if hasattr(L, "sg_lm_next_score"): L.sg_lm_next_score.argtypes = [vp, vp, u32, u32, i32, C.POINTER(dbl)]
     if hasattr(L, "sg_lm_tokenize"): L.sg_lm_tokenize.argtypes = [vp, C.c_char_p, u32, C.c_char_p, u32]
+    if hasattr(L, "sg_lm_score_text_batch"): L.sg_lm_score_text_batch.argtypes = [vp, i32, vp, vp, u32, vp, vp, vp]
+    if hasattr(L, "sg_lm_score_text_batch_device"): L.sg_lm_score_text_batch_device.argtypes = [vp, i32, vp, vp, u32, u64, vp, vp, vp, vp]
+    if hasattr(L, "sg_lm_score_word_ids_batch"): L.sg_lm_score_word_ids_batch.argtypes = [vp, i32, vp, vp, u32, vp]
     if hasattr(L, "sg_spell_index_build"): L.sg_spell_index_build.argtypes = [vp, C.POINTER(SgDesc), i32, C.POINTER(vp)]
     if hasattr(L, "sg_spell_predict_batch"): L.sg_spell_predict_batch.argtypes = [vp, vp, vp, vp, u32, u32, dbl, vp, vp]
     if hasattr(L, "sg_spell_predict_batch_device"): L.sg_spell_predict_batch_device.argtypes = [vp, vp, vp, vp, u32, C.c_uint64, u32, dbl, vp, vp, vp]

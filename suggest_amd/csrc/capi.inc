@@ -204,6 +204,11 @@ struct sg_lm {
   uint2* d_alpha_ranges = nullptr; uint32_t n_alpha_ranges = 0; uint64_t alpha_ascii[2] = {0, 0};
   uint4* d_vocab = nullptr; uint32_t vocab_mask = 0;
   uint8_t* d_vocab_bytes = nullptr; uint32_t* d_vocab_off = nullptr;
+  // sentence scoring (lm_score.inc): its own copy of the simple lower-case pairs (there is no index replica to take them from),
+  // whether the unigram level is every word in id order (a direct index instead of a search), a line's slot per byte
+  uint32_t* d_lower_from = nullptr; uint32_t* d_lower_to = nullptr; uint32_t n_lower = 0;
+  bool uni_dense = false;
+  uint32_t slot_mul = 2;
 };
 
 static void* g_prof_buf = nullptr;   // SG_PHASE_TIMING builds only (sg_debug_set_prof)
@@ -340,8 +345,9 @@ struct GrowBlock {
 // several streams during an index swap, tests/cpp/service_test.cpp).  hipFree waits for the device, so growing or
 // dropping a buffer never pulls it from under a running kernel.
 // A block per tag: one launch holds SCRATCH_ROWS, SCRATCH_LONG_LIST and one of SCRATCH_PRETOK / SCRATCH_PIPE of its stream at
-// once, and Predict's block besides when Predict is the caller — four at most.
-enum ScratchTag { SCRATCH_ROWS = 0, SCRATCH_PREDICT = 1, SCRATCH_LONG_LIST = 2, SCRATCH_PRETOK = 3, SCRATCH_PIPE = 4 };
+// once, and Predict's block besides when Predict is the caller — four at most.  Sentence scoring (lm_score.inc) holds its own
+// block alone.
+enum ScratchTag { SCRATCH_ROWS = 0, SCRATCH_PREDICT = 1, SCRATCH_LONG_LIST = 2, SCRATCH_PRETOK = 3, SCRATCH_PIPE = 4, SCRATCH_LM_SCORE = 5 };
 struct ScratchSlot { int device; hipStream_t stream; int tag; GrowBlock blk; };
 inline bool on_main_thread() { return (long)getpid() == (long)syscall(SYS_gettid); }
 // (a thread that ends hands its buffers back; the main thread's are left to process exit, when the HIP runtime may already
@@ -1552,14 +1558,14 @@ static int finish_host_call(const HostCall& c) {
   return SG_OK;
 }
 
-// A synchronous host-buffer call: begin and finish on the calling thread's context for the replica's device, whose current
-// device is the same afterwards.
-static int run_host_call(Replica* rep, const HostBufs& b, bool clear_rows, const Enqueue& enqueue) {
+// A synchronous host-buffer call: begin and finish on the calling thread's context for `device`, whose current device is the
+// same afterwards.
+static int run_host_call(int device, const HostBufs& b, bool clear_rows, const Enqueue& enqueue) {
   if (b.n_q == 0) return SG_OK;
   DeviceGuard dg;
-  HIP_TRY(dg.set(rep->device));
+  HIP_TRY(dg.set(device));
   HostCtx* ctx;
-  if (int rc = host_ctx(rep->device, &ctx)) return rc;
+  if (int rc = host_ctx(device, &ctx)) return rc;
   IoCtx x;
   x.in = x.run = x.out = ctx->stream;
   x.dev = &ctx->dblock; x.pin_in = x.pin_out = &ctx->pinned;
@@ -1597,7 +1603,7 @@ static HostBufs search_bufs(const uint8_t* q, const uint64_t* offs, uint32_t n_q
 static int run_host(sg_index* index, Replica* rep, const uint8_t* q, const uint64_t* offs, uint32_t n_q, const LaunchReq& r,
                     uint32_t* ids, double* scores, uint32_t* counts, uint32_t* aux = nullptr) {
   const HostBufs b = search_bufs(q, offs, n_q, r, ids, scores, counts, aux);
-  return run_host_call(rep, b, true, search_enqueue(index, rep, r, b));
+  return run_host_call(rep->device, b, true, search_enqueue(index, rep, r, b));
 }
 
 int sg_suggest_batch(sg_index* index, const uint8_t* q, const uint64_t* offs, uint32_t n_q, int metric, double similarity,
@@ -2292,6 +2298,7 @@ void sg_lm_release(sg_lm* lm) {
   if (lm->d_values) {
     (void)hipSetDevice(lm->device); (void)hipFree(lm->d_values); (void)hipFree(lm->d_child_begin);
     (void)hipFree(lm->d_alpha_ranges); (void)hipFree(lm->d_vocab); (void)hipFree(lm->d_vocab_bytes); (void)hipFree(lm->d_vocab_off);
+    (void)hipFree(lm->d_lower_from); (void)hipFree(lm->d_lower_to);
   }
   delete lm;
 }
@@ -2410,6 +2417,14 @@ static int lm_upload(sg_lm* lm, int device) {
     if (!bytes.empty()) HIP_TRY(hipMemcpy(vb, bytes.data(), bytes.size(), hipMemcpyHostToDevice));
     LM_ALLOC(vo, (nw + 1) * 4);
     HIP_TRY(hipMemcpy(vo, off.data(), (nw + 1) * 4, hipMemcpyHostToDevice));
+    // ... and, for sentence scoring, the simple lower-case pairs (Predict takes the index replica's)
+    std::vector<uint32_t> lf, lt;
+    for (const auto& pr : kLowerPairs) { lf.push_back(pr.from); lt.push_back(pr.to); }
+    void *lfd = nullptr, *ltd = nullptr;
+    LM_ALLOC(lfd, lf.size() * 4);
+    HIP_TRY(hipMemcpy(lfd, lf.data(), lf.size() * 4, hipMemcpyHostToDevice));
+    LM_ALLOC(ltd, lt.size() * 4);
+    HIP_TRY(hipMemcpy(ltd, lt.data(), lt.size() * 4, hipMemcpyHostToDevice));
 #undef LM_ALLOC
     // ---- every step succeeded: commit ----
     owned.keep = true;
@@ -2418,6 +2433,15 @@ static int lm_upload(sg_lm* lm, int device) {
     lm->alpha_ascii[0] = alpha_ascii[0]; lm->alpha_ascii[1] = alpha_ascii[1];
     lm->d_vocab = (uint4*)vt; lm->vocab_mask = (uint32_t)(cap - 1);
     lm->d_vocab_bytes = (uint8_t*)vb; lm->d_vocab_off = (uint32_t*)vo;
+    lm->d_lower_from = (uint32_t*)lfd; lm->d_lower_to = (uint32_t*)ltd; lm->n_lower = (uint32_t)lf.size();
+    // (a token of invalid bytes lengthens 1 -> 3 bytes when U+FFFD is in the alphabet; a lower-case mapping 2 -> 3 at most)
+    lm->slot_mul = host_alphabet_has(h.alphabet, kRuneError) ? 3u : 2u;
+  }
+  {  // the unigram level as a direct index: one bucket (the orphans') holding word i at entry i, every i
+    const LmLevel& u = lm->host.level[0];
+    bool dense = u.child_begin.size() == 2 && u.child_begin[0] == 0 && u.child_begin[1] == u.word.size();
+    for (size_t i = 0; dense && i < u.word.size(); i++) dense = u.word[i] == (uint32_t)i;
+    lm->uni_dense = dense;
   }
   lm->level_base = std::move(level_base); lm->cb_base = std::move(cb_base);
   lm->d_child_begin = (uint32_t*)q;
@@ -2536,9 +2560,130 @@ int sg_spell_predict_batch(sg_index* index, sg_lm* lm, const uint8_t* q_utf8, co
   Replica* rep = find_replica(index, -1);
   if ((rc = lm_upload(lm, rep->device))) return rc;
   const HostBufs b{q_utf8, q_offs, n_q, top_k + 1, out_ids, nullptr, out_counts, nullptr};
-  return run_host_call(rep, b, false, [&](char* dev, const IoLayout& io, hipStream_t st) {
+  return run_host_call(rep->device, b, false, [&](char* dev, const IoLayout& io, hipStream_t st) {
     return predict_on_device(index, lm, rep, (const uint8_t*)(dev + io.q), (const uint64_t*)(dev + io.offs), n_q, io.q_bytes, top_k, similarity,
                              (uint32_t*)(dev + io.ids), (uint32_t*)(dev + io.cnt), st);
+  });
+  SG_GUARD_END(SG_RC)
+}
+
+// ---- LanguageModel.ScoreSentence / ScoreWordIDs for a batch (lm_score.inc) ----
+static const uint64_t kLmTextMax = (uint64_t)1 << 30;    // bytes of a text batch: a line's slot (3 bytes per byte at most) has 32-bit offsets
+
+// The launches of one batch on `st`, every pointer on the device.  is_text: lines (text_bytes bytes, n + 1 byte offsets)
+// through the tokeniser first; else ids with n + 1 BYTE offsets into them.  words / unknown may be null.
+static int lm_score_on_device(sg_lm* lm, int device, bool is_text, const uint8_t* text, uint64_t text_bytes, const uint32_t* ids, const uint64_t* offs,
+                              uint32_t n, uint64_t n_ids, double* scores, uint32_t* words, uint32_t* unknown, hipStream_t st) {
+  const HostLM& h = lm->host;
+  LmScoreArgs a{};
+  SpellArgs& p = a.sp;
+  p.values = lm->d_values; p.child_begin = lm->d_child_begin;
+  for (size_t l = 0; l < h.level.size(); l++) {
+    p.level_base[l] = lm->level_base[l]; p.cb_base[l] = lm->cb_base[l];
+    p.n_parents[l] = l ? (uint32_t)h.level[l - 1].word.size() : 0u;
+  }
+  p.order = h.order; p.n_q = n;
+  p.alpha_ranges = lm->d_alpha_ranges; p.n_alpha_ranges = lm->n_alpha_ranges; p.alpha_ascii[0] = lm->alpha_ascii[0]; p.alpha_ascii[1] = lm->alpha_ascii[1];
+  p.lower_from = lm->d_lower_from; p.lower_to = lm->d_lower_to; p.n_lower = lm->n_lower;
+  p.vocab = lm->d_vocab; p.vocab_mask = lm->vocab_mask; p.vocab_bytes = lm->d_vocab_bytes; p.vocab_off = lm->d_vocab_off;
+  p.start_symbol = h.start_symbol;
+  p.q_blob = text;
+  a.n = n; a.end_symbol = h.end_symbol; a.total0 = (uint32_t)h.level[0].total; a.n_uni = (uint32_t)h.level[0].word.size();
+  a.uni_dense = lm->uni_dense ? 1u : 0u; a.text = is_text ? 1u : 0u; a.slot_mul = lm->slot_mul; a.text_bytes = text_bytes;
+  a.offs = offs; a.ids = ids; a.out_scores = scores; a.out_words = words; a.out_unknown = unknown;
+  // sentences per workgroup: about two rounds of SG_LM_GROUP windows (a text line: a word per ~6 bytes, a guess)
+  const double per = is_text ? (double)text_bytes / n / 6.0 + 1.0 : (double)n_ids / n;
+  const double win = std::max(1.0, per + 3.0 - (double)h.order);
+  a.per_group = (uint32_t)std::min<double>(SG_LM_GROUP, std::max(4.0, 2.0 * SG_LM_GROUP / win));
+  if (is_text) {
+    Carve c;
+    const size_t o_blob = c.take((size_t)text_bytes * lm->slot_mul + 16), o_tok = c.take(((size_t)(text_bytes >> 1) + n + 1) * 4),
+                 o_ntok = c.take((size_t)n * 4), o_wlen = c.take((size_t)n * 4);
+    void* blk = nullptr;
+    if (int rc = stream_scratch(device, st, c.size(), &blk, SCRATCH_LM_SCORE)) return rc;
+    char* dev = (char*)blk;
+    a.w_blob = (uint8_t*)(dev + o_blob); a.tok = (uint32_t*)(dev + o_tok); a.n_tok = (uint32_t*)(dev + o_ntok); a.w_len = (uint32_t*)(dev + o_wlen);
+    hipLaunchKernelGGL(lm_text_tokenize_kernel, dim3((n + 255) / 256), dim3(256), 0, st, a);
+  }
+  hipLaunchKernelGGL(lm_score_kernel, dim3((n + a.per_group - 1) / a.per_group), dim3(SG_LM_GROUP), 0, st, a);
+  HIP_TRY(hipGetLastError());
+  return SG_OK;
+}
+
+// the arguments every scoring entry point checks before any HIP call
+static int lm_score_check(sg_lm* lm, int device, const void* offs, const void* scores) {
+  if (!lm || !offs || !scores) { set_error("null argument"); return SG_E_INVALID; }
+  if (device < 0) { set_error("negative device"); return SG_E_INVALID; }
+  if (lm->host.order < 1 || lm->host.order > 8) { set_error("nGramOrder outside 1 .. 8"); return SG_E_UNSUPPORTED; }
+  return SG_OK;
+}
+
+// host offsets: ascending, the buffer they index present, at most max_span units of it
+static int lm_check_offsets(const void* buf, const uint64_t* offs, uint32_t n, uint64_t max_span) {
+  for (uint32_t i = 0; i < n; i++)
+    if (offs[i + 1] < offs[i]) { set_error("offsets are not ascending"); return SG_E_INVALID; }
+  if (!buf && offs[n] != offs[0]) { set_error("null input buffer"); return SG_E_INVALID; }
+  if (offs[n] - offs[0] > max_span) { set_error("batch too large"); return SG_E_INVALID; }
+  return SG_OK;
+}
+
+int sg_lm_score_text_batch(sg_lm* lm, int device, const uint8_t* text, const uint64_t* offs, uint32_t n, double* out_scores, uint32_t* out_words,
+                           uint32_t* out_unknown) {
+  SG_GUARD_BEGIN
+  int rc = lm_score_check(lm, device, offs, out_scores);
+  if (rc) return rc;
+  if (n == 0) return SG_OK;
+  if ((rc = lm_check_offsets(text, offs, n, kLmTextMax))) return rc;
+  sg_lm_retain(lm);
+  struct Release { sg_lm* l; ~Release() { sg_lm_release(l); } } release{lm};
+  if ((rc = lm_upload(lm, device))) return rc;
+  std::vector<uint32_t> words_tmp, unknown_tmp;                  // (the host-buffer path copies both rows back)
+  if (!out_words) { words_tmp.resize(n); out_words = words_tmp.data(); }
+  if (!out_unknown) { unknown_tmp.resize(n); out_unknown = unknown_tmp.data(); }
+  const HostBufs b{text, offs, n, 1, out_words, out_scores, out_unknown, nullptr};
+  return run_host_call(device, b, true, [&](char* dev, const IoLayout& io, hipStream_t st) {
+    return lm_score_on_device(lm, device, true, (const uint8_t*)(dev + io.q), io.q_bytes, nullptr, (const uint64_t*)(dev + io.offs), n, 0, (double*)dev,
+                              (uint32_t*)(dev + io.ids), (uint32_t*)(dev + io.cnt), st);
+  });
+  SG_GUARD_END(SG_RC)
+}
+
+int sg_lm_score_text_batch_device(sg_lm* lm, int device, const void* d_text, const void* d_offs, uint32_t n, uint64_t text_bytes, void* d_out_scores,
+                                  void* d_out_words, void* d_out_unknown, void* stream) {
+  SG_GUARD_BEGIN
+  int rc = lm_score_check(lm, device, d_offs, d_out_scores);
+  if (rc) return rc;
+  if (n == 0) return SG_OK;
+  if (!d_text && text_bytes) { set_error("null text"); return SG_E_INVALID; }
+  if (text_bytes > kLmTextMax) { set_error("text batch above 1 GiB"); return SG_E_INVALID; }
+  sg_lm_retain(lm);
+  struct Release { sg_lm* l; ~Release() { sg_lm_release(l); } } release{lm};
+  if ((rc = lm_upload(lm, device))) return rc;
+  DeviceGuard dg;
+  HIP_TRY(dg.set(device));
+  return lm_score_on_device(lm, device, true, (const uint8_t*)d_text, text_bytes, nullptr, (const uint64_t*)d_offs, n, 0,
+                            (double*)d_out_scores, (uint32_t*)d_out_words, (uint32_t*)d_out_unknown, (hipStream_t)stream);
+  SG_GUARD_END(SG_RC)
+}
+
+int sg_lm_score_word_ids_batch(sg_lm* lm, int device, const uint32_t* ids, const uint64_t* offs, uint32_t n, double* out_scores) {
+  SG_GUARD_BEGIN
+  int rc = lm_score_check(lm, device, offs, out_scores);
+  if (rc) return rc;
+  if (n == 0) return SG_OK;
+  if ((rc = lm_check_offsets(ids, offs, n, (uint64_t)1 << 30))) return rc;
+  sg_lm_retain(lm);
+  struct Release { sg_lm* l; ~Release() { sg_lm_release(l); } } release{lm};
+  if ((rc = lm_upload(lm, device))) return rc;
+  // the host-buffer path moves bytes: the ids as a blob, offsets in bytes from the first sentence's ids on
+  std::vector<uint64_t> boffs((size_t)n + 1);
+  for (uint32_t i = 0; i <= n; i++) boffs[i] = (offs[i] - offs[0]) * 4;
+  std::vector<uint32_t> rows_a(n), rows_b(n);                    // (the two u32 rows of the host-buffer block: unused here)
+  const HostBufs b{(const uint8_t*)(ids ? ids + offs[0] : nullptr), boffs.data(), n, 1, rows_a.data(), out_scores, rows_b.data(), nullptr};
+  const uint64_t n_ids = offs[n] - offs[0];
+  return run_host_call(device, b, true, [&](char* dev, const IoLayout& io, hipStream_t st) {
+    return lm_score_on_device(lm, device, false, nullptr, 0, (const uint32_t*)(dev + io.q), (const uint64_t*)(dev + io.offs), n, n_ids, (double*)dev,
+                              nullptr, nullptr, st);
   });
   SG_GUARD_END(SG_RC)
 }

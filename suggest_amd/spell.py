@@ -95,6 +95,55 @@ class LanguageModel:
         ids = self._ids(words)
         return float(_lib.lib().sg_lm_score_word_ids(self._h, ids.ctypes.data, len(ids)))
 
+    def _vocab(self):
+        """token bytes -> word id, built once (Indexer.Get without a call per token; a word listed twice keeps its first id)"""
+        v = getattr(self, "_vocab_ids", None)
+        if v is None:
+            v = {}
+            for i, w in enumerate(self.words()):
+                v.setdefault(w, i)
+            self._vocab_ids = v
+        return v
+
+    def ScoreSentenceBatch(self, sentences, device=0):
+        """ScoreSentence for every token list of `sentences` on the GPU (sg_lm_score_word_ids_batch) -> float64 [n]"""
+        v = self._vocab()
+        lens = np.array([len(s) for s in sentences], dtype=np.uint64)
+        offs = np.zeros(len(sentences) + 1, dtype=np.uint64)
+        offs[1:] = np.cumsum(lens, dtype=np.uint64)
+        ids = np.fromiter((v.get(_enc(w), 0xFFFFFFFF) for s in sentences for w in s), dtype=np.uint32, count=int(offs[-1]))
+        return self.score_word_ids_batch(ids, offs, device)
+
+    def score_word_ids_batch(self, ids, offs, device=0):
+        """ScoreWordIDs of ids[offs[i] .. offs[i+1]) for every i on the GPU -> float64 [n]"""
+        ids = np.ascontiguousarray(ids, dtype=np.uint32)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        n = len(offs) - 1
+        out = np.zeros(n, dtype=np.float64)
+        _lib.check(_lib.lib().sg_lm_score_word_ids_batch(self._h, int(device), ids.ctypes.data if ids.size else None, offs.ctypes.data, n,
+                                                         out.ctypes.data))
+        return out
+
+    def score_text_batch(self, lines=None, blob=None, offs=None, device=0):
+        """`lm eval` for a batch: ScoreSentence(Tokenize(line)) of every line on the GPU (sg_lm_score_text_batch)
+        -> (scores float64 [n], words uint32 [n] = len(Tokenize(line)), unknown uint32 [n] = its tokens without an id)"""
+        if blob is None:
+            blob, offs = pack_strings(lines)
+        blob = np.ascontiguousarray(blob, dtype=np.uint8)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        n = len(offs) - 1
+        scores = np.zeros(n, dtype=np.float64)
+        words = np.zeros(n, dtype=np.uint32)
+        unknown = np.zeros(n, dtype=np.uint32)
+        _lib.check(_lib.lib().sg_lm_score_text_batch(self._h, int(device), blob.ctypes.data if blob.size else None, offs.ctypes.data, n,
+                                                     scores.ctypes.data, words.ctypes.data, unknown.ctypes.data))
+        return scores, words, unknown
+
+    def score_text_batch_device(self, d_blob, d_offs, n, text_bytes, d_scores, d_words=None, d_unknown=None, stream=0, device=0):
+        """sg_lm_score_text_batch_device: raw device pointers (torch tensors' data_ptr()), asynchronous on `stream`"""
+        _lib.check(_lib.lib().sg_lm_score_text_batch_device(self._h, int(device), d_blob, d_offs, int(n), int(text_bytes), d_scores, d_words,
+                                                            d_unknown, stream))
+
     def next_score(self, context, word, model_level=False):
         """Next(context).ScoreNext(word) -> (status, score); status 0 scorer, 1 nil scorer, 2 error"""
         ids = self._ids(context)
