@@ -345,6 +345,10 @@ int sg_debug_tune_choice(double est_query_chunks, double max_term_chunks, int32_
  * 2^11 / 2^12 / 2^13 counters.  No GPU needed; no reference counterpart. */
 int sg_debug_pipe_shape(double est_query_chunks, double terms_per_doc, int32_t t_floor, int32_t metric, double similarity, int32_t* out_shape);
 int sg_debug_tune_index(sg_index* index, double out_stats[2], int32_t out[6]);
+/* Test hook (no GPU needed): row i of the knob table (i = 0 .. n-1; SG_E_INVALID past the end): its name, out = {lowest, highest,
+ * default, flags: 1 environment, 2 sg_index_tune, 4 pins the stream shape, 8 the auto-tuner may choose it, 16 powers of two only},
+ * and, when index is not null, out[4] = its current value and out[5] = 1 if it was set explicitly (else the default and 0). */
+int sg_debug_knob(const sg_index* index, uint32_t i, char name[32], int32_t out[6]);
 /* Test hook, off by default: with on = 1 or 2 every call of the process first fills the working memory and result rows it is meant to
  * write before it reads with a pattern (1: 0xA5 bytes, 2: 0x5A bytes; item queue, part counts, query lists and term ids take values a
  * kernel can read safely — capi.inc, "Test-only poison"), so that a read of a word the call did not write shows as a wrong row.
@@ -363,11 +367,14 @@ int sg_debug_pipe_layout(uint32_t n_q, uint32_t cand_cap, uint64_t out[12]);
  * forward-index records and terms, term table and counter block are resident on (-1: null).  All must equal out[0]. */
 int sg_debug_replica_devices(sg_index* index, uint32_t replica, int32_t out[8]);
 
-/* Sets a tuning knob of the index (names and ranges of the SG_* environment variables in DESIGN.md: SG_LOG2_CNT, SG_T_FLOOR,
- * SG_FILTER_LEVEL, SG_TIGHTEN, SG_ROOMY, SG_ORDER, SG_PRETOK, SG_SPLIT_CHUNKS, SG_PARTS_CNT_BONUS; the pipeline's SG_PIPE,
- * SG_PIPE_SUB, SG_PIPE_CAND_CAP, SG_PIPE_WIDE, SG_PLAN2, SG_PIPE_SHAPE_BIAS).  SG_PIPE_NW, SG_PIPE_LOG2_CNT and SG_PIPE_DT_BYTES
- * freeze the stream workgroup's shape for every launch; SG_PIPE_SHAPE_AUTO = 1 hands it back to the per-launch choice.
- * Results never depend on the knobs; for parameter sweeps. */
+/* Sets a tuning knob of the index, before or after its first upload: SG_LOG2_CNT, SG_T_FLOOR, SG_FILTER_LEVEL, SG_TIGHTEN, SG_ROOMY,
+ * SG_ORDER, SG_PRETOK, SG_SPLIT_CHUNKS, SG_PARTS_CNT_BONUS; the pipeline's SG_PIPE, SG_PIPE_SUB, SG_PIPE_CAND_CAP, SG_PIPE_WIDE,
+ * SG_PLAN2.  SG_PIPE_NW, SG_PIPE_LOG2_CNT and SG_PIPE_DT_BYTES freeze the stream workgroup's shape for every launch;
+ * SG_PIPE_SHAPE_AUTO = 1 hands it back to the per-launch choice, SG_PIPE_SHAPE_BIAS is a test hook (these two: this call only).
+ * The others are also read from the environment at the first upload, and SG_G8 only there.  Ranges, defaults and meanings: the
+ * table of DESIGN.md §4c.  An unknown name or a value outside its range is refused (invalid argument) on either route — from the
+ * environment, by the first upload.  A knob set explicitly is not chosen by the auto-tuner.  Results never depend on the knobs;
+ * for parameter sweeps; not synchronised with launches in flight. */
 int sg_index_tune(sg_index* index, const char* knob, int value);
 
 /* Tokens of `text` as the index sees them, one packed 64-bit term key each (DESIGN.md §Term keys);

@@ -145,6 +145,7 @@ struct Replica {
   ~Replica();
 };
 
+#include "knobs.inc"
 struct Coalescer;
 static void coalescer_stop(Coalescer* c);
 struct MultiPool;
@@ -160,33 +161,12 @@ struct sg_index {
   std::atomic<bool> uploaded{false};
   int device = -1;                                      // the primary replica's
   bool tuned = false;
-  uint32_t log2_cnt = 11;
-  int t_floor = 8;
-  uint32_t filter_level = 4;
-  int order_queries = 1;           // big batches run their queries heaviest first (query_order_kernel); SG_ORDER=0 keeps the caller's order
-  int g8 = 0;                      // 8-bit gaps for dense terms (packed_store.inc): 0 never (default: the store shrinks by a third on bigram indexes, but its chunks are 81 % full and the launches follow the posting SLOTS: cfg 4 -26 %), 1 where they save chunks, 2 every term (tests); SG_G8, before the first upload
-  int pre_tokenize = 2048;         // batches of at least this many queries are tokenised by a launch of their own (sg_terms_kernel); SG_PRETOK=0: never
-  int roomy = 2;                   // candidate queue: 0 small (12 wavefronts per CU), 1 large (11), 2 by the results per query of the recent launches
-  int tighten = 2;                 // threshold tightening: 0 never, 1 always, 2 by the share of queries whose top-k fills
-  uint32_t split_chunks = 65536;   // 1 MiB of postings per part at least; 0 = never split a query
+  Knobs knobs;                     // knobs.inc: environment at the first upload, sg_index_tune; below: what tune_index() derives
   double terms_per_doc = 0;
   double max_term_chunks = 0;      // chunks of the longest term (all segments)
-  uint32_t parts_cnt_bonus = 2;    // log2 of the counter-array growth of the parts launch for small batches
-  uint32_t parts_grid = 3072;      // wavefronts of the second launch (three per SIMD are resident)
   double est_query_chunks = 0;     // expected 16-byte chunks of postings a query's terms hold (size-biased mean list x terms per doc)
-  // [r5] the three-launch pipeline of ordinary fuzzy batches (pipeline.inc): plan -> stream -> verify, the fused kernel behind it
-  int pipe = 2;                    // 0 never, 1 whenever a launch is eligible, 2 (default) eligible launches of indexes whose queries stream
-                                   // enough postings for it to pay, unless the replica's recent queries mostly fell back (SG_PIPE)
-  bool pipe_pays = false;          // ... by tune_choice()
-  uint32_t pipe_nw = 8;            // wavefronts of a stream workgroup: 2, 4 or 8 (SG_PIPE_NW)
-  int pipe_shape_bias = 0;         // test hook (sg_index_tune SG_PIPE_SHAPE_BIAS -2 .. 0): the model's shape lowered by this much — a launch that starts too light
-  bool pipe_shape_fixed = false;   // SG_PIPE_NW / SG_PIPE_LOG2_CNT / SG_PIPE_DT_BYTES were given: every launch takes them (else: pipe_shape per launch)
-  uint32_t pipe_dt_bytes = 8192;   // LDS of a stream workgroup's sub-row descriptors (SG_PIPE_DT_BYTES): with the counters, the workgroups a CU holds
-  uint32_t pipe_sub = 4;           // log2 of the chunks a row descriptor covers: 3 .. 6 (SG_PIPE_SUB)
-  uint32_t pipe_log2_cnt = 13;     // u32 counters of a stream workgroup (SG_PIPE_LOG2_CNT)
-  uint32_t pipe_cand_cap = 64;     // candidate slots per query (SG_PIPE_CAND_CAP)
-  int plan2 = 1;                   // [r6] the plan launch with two queries per wavefront (plan2.inc) where the description allows it (SG_PLAN2; 0: sg_plan_kernel alone)
-  int pipe_wide = 0;               // 1: the stream launch's 8-byte sub-row descriptors whatever the store's size (SG_PIPE_WIDE; tests — stores of 2^26 chunks and more take them anyway)
+  uint32_t parts_grid = 3072;      // wavefronts of the second launch (three per SIMD are resident)
+  bool pipe_pays = false;          // [r5] plan -> stream -> verify pays for this index (tune_choice; SG_PIPE=2 asks)
   Coalescer* coalescer = nullptr;  // sg_suggest_one / sg_autocomplete_one (made on first use)
   MultiPool* multi = nullptr;      // sg_*_batch_multi: one worker thread per replica (made on first use)
 };
@@ -396,18 +376,18 @@ struct Carve {
 // above the one-counter-per-document size, a chunk index of 32 bits.  Stores of 2^26 chunks (1 GiB) and more take the stream
 // launch's 8-byte sub-row descriptors (pipe_wide); top-k rows above SG_K_LDS entries live in HBM as the fused kernel's.
 bool pipe_capable(const sg_index* index, const Replica* rep) {
-  return index->pipe != 0 && rep->dix.n_docs > (4u << index->log2_cnt) && rep->packed_chunks < (1ull << 32) && index->pipe_sub >= 3 && index->pipe_sub <= 5;
+  return index->knobs.pipe != 0 && rep->dix.n_docs > (4u << index->knobs.log2_cnt) && rep->packed_chunks < (1ull << 32);
 }
 // the tokeniser as a launch of its own (512 B of scratch per query: a batch of more than 2 M queries — 1 GiB of it — lets the
 // search kernel tokenise itself)
-bool pretok_launch(const sg_index* index, uint32_t n_q) { return index->pre_tokenize && n_q >= (uint32_t)index->pre_tokenize && n_q <= (1u << 21); }
+bool pretok_launch(const sg_index* index, uint32_t n_q) { return index->knobs.pretok && n_q >= (uint32_t)index->knobs.pretok && n_q <= (1u << 21); }
 // [r5] Whether a launch may go through plan -> stream -> verify (pipeline.inc: the plan launch tokenises; the fused kernel runs
 // behind them over the queries they hand back): an ordinary fuzzy batch — top-k by score, no LM collector, no 8-bit gaps, no
 // tightening — large enough for a tokeniser launch of its own, on a replica that can run the pipeline, always (SG_PIPE=1) or
 // where it pays (tune_choice; profiles/r05r_*) while the run-time guard does not hold it off.  launch() adds: no split queries.
 bool pipe_eligible(const sg_index* index, const Replica* rep, const LaunchReq& r, bool tight, bool guard_off) {
   return pipe_capable(index, rep) && !r.lm && !r.autocomplete && !r.by_doc && !rep->dix.has_g8 && !tight && pretok_launch(index, r.n_q) &&
-         (index->pipe == 1 || (index->pipe_pays && !guard_off));
+         (index->knobs.pipe == 1 || (index->pipe_pays && !guard_off));
 }
 // [r6] The stream workgroup a launch starts from (plan_launch): 0 / 1 / 2 = 2 / 4 / 8 wavefronts on 2^11 / 2^12 /
 // 2^13 counters, by the index's expected query volume x the square of the share of a typical query's lists that skipping leaves
@@ -424,12 +404,12 @@ uint32_t pipe_shape_model(double est_query_chunks, double terms_per_doc, int t_f
 // and computes the five metrics of pkg/metric itself: any other description or a tabulated metric keeps sg_plan_kernel
 bool plan2_usable(const sg_index* index, const Replica* rep, int metric) {
   const DeviceIndex& d = rep->dix;
-  if (!index->plan2 || metric == SG_TABLE || d.q > 3u || d.q == 0u || d.n_pad != 1u || !d.slots || d.n_wrap0 > SG_WRAP_MAX || d.n_wrap1 > SG_WRAP_MAX) return false;
+  if (!index->knobs.plan2 || metric == SG_TABLE || d.q > 3u || d.q == 0u || d.n_pad != 1u || !d.slots || d.n_wrap0 > SG_WRAP_MAX || d.n_wrap1 > SG_WRAP_MAX) return false;
   for (uint32_t i = 0; i < d.n_wrap0; i++) if (d.wrap0[i] >= 128u) return false;
   for (uint32_t i = 0; i < d.n_wrap1; i++) if (d.wrap1[i] >= 128u) return false;
   return true;
 }
-bool pipe_wide(const sg_index* index, const Replica* rep) { return index->pipe_wide || rep->packed_chunks >= (1ull << 26); }
+bool pipe_wide(const sg_index* index, const Replica* rep) { return index->knobs.pipe_wide || rep->packed_chunks >= (1ull << 26); }
 
 // What a launch does, decided before it allocates or enqueues anything.  One thing may change it afterwards: a pipeline launch
 // whose block of records the device cannot give takes the fused kernel with the tokeniser launch instead (launch()).
@@ -457,38 +437,39 @@ void split_caps(LaunchPlan& p, uint32_t n_q, uint32_t k) {
 LaunchPlan plan_launch(sg_index* index, Replica* rep, const LaunchReq& r) {
   const uint32_t n_q = r.n_q, k = r.k;
   const volatile uint32_t* h = rep->h_fill;
+  const Knobs& kn = index->knobs;
   LaunchPlan p;
   p.mode = r.by_doc ? 2 : r.autocomplete; p.metric = r.mt ? SG_TABLE : r.metric;
   p.long_list = rep->long_scratch && !r.no_long_queries;
   // heaviest queries first (query_order_kernel): a batch that fills the machine many times over, no order given by the caller
   // (flag: a launch over the queries a flag array marks — the order kernels make the list, heaviest first like any other)
-  p.reorder = r.flag || (!r.sel && index->order_queries && n_q >= (index->order_queries == 1 ? 8192u : (uint32_t)index->order_queries));
+  p.reorder = r.flag || (!r.sel && kn.order && n_q >= (kn.order == 1 ? 8192u : (uint32_t)kn.order));
   p.ord_blocks = (n_q + 1023u) / 1024u; p.ord_direct = p.ord_blocks <= SG_ORDER_DIRECT_BLOCKS;
   p.pretok = pretok_launch(index, n_q);
   p.g8 = rep->dix.has_g8 != 0u;             // dense terms with 8-bit gaps: the kG8 instantiations (full LDS layout)
   // [r6] Split queries, unless the launch will take the pipeline — judged on the controllers as they stand before this launch steps
   // them: a stream workgroup per query is the balance there.  (Round 5 had the two exclude each other the other way round, and an
   // index whose queries pass the splitting threshold — 25 M strings — dropped to the fused kernel without a word.)
-  const bool tight_before = index->tighten == 1 || (index->tighten == 2 && rep->tighten.now(h, r.similarity));
-  if (k <= SG_K_LDS && index->split_chunks && !r.lm && !r.by_doc && !pipe_eligible(index, rep, r, tight_before, rep->pipe_guard.holding())) {
+  const bool tight_before = kn.tighten == 1 || (kn.tighten == 2 && rep->tighten.now(h, r.similarity));
+  if (k <= SG_K_LDS && kn.split_chunks && !r.lm && !r.by_doc && !pipe_eligible(index, rep, r, tight_before, rep->pipe_guard.holding())) {
     // Splitting pays (1) when the batch cannot fill the machine by itself: every query above 2 MiB of postings is cut
     // into 1 MiB parts; (2) for the outliers of a big batch, which would otherwise be its tail: one wavefront streams
     // ~1/3000 of the machine's rate, so a query holding more than 2x the expected volume and more than ~1/30000 of the
     // batch's is cut into parts of a quarter of that.  A big batch of equally heavy queries is left alone.
     const double batch_chunks = (double)n_q * index->est_query_chunks;
-    double smin = 2.0 * index->split_chunks;
+    double smin = 2.0 * kn.split_chunks;
     if (n_q > 4096u) smin = std::max(smin, std::max(2.0 * index->est_query_chunks, batch_chunks / 30000.0));
     // (the figures above are in chunks of the u32 CSR — 4 postings; the kernel counts chunks of the packed store — SG_PPC)
     const double pk = 4.0 / SG_PPC;
     p.split_min = (uint32_t)std::min(smin * pk, 4.0e9);
-    p.split_chunks = std::max<uint32_t>((uint32_t)(index->split_chunks * pk), p.split_min / 4u);
+    p.split_chunks = std::max<uint32_t>((uint32_t)(kn.split_chunks * pk), p.split_min / 4u);
     // an index whose queries do not come near the threshold (4x the expected volume) pays nothing for the machinery
     if (4.0 * index->est_query_chunks * pk < (double)p.split_min) p.split_min = 0;
   }
   if (p.split_min) split_caps(p, n_q, k);
   if (!r.lm && p.mode == 0) {
-    p.tight = index->tighten == 1;
-    if (index->tighten == 2 && h) { p.tight = rep->tighten.step(h, r.similarity); p.sample = true; }
+    p.tight = kn.tighten == 1;
+    if (kn.tighten == 2 && h) { p.tight = rep->tighten.step(h, r.similarity); p.sample = true; }
   }
   // [r4] The large queue (11 wavefronts per CU instead of 12) only for the tightening instantiation (the full layout anyway)
   // and the docID-ordered mode (every candidate is a result).  Rounds 2-3 also gave it to launches whose recent queries had
@@ -496,12 +477,12 @@ LaunchPlan plan_launch(sg_index* index, Replica* rep, const LaunchReq& r) {
   // small / large: words Jaccard 58.9 / 56.7 M q/s, families 33.4 / 32.5, cfg 5 39.5 / 37.1 M predictions/s —
   // profiles/r04t_*, r04s_spell_sweep.txt): a queue that fills is emptied by the overflow walk, a wavefront that is missing is missing
   // all the time.
-  p.roomy = index->roomy == 2 ? (p.tight || r.by_doc) : index->roomy == 1;
+  p.roomy = kn.roomy == 2 ? (p.tight || r.by_doc) : kn.roomy == 1;
   // the slim table sizes where they buy a wavefront per CU (engine.hip, Lds<>); the tightening instantiation has the full ones
-  p.slim = !p.tight && !p.g8 && sg_lds_waves(index->log2_cnt, k, p.roomy, true) > sg_lds_waves(index->log2_cnt, k, p.roomy, false);
+  p.slim = !p.tight && !p.g8 && sg_lds_waves(kn.log2_cnt, k, p.roomy, true) > sg_lds_waves(kn.log2_cnt, k, p.roomy, false);
   // the pipeline on the controllers' state after this launch's step; the guard looks only at launches that could take it
   p.pipe = !p.split_min && pipe_eligible(index, rep, r, p.tight, false) &&
-           !(index->pipe == 2 && h && rep->pipe_guard.step(h, rep->pipe_queries.load(std::memory_order_relaxed)));
+           !(kn.pipe == 2 && h && rep->pipe_guard.step(h, rep->pipe_queries.load(std::memory_order_relaxed)));
   if (!p.pipe) return p;
   // [r6] The stream workgroup's shape, per launch.  Which of the three measured shapes is fastest follows what a query of THIS
   // launch streams, not the index alone: 10 M strings want four wavefronts on 2^12 counters at Jaccard >= 0.5 (1.324 against
@@ -510,10 +491,10 @@ LaunchPlan plan_launch(sg_index* index, Replica* rep, const LaunchReq& r) {
   // query's lists that list skipping leaves under this metric and similarity (the lists left are the short ones); the cuts, 3 200
   // and 12 000 chunks, put all sixteen measured launches — 1 M ... 16 M strings under both — on their fastest shape
   // (profiles/r06final_shape_by_size.txt, r06final_shape_auto_by_size.txt).  Where the model is wrong, ShapeFloor corrects it.
-  p.nw = index->pipe_nw; p.log2_cnt = index->pipe_log2_cnt; p.dt_bytes = index->pipe_dt_bytes;
-  if (!index->pipe_shape_fixed && p.metric >= SG_JACCARD && p.metric <= SG_OVERLAP) {
-    uint32_t shape = pipe_shape_model(index->est_query_chunks, index->terms_per_doc, index->t_floor, p.metric, r.similarity);
-    shape = (uint32_t)std::max(0, (int)shape + index->pipe_shape_bias);
+  p.nw = kn.pipe_nw; p.log2_cnt = kn.pipe_log2_cnt; p.dt_bytes = kn.pipe_dt_bytes;
+  if (kn.pipe_shape_auto && p.metric >= SG_JACCARD && p.metric <= SG_OVERLAP) {
+    uint32_t shape = pipe_shape_model(index->est_query_chunks, index->terms_per_doc, kn.t_floor, p.metric, r.similarity);
+    shape = (uint32_t)std::max(0, (int)shape + kn.pipe_shape_bias);
     shape = rep->shape_floor.step(h, rep->pipe_queries.load(std::memory_order_relaxed), shape);
     static const uint32_t kShape[3][3] = {{2u, 11u, 2048u}, {4u, 12u, 4096u}, {8u, 13u, 8192u}};
     p.nw = kShape[shape][0]; p.log2_cnt = kShape[shape][1]; p.dt_bytes = kShape[shape][2];
@@ -616,10 +597,10 @@ BatchArgs batch_args(const sg_index* index, const Replica* rep, const LaunchReq&
   a.q_blob = (const uint8_t*)r.q; a.q_offs = (const uint64_t*)r.offs;
   a.out_ids = (uint32_t*)r.ids; a.out_scores = (double*)r.scores; a.out_counts = (uint32_t*)r.counts;
   a.alpha = r.similarity; a.n_q = r.n_q; a.k = r.k; a.metric = p.metric; a.autocomplete = p.mode;
-  a.log2_cnt = index->log2_cnt; a.t_floor = index->t_floor; a.filter_level = index->filter_level;
+  a.log2_cnt = index->knobs.log2_cnt; a.t_floor = index->knobs.t_floor; a.filter_level = index->knobs.filter_level;
   a.prof = (unsigned long long*)g_prof_buf;
 #ifdef SG_PHASE_TIMING
-  { const char* e = getenv("SG_DEBUG_SKIP"); a.dbg_skip = e ? (uint32_t)atoi(e) : 0u; }
+  a.dbg_skip = (uint32_t)env_int("SG_DEBUG_SKIP", 0, INT32_MAX, 0);
 #endif
   a.split_min = p.split_min; a.split_chunks = p.split_chunks; a.slot_cap = p.slot_cap; a.item_cap = p.item_cap;
   if (p.sample) { a.fill_stat = rep->d_fill; a.fill_mask = r.n_q <= 1024u ? 0u : 31u; }
@@ -643,9 +624,9 @@ int enqueue_pipeline(const sg_index* index, const Replica* rep, const BatchArgs&
                      uint32_t* order_ctl, hipStream_t stream) {
   const uint32_t n_q = a.n_q, k = a.k;
   PipeArgs pa{};
-  pa.sub_log2 = index->pipe_sub;
+  pa.sub_log2 = index->knobs.pipe_sub;
   pa.stat = rep->d_fill; pa.stat_mask = n_q <= 1024u ? 0u : 255u;      // (one query in 256: a few hundred atomics on one line per launch)
-  pa.log2_cnt = p.log2_cnt; pa.cand_cap = index->pipe_cand_cap; pa.vrec_words = L.vrec_words;
+  pa.log2_cnt = p.log2_cnt; pa.cand_cap = index->knobs.pipe_cand_cap; pa.vrec_words = L.vrec_words;
   // a stream workgroup's LDS (pipeline.inc): counters | sub-row descriptors of the query's groups + a dead one
   const size_t cnt_bytes = 4 * std::max<size_t>((size_t)1 << pa.log2_cnt, SG_PIPE_REC_WORDS);
   const size_t lds = std::min<size_t>((cnt_bytes + p.dt_bytes + 1279) / 1280 * 1280, 65536);   // (whole allocation granules: 40 960 B = four workgroups per CU with the defaults; a workgroup's limit is 64 KB)
@@ -763,7 +744,7 @@ int launch(sg_index* index, Replica* rep, const LaunchReq& r) {
   if (a.long_list && !order_ctl) HIP_TRY(hipMemsetAsync(a.long_list, 0, 4, stream));
   // the pipeline's records; if the device cannot give them the launch takes the fused kernel with the tokeniser launch — less memory
   // — instead of failing (the one change to a plan after it is made)
-  const PipeLayout P = pipe_layout(n_q, index->pipe_cand_cap);
+  const PipeLayout P = pipe_layout(n_q, index->knobs.pipe_cand_cap);
   void* pipe_blk = nullptr;
   if (p.pipe && stream_scratch(rep->device, stream, P.bytes, &pipe_blk, SCRATCH_PIPE) != SG_OK) { p.pipe = false; (void)hipGetLastError(); }
   if (p.pipe && poison) if (int rc = poison_words((char*)pipe_blk + P.fb_list, (size_t)n_q + 1, 0u, PZ_PIPE, stream)) return rc;
@@ -790,7 +771,7 @@ int launch(sg_index* index, Replica* rep, const LaunchReq& r) {
   if (a.split_ctl) {     // the queued parts of split queries: persistent wavefronts, which leave at once if there are none
     // the parts of a small batch are long streams on a machine they cannot fill anyway: they get 4x the counters (fewer
     // docID-range passes; the launch has its own LDS size).  q=2: one query 0.57 -> 0.43 ms, 256 queries +30 %.
-    a.log2_cnt = std::min<uint32_t>(index->log2_cnt + (n_q <= 4096u ? index->parts_cnt_bonus : 0u), 14u);
+    a.log2_cnt = std::min<uint32_t>(index->knobs.log2_cnt + (n_q <= 4096u ? index->knobs.parts_cnt_bonus : 0), 14u);
     a.cq_cap = sg_queue_cap(a.log2_cnt, k, p.roomy, false);
     hipLaunchKernelGGL(parts_kernel(p.tight, p.g8), dim3(index->parts_grid), dim3(64), lds_bytes(a.log2_cnt, k, p.roomy), stream, a);
     HIP_TRY(hipGetLastError());
@@ -824,9 +805,27 @@ namespace {
 struct TuneChoice { uint32_t log2_cnt, filter_level; int pipe_pays; uint32_t pipe_nw, pipe_log2_cnt, pipe_dt_bytes; };
 TuneChoice tune_choice(double est_query_chunks, double max_term_chunks) {
   TuneChoice c{11u, 4u, 0, 8u, 13u, 8192u};
-  // counter array: 2^12 words only for long-list indexes whose longest terms are as heavy as a typical query's whole volume
+  // [r4] The counter array.  Long-list indexes (megabytes of postings per query) run mostly docID-range passes, and 2^12
+  // words halve the passes — but cost the wavefronts: 7 per CU instead of 12.  Swept on the final round-3 kernel
+  // (profiles/r04o_sweep_*, r04p_sweep_*): a uniform bigram index (q = 2, 10 M strings: every term about as long as any
+  // other) does best at 2^11 — 20.0 ms per 16 384 queries against 24.3 at 2^12 and 33.8 at 2^13; an index whose longest
+  // terms are as heavy as a typical query's whole volume (Zipf symbols: a few lists of millions of postings, met by a
+  // minority of the queries, which then set the launch's tail) does best at 2^12 ... 2^13 (28.4 / 27.0 ms against 34.8 at
+  // 2^11).  So: 2^12 where the longest term holds more than a quarter of the expected query volume, else 2^11.
+  // (Rounds 2-3 took 2^12 for every index above 2 MiB per query: cfg 4 paid 30 % for it.)
   if (est_query_chunks > 131072.0 && max_term_chunks > 0.25 * est_query_chunks) c.log2_cnt = 12;
-  // filter table: the strict one (level 2) only for small dictionaries of real words (uneven term lengths); else the loose one
+  // [r4] The filter level.  The loose per-posting table (level 4) is right for every index above a few thousand chunks
+  // per query — long-list ones included: since verification is one forward-index read (round 2) and the queue takes
+  // whatever comes (round 3), q = 2 on 10 M strings runs 20.0 ms at level 4 against 22.7 at level 2 (same counter array),
+  // the Zipf dictionary 28.4 against 39.2.  (The strict table was chosen for them in round 2, when a false candidate
+  // cost a binary search per query term: level 2 0.41 M q/s, level 4 0.39 then.)
+  // Small dictionaries of real words (the reference's cars / words: a few thousand chunks per query, and n-gram lists as
+  // uneven as a language's — the longest term holds a third to two thirds of a query's volume) merge their few postings
+  // into large groups either way; with the loose table they also skip deeper and flag every matching document — they
+  // have many per query — in more of its lists: words Jaccard k=10 56.8 M q/s at level 2, 31.8 at level 4
+  // (profiles/r04q_small_dictionaries_levels.txt).  A small dictionary of UNIFORM strings (1 M synthetic strings: the
+  // longest term a tenth of a query's volume, 0.9 results per query) is the headline in small and takes the loose table
+  // like it: cfg 2 0.585 ms per 65 536 queries at level 4, 0.648 at level 2 (profiles/r04q_sweep_cfg2.txt).
   const bool small_uneven = est_query_chunks < 8192.0 && max_term_chunks > 0.25 * est_query_chunks;
   if (small_uneven) c.filter_level = 2;
   // [r5] plan -> stream -> verify pays wherever its stream workgroup has the size of the queries' streams: for 10 M strings
@@ -844,87 +843,42 @@ TuneChoice tune_choice(double est_query_chunks, double max_term_chunks) {
   return c;
 }
 
-// Tuning knobs and the statistics they depend on: once per index, at its first upload (results never depend on them).
-void tune_index(sg_index* ix) {
-  if (ix->tuned) return;
-  ix->tuned = true;
+// The statistics the tuner and the launch plans go by: a query term is a dictionary term drawn by occurrence, so the expected list
+// length is size-biased — E[list length] = sum len^2 / sum len.
+void index_statistics(sg_index* ix) {
   const HostIndex& h = ix->host;
-  const char* env = getenv("SG_LOG2_CNT");   // LDS counter words per wavefront (default 2^11)
-  if (env) { int v = atoi(env); if (v >= 9 && v <= 14) ix->log2_cnt = (uint32_t)v; }
-  env = getenv("SG_T_FLOOR");                 // lowest flag threshold list skipping may leave (default 8)
-  if (env) { int v = atoi(env); if (v >= 2 && v <= 64) ix->t_floor = v; }
-  {  // a query term is a dictionary term drawn by occurrence: E[list length] = sum len^2 / sum len (size-biased)
-    const size_t S = h.n_segments, nt = h.term_key.size();
-    double s1 = 0, s2 = 0;
-    for (size_t t = 0; t < nt; t++) {
-      const double len = (double)(h.seg_off[t * (S + 1) + S] - h.seg_off[t * (S + 1)]);
-      s1 += len; s2 += len * len;
-      ix->max_term_chunks = std::max(ix->max_term_chunks, len);
-    }
-    const double terms_per_doc = h.n_docs ? (double)h.n_postings_raw / (double)h.n_docs : 0.0;
-    ix->est_query_chunks = s1 > 0 ? terms_per_doc * s2 / s1 : 0.0;
-    ix->terms_per_doc = terms_per_doc;
-    // [r4] The counter array.  Long-list indexes (megabytes of postings per query) run mostly docID-range passes, and 2^12
-    // words halve the passes — but cost the wavefronts: 7 per CU instead of 12.  Swept on the final round-3 kernel
-    // (profiles/r04o_sweep_*, r04p_sweep_*): a uniform bigram index (q = 2, 10 M strings: every term about as long as any
-    // other) does best at 2^11 — 20.0 ms per 16 384 queries against 24.3 at 2^12 and 33.8 at 2^13; an index whose longest
-    // terms are as heavy as a typical query's whole volume (Zipf symbols: a few lists of millions of postings, met by a
-    // minority of the queries, which then set the launch's tail) does best at 2^12 ... 2^13 (28.4 / 27.0 ms against 34.8 at
-    // 2^11).  So: 2^12 where the longest term holds more than a quarter of the expected query volume, else 2^11.
-    // (Rounds 2-3 took 2^12 for every index above 2 MiB per query: cfg 4 paid 30 % for it.)
-    const TuneChoice choice = tune_choice(ix->est_query_chunks, ix->max_term_chunks);
-    if (!getenv("SG_LOG2_CNT")) ix->log2_cnt = choice.log2_cnt;
-    // [r4] The filter level.  The loose per-posting table (level 4) is right for every index above a few thousand chunks
-    // per query — long-list ones included: since verification is one forward-index read (round 2) and the queue takes
-    // whatever comes (round 3), q = 2 on 10 M strings runs 20.0 ms at level 4 against 22.7 at level 2 (same counter array),
-    // the Zipf dictionary 28.4 against 39.2.  (The strict table was chosen for them in round 2, when a false candidate
-    // cost a binary search per query term: level 2 0.41 M q/s, level 4 0.39 then.)
-    // Small dictionaries of real words (the reference's cars / words: a few thousand chunks per query, and n-gram lists as
-    // uneven as a language's — the longest term holds a third to two thirds of a query's volume) merge their few postings
-    // into large groups either way; with the loose table they also skip deeper and flag every matching document — they
-    // have many per query — in more of its lists: words Jaccard k=10 56.8 M q/s at level 2, 31.8 at level 4
-    // (profiles/r04q_small_dictionaries_levels.txt).  A small dictionary of UNIFORM strings (1 M synthetic strings: the
-    // longest term a tenth of a query's volume, 0.9 results per query) is the headline in small and takes the loose table
-    // like it: cfg 2 0.585 ms per 65 536 queries at level 4, 0.648 at level 2 (profiles/r04q_sweep_cfg2.txt).
-    if (!getenv("SG_FILTER_LEVEL")) ix->filter_level = choice.filter_level;
-    ix->pipe_pays = choice.pipe_pays != 0;
-    if (!getenv("SG_PIPE_NW")) ix->pipe_nw = choice.pipe_nw;
-    if (!getenv("SG_PIPE_LOG2_CNT")) ix->pipe_log2_cnt = choice.pipe_log2_cnt;
-    if (!getenv("SG_PIPE_DT_BYTES")) ix->pipe_dt_bytes = choice.pipe_dt_bytes;
-    if (getenv("SG_VERBOSE")) fprintf(stderr, "[suggest_hip] terms/doc %.2f, expected query volume %.0f chunks, longest term %.0f chunks\n", terms_per_doc, ix->est_query_chunks, ix->max_term_chunks);
+  const size_t S = h.n_segments, nt = h.term_key.size();
+  double s1 = 0, s2 = 0;
+  for (size_t t = 0; t < nt; t++) {
+    const double len = (double)(h.seg_off[t * (S + 1) + S] - h.seg_off[t * (S + 1)]);
+    s1 += len; s2 += len * len;
+    ix->max_term_chunks = std::max(ix->max_term_chunks, len);
   }
-  env = getenv("SG_SPLIT_CHUNKS");            // fewest 16-byte chunks per part of a split query (default 65536; 0 = off)
-  if (env && *env) ix->split_chunks = (uint32_t)std::max(0, atoi(env));
-  env = getenv("SG_FILTER_LEVEL");            // row of kBucketsPer16Postings: 0..3 strict, 4..7 loose
-  if (env) { int v = atoi(env); if (v >= 0 && v <= 7) ix->filter_level = (uint32_t)v; }
-  env = getenv("SG_TIGHTEN");                 // threshold tightening: 0 never, 1 always, 2 (default) by what the recent queries did
-  if (env) { int v = atoi(env); if (v >= 0 && v <= 2) ix->tighten = v; }
-  env = getenv("SG_ORDER");                   // 1 (default): batches of >= 8192 queries run heaviest (longest; autocomplete: shortest) first
-  if (env) ix->order_queries = std::max(0, atoi(env));
-  env = getenv("SG_G8");                      // 8-bit gaps for dense terms: 0 never (default), 1 where they save chunks, 2 every term
-  if (env) ix->g8 = std::max(0, std::min(atoi(env), 2));
-  env = getenv("SG_PRETOK");                  // batches of >= this many queries: tokeniser as its own launch (default 2048; 0 = never)
-  if (env) ix->pre_tokenize = std::max(0, atoi(env));
-  env = getenv("SG_ROOMY");                   // candidate queue size (and with it 11 or 12 wavefronts per CU): 0 small, 1 large, 2 (default) by the recent results per query
-  if (env) { int v = atoi(env); if (v >= 0 && v <= 2) ix->roomy = v; }
-  env = getenv("SG_PIPE");                    // [r5] plan -> stream -> verify for ordinary fuzzy batches: 0 never, 1 when eligible, 2 (default) where it pays
-  if (env) ix->pipe = std::max(0, std::min(atoi(env), 2));
-  env = getenv("SG_PIPE_NW");
-  if (env) { int v = atoi(env); if (v == 2 || v == 4 || v == 8) { ix->pipe_nw = (uint32_t)v; ix->pipe_shape_fixed = true; } }
-  env = getenv("SG_PIPE_DT_BYTES");
-  if (env) { int v = atoi(env); if (v >= 1024 && v <= 32768) { ix->pipe_dt_bytes = (uint32_t)v; ix->pipe_shape_fixed = true; } }
-  env = getenv("SG_PIPE_SUB");
-  if (env) { int v = atoi(env); if (v >= 3 && v <= 5) ix->pipe_sub = (uint32_t)v; }
-  env = getenv("SG_PIPE_LOG2_CNT");
-  if (env) { int v = atoi(env); if (v >= 9 && v <= 13) { ix->pipe_log2_cnt = (uint32_t)v; ix->pipe_shape_fixed = true; } }
-  env = getenv("SG_PIPE_CAND_CAP");
-  if (env) { int v = atoi(env); if (v >= 1 && v <= 4096) ix->pipe_cand_cap = (uint32_t)v; }
-  env = getenv("SG_PIPE_WIDE");
-  if (env) ix->pipe_wide = atoi(env) != 0;
-  env = getenv("SG_PLAN2");
-  if (env) ix->plan2 = atoi(env) != 0;
-  env = getenv("SG_PARTS_CNT_BONUS");         // log2 of how much larger the parts launch's counter array is
-  if (env) { int v = atoi(env); if (v >= 0 && v <= 3) ix->parts_cnt_bonus = (uint32_t)v; }
+  ix->terms_per_doc = h.n_docs ? (double)h.n_postings_raw / (double)h.n_docs : 0.0;
+  ix->est_query_chunks = s1 > 0 ? ix->terms_per_doc * s2 / s1 : 0.0;
+}
+
+// Once per index, at its first upload (caller holds ix->mu): the statistics, the environment's knobs, then the tuner's choice for
+// every knob it may choose that nobody set explicitly.  A value the table refuses fails the upload and leaves the index untuned.
+int tune_index(sg_index* ix) {
+  if (ix->tuned) return SG_OK;
+  index_statistics(ix);
+  Knobs k = ix->knobs;                       // (a copy: nothing half-set reaches the index when a value is refused)
+  for (const KnobRow& row : kKnobs) {
+    int32_t v = 0;
+    const char* e = getenv(row.name);
+    if (!e || !*e) continue;                 // (an empty variable counts as not set)
+    if ((row.flags & KNOB_ENV) && !parse_int32(e, &v)) return knob_refused(row, std::string("=") + e + ": not an integer");
+    if (const int rc = set_knob(k, row, v, KNOB_ENV)) return rc;
+  }
+  const TuneChoice c = tune_choice(ix->est_query_chunks, ix->max_term_chunks);
+  Knobs t = k;   // (the choice as knobs: taken where the row lets the tuner choose and nobody chose before it)
+  t.log2_cnt = c.log2_cnt; t.filter_level = c.filter_level; t.pipe_nw = c.pipe_nw; t.pipe_log2_cnt = c.pipe_log2_cnt; t.pipe_dt_bytes = c.pipe_dt_bytes;
+  for (uint32_t i = 0; i < kNumKnobs; i++)
+    if ((kKnobs[i].flags & KNOB_TUNER) && !((k.explicit_set >> i) & 1u)) k.*kKnobs[i].field = t.*kKnobs[i].field;
+  ix->knobs = k; ix->pipe_pays = c.pipe_pays != 0; ix->tuned = true;
+  if (env_int("SG_VERBOSE", 0, 1, 0)) fprintf(stderr, "[suggest_hip] terms/doc %.2f, expected query volume %.0f chunks, longest term %.0f chunks\n", ix->terms_per_doc, ix->est_query_chunks, ix->max_term_chunks);
+  return SG_OK;
 }
 
 // Fills a replica on `device` (caller holds ix->mu).  `r` may already own the u32 posting store and seg_off (device build).
@@ -940,7 +894,7 @@ int fill_replica(sg_index* ix, Replica* r, int device) {
   if (!d.postings && (rc = to_device(r, h.postings.data(), h.postings.size(), &d.postings))) return rc;
   if (!d.seg_off && (rc = to_device(r, h.seg_off.data(), h.seg_off.size(), &d.seg_off))) return rc;
   if ((rc = build_forward_index(h, r))) return rc;
-  if ((rc = pack_store(h, r, ix->g8))) return rc;
+  if ((rc = pack_store(h, r, ix->knobs.g8))) return rc;
   {  // long-query working memory: sized by the largest cardinality segment (one counter per document of a segment)
     std::vector<uint32_t> sb((size_t)h.n_segments + 1, 0);
     HIP_TRY(hipMemcpy(sb.data(), d.seg_base, sb.size() * 4, hipMemcpyDeviceToHost));
@@ -948,7 +902,7 @@ int fill_replica(sg_index* ix, Replica* r, int device) {
     for (size_t b = 0; b + 1 < sb.size(); b++) max_seg = std::max(max_seg, sb[b + 1] - sb[b]);
     r->long_max_seg = max_seg;
     r->long_slot_bytes = LongSlot::bytes(max_seg);
-    if (!getenv("SG_NO_LONG_QUERIES")) {
+    if (!env_int("SG_NO_LONG_QUERIES", 0, 1, 0)) {
       if ((rc = dev_alloc(r, (size_t)(r->long_slot_bytes * SG_LONG_SLOTS), &r->long_scratch))) return rc;
       if ((rc = dev_alloc(r, (size_t)SG_LONG_SLOTS + 4, &r->long_lock))) return rc;
       HIP_TRY(hipMemset(r->long_lock, 0, (SG_LONG_SLOTS + 4) * 4));
@@ -1021,7 +975,7 @@ int add_replica(sg_index* ix, int device) {
   int prev = -1;
   (void)hipGetDevice(&prev);
   std::lock_guard<std::mutex> lock(ix->mu);
-  tune_index(ix);
+  if (const int rc = tune_index(ix)) return rc;   // (a knob the environment sets out of range: before anything is allocated)
   std::unique_ptr<Replica> r;
   if (ix->prebuilt && ix->prebuilt->device == device) r = std::move(ix->prebuilt);
   else r.reset(new Replica());
@@ -1175,32 +1129,14 @@ int sg_debug_replica_devices(sg_index* ix, uint32_t replica, int32_t out[8]) {
   SG_GUARD_END(SG_RC)
 }
 
-// Tuning knobs of an uploaded index (same names as the SG_* environment variables read at the first upload).  Results never
-// depend on them; not synchronised with launches in flight (a tool for sweeps, tools/sweep_knobs.py).
+// Sets a knob of the table (knobs.inc), before or after the first upload.  Results never depend on the knobs; not synchronised with
+// launches in flight (a tool for sweeps, tools/sweep_knobs.py).
 int sg_index_tune(sg_index* ix, const char* knob, int value) {
+  SG_GUARD_BEGIN
   if (!ix || !knob) { set_error("null argument"); return SG_E_INVALID; }
-  const std::string k(knob);
-  if (k == "SG_LOG2_CNT" && value >= 9 && value <= 14) ix->log2_cnt = (uint32_t)value;
-  else if (k == "SG_T_FLOOR" && value >= 2 && value <= 64) ix->t_floor = value;
-  else if (k == "SG_FILTER_LEVEL" && value >= 0 && value <= 7) ix->filter_level = (uint32_t)value;
-  else if (k == "SG_TIGHTEN" && value >= 0 && value <= 2) ix->tighten = value;
-  else if (k == "SG_ROOMY" && value >= 0 && value <= 2) ix->roomy = value;
-  else if (k == "SG_ORDER" && value >= 0) ix->order_queries = value;        // 0 off, 1 batches of >= 8192, n >= 2: batches of >= n (tests)
-  else if (k == "SG_PRETOK" && value >= 0) ix->pre_tokenize = value;        // 0 never, n: batches of >= n queries
-  else if (k == "SG_SPLIT_CHUNKS" && value >= 0) ix->split_chunks = (uint32_t)value;
-  else if (k == "SG_PARTS_CNT_BONUS" && value >= 0 && value <= 3) ix->parts_cnt_bonus = (uint32_t)value;
-  else if (k == "SG_PIPE" && value >= 0 && value <= 2) ix->pipe = value;
-  else if (k == "SG_PIPE_NW" && (value == 2 || value == 4 || value == 8)) { ix->pipe_nw = (uint32_t)value; ix->pipe_shape_fixed = true; }
-  else if (k == "SG_PIPE_DT_BYTES" && value >= 1024 && value <= 32768) { ix->pipe_dt_bytes = (uint32_t)value; ix->pipe_shape_fixed = true; }
-  else if (k == "SG_PIPE_SHAPE_AUTO" && value == 1) ix->pipe_shape_fixed = false;     // (back to a shape per launch)
-  else if (k == "SG_PIPE_SHAPE_BIAS" && value >= -2 && value <= 0) ix->pipe_shape_bias = value;
-  else if (k == "SG_PIPE_SUB" && value >= 3 && value <= 5) ix->pipe_sub = (uint32_t)value;
-  else if (k == "SG_PIPE_LOG2_CNT" && value >= 9 && value <= 13) { ix->pipe_log2_cnt = (uint32_t)value; ix->pipe_shape_fixed = true; }
-  else if (k == "SG_PIPE_CAND_CAP" && value >= 1 && value <= 4096) ix->pipe_cand_cap = (uint32_t)value;
-  else if (k == "SG_PIPE_WIDE" && value >= 0 && value <= 1) ix->pipe_wide = value;
-  else if (k == "SG_PLAN2" && value >= 0 && value <= 1) ix->plan2 = value;
-  else { set_error("unknown knob or value out of range: " + k); return SG_E_INVALID; }
-  return SG_OK;
+  for (const KnobRow& row : kKnobs) if (!strcmp(row.name, knob)) return set_knob(ix->knobs, row, value, KNOB_TUNE);
+  set_error(std::string("unknown knob: ") + knob); return SG_E_INVALID;
+  SG_GUARD_END(SG_RC)
 }
 
 // The forward index of the primary replica, copied back for `n` documents starting at `first` (tests): out_card[i] = the
@@ -1283,8 +1219,7 @@ struct HostPool {
   uint64_t generation = 0;
   bool stop = false;
   HostPool() {
-    uint32_t n_thr = std::min(std::max(std::thread::hardware_concurrency(), 2u), 16u);
-    if (const char* e = getenv("SG_HOST_THREADS")) n_thr = (uint32_t)std::max(1, std::min(atoi(e), 64));
+    const uint32_t n_thr = (uint32_t)env_int("SG_HOST_THREADS", 1, 64, (int32_t)std::min(std::max(std::thread::hardware_concurrency(), 2u), 16u));
     for (uint32_t t = 1; t < n_thr; t++) workers.emplace_back([this] { loop(); });
   }
   ~HostPool() {
@@ -2126,7 +2061,7 @@ static void coalescer_lane(Coalescer* c, Replica* rep) {
     }
     // the sleeping callers are woken one by one; SG_COALESCE_TREE=1 lets them wake each other up as a binary tree instead
     // (one futex wake on the dispatcher per batch: better with spare cores, worse on a CPU quota)
-    static const bool tree = [] { const char* e = getenv("SG_COALESCE_TREE"); return e && atoi(e) != 0; }();
+    static const bool tree = env_int("SG_COALESCE_TREE", 0, 1, 0) != 0;
     for (size_t i = 0; i < sleepers.size(); i++) {
       sleepers[i]->child[0] = tree && 2 * i + 1 < sleepers.size() ? sleepers[2 * i + 1] : nullptr;
       sleepers[i]->child[1] = tree && 2 * i + 2 < sleepers.size() ? sleepers[2 * i + 2] : nullptr;
@@ -2143,8 +2078,7 @@ static Coalescer* coalescer_of(sg_index* ix) {
   if (!ix->coalescer) {
     auto* c = new Coalescer();
     c->index = ix;
-    uint32_t lanes = 1;                                      // (one dispatcher per replica: larger batches beat overlap — 256 callers: 590 k q/s with 1, 215 k with 4)
-    if (const char* e = getenv("SG_COALESCE_LANES")) { int v = atoi(e); if (v >= 1 && v <= 16) lanes = (uint32_t)v; }
+    const uint32_t lanes = (uint32_t)env_int("SG_COALESCE_LANES", 1, 16, 1);   // (one dispatcher per replica: larger batches beat overlap — 256 callers: 590 k q/s with 1, 215 k with 4)
     for (auto& r : ix->replicas) for (uint32_t l = 0; l < lanes; l++) c->lanes.emplace_back(coalescer_lane, c, r.get());
     ix->coalescer = c;
   }
@@ -2167,7 +2101,7 @@ static int submit_one(sg_index* index, OneReq& r) {
   // Callers sleep at once by default.  Spinning first (SG_COALESCE_SPIN_US) saves the futex round trip when every caller has
   // a core of its own — and is ruinous when they do not: 256 callers on the GPU box's 16-CPU quota reach 670 k q/s
   // sleeping, 137 k spinning 100 us, 59 k spinning 300 us (tests/cpp/single_query_load).
-  static const uint32_t spin_ns = [] { const char* e = getenv("SG_COALESCE_SPIN_US"); const int v = e ? atoi(e) : 0; return (uint32_t)std::max(0, std::min(v, 100000)) * 1000u; }();
+  static const uint32_t spin_ns = (uint32_t)env_int("SG_COALESCE_SPIN_US", 0, 100000, 0) * 1000u;
   const auto t_spin = std::chrono::steady_clock::now();
   for (uint32_t spin = 0; r.state.load(std::memory_order_acquire) != 1; spin++) {
     __builtin_ia32_pause();
@@ -2340,7 +2274,7 @@ int sg_spell_index_build(const sg_lm* lm, const sg_desc* desc, int device, sg_in
   // A vocabulary is short documents (3 .. 12 n-grams) searched at low thresholds (T = 3 .. 5): with the strict bucket table
   // the fuzzy top-up ran 6.7 groups per query, each a chain of dependent round trips; the looser table halves them
   // (BASELINE config 5: 1.88 -> 1.70 ms per Predict step, profiles/r04c_spell_sweep.txt).  SG_FILTER_LEVEL still overrides.
-  if (!getenv("SG_FILTER_LEVEL")) (*out)->filter_level = 4;
+  if (!knob_is_explicit((*out)->knobs, &Knobs::filter_level)) (*out)->knobs.filter_level = 4;
   return rc;
 }
 
@@ -2764,7 +2698,7 @@ int sg_index_pipe_volumes(sg_index* index, uint64_t out[8]) {
   HIP_TRY(hipMemcpy(w, rep->d_fill, sizeof w, hipMemcpyDeviceToHost));
   for (int i = 0; i < 5; i++) out[i] = w[SG_STAT_PLANNED + i];
   out[5] = rep->packed_chunks; out[6] = pipe_wide(index, rep) ? 1u : 0u;
-  out[7] = index->pipe_shape_fixed ? 3u : rep->shape_floor.last.load(std::memory_order_relaxed);   // the stream workgroup of the latest launch: 0 / 1 / 2 = 2 / 4 / 8 wavefronts, 3 = the knobs' own
+  out[7] = !index->knobs.pipe_shape_auto ? 3u : rep->shape_floor.last.load(std::memory_order_relaxed);   // the stream workgroup of the latest launch: 0 / 1 / 2 = 2 / 4 / 8 wavefronts, 3 = the knobs' own
   return SG_OK;
   SG_GUARD_END(SG_RC)
 }
@@ -2827,13 +2761,21 @@ int sg_debug_tune_index(sg_index* ix, double out_stats[2], int32_t out[6]) {
   if (!ix || !out_stats || !out) { set_error("null argument"); return SG_E_INVALID; }
   {
     std::lock_guard<std::mutex> lock(ix->mu);
-    tune_index(ix);
+    if (const int rc = tune_index(ix)) return rc;
   }
   out_stats[0] = ix->est_query_chunks; out_stats[1] = ix->max_term_chunks;
-  out[0] = (int32_t)ix->log2_cnt; out[1] = (int32_t)ix->filter_level; out[2] = ix->pipe_pays ? 1 : 0;
-  out[3] = (int32_t)ix->pipe_nw; out[4] = (int32_t)ix->pipe_log2_cnt; out[5] = (int32_t)ix->pipe_dt_bytes;
+  out[0] = ix->knobs.log2_cnt; out[1] = ix->knobs.filter_level; out[2] = ix->pipe_pays ? 1 : 0;
+  out[3] = ix->knobs.pipe_nw; out[4] = ix->knobs.pipe_log2_cnt; out[5] = ix->knobs.pipe_dt_bytes;
   return SG_OK;
   SG_GUARD_END(SG_RC)
+}
+int sg_debug_knob(const sg_index* ix, uint32_t i, char name[32], int32_t out[6]) {   // (nothing in it throws)
+  if (!name || !out || i >= kNumKnobs) { set_error("null argument / no such row of the knob table"); return SG_E_INVALID; }
+  const KnobRow& row = kKnobs[i];
+  snprintf(name, 32, "%s", row.name);
+  out[0] = row.lo; out[1] = row.hi; out[2] = row.def; out[3] = (int32_t)row.flags;
+  out[4] = ix ? ix->knobs.*row.field : row.def; out[5] = ix ? (int32_t)((ix->knobs.explicit_set >> i) & 1u) : 0;
+  return SG_OK;
 }
 
 int sg_index_stats(const sg_index* ix, sg_stats* out) {

@@ -1818,12 +1818,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kG8 ? 2 : 3,
 #pragma unroll
         for (int r = 0; r < 2; r++) {
           const bool skipped = (skip_m[r] >> lane) & 1ull;
-#ifdef SG_EXP_DROP_TAILS   // (timing experiment only — wrong results: a list's last row is dropped when it is less than half full: what a layout
-                          //  without lanes behind the ends of the lists could gain at best, profiles/r04y_drop_tails.txt)
-          nr[r] = (r < a_rounds && !skipped) ? (ln_r[r] + 31u) >> 6 : 0u;
-#else
           nr[r] = (r < a_rounds && !skipped) ? (ln_r[r] + 63u) >> 6 : 0u;
-#endif
           const uint32_t incl = wave_scan_incl(nr[r], lane);
           pr[r] = n_rows + incl - nr[r];
           n_rows += readlane(incl, 63);

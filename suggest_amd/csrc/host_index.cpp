@@ -325,8 +325,7 @@ int build_host_index(const uint8_t* utf8, const uint64_t* offs, uint32_t n_docs,
   // Contiguous blocks of docs, one thread each (SG_BUILD_THREADS, default: the cores this process may run on, at most
   // 32).  Every step below is arranged so that the result is the one the sequential build gives: term ids in
   // first-occurrence order over ascending docIDs, lists ascending.
-  uint32_t n_thr = std::min<uint32_t>(32, std::max<uint32_t>(1, std::thread::hardware_concurrency()));
-  if (const char* e = getenv("SG_BUILD_THREADS")) n_thr = (uint32_t)std::max(1, atoi(e));
+  uint32_t n_thr = (uint32_t)env_int("SG_BUILD_THREADS", 1, 65536, (int32_t)std::min<uint32_t>(32, std::max<uint32_t>(1, std::thread::hardware_concurrency())));
   n_thr = std::max<uint32_t>(1, std::min<uint32_t>(n_thr, n_docs / 4096 + 1));
   std::vector<BuildBlock> blk(n_thr);
   for (uint32_t b = 0; b < n_thr; b++) {
@@ -404,7 +403,7 @@ int build_host_index(const uint8_t* utf8, const uint64_t* offs, uint32_t n_docs,
   const size_t nT = ix.term_key.size();
   const size_t nTS = nT * (size_t)S;
   // the per-block counters below take nTS words per block: past 2 GiB in total, one shared set and a sequential scatter
-  const bool shared = n_thr > 1 && (nTS * n_thr > (1ull << 29) || getenv("SG_BUILD_SHARED_COUNTERS"));
+  const bool shared = n_thr > 1 && (nTS * n_thr > (1ull << 29) || env_int("SG_BUILD_SHARED_COUNTERS", 0, 1, 0));
 
   // pass 2: count per (term, segment) and block, lay the lists out term-major, each padded to 4 postings
   run_blocks(n_thr, [&](uint32_t b) {

@@ -417,7 +417,7 @@ int build_on_device(sg_index* ix, const uint8_t* utf8, const uint64_t* offs, uin
   HIP_TRY(hipDeviceSynchronize());
   keep->dix.postings = d_postings;
   keep->dix.seg_off = d_seg_off;
-  if (!getenv("SG_BUILD_NO_KEEP")) ix->prebuilt = std::move(keep);   // (knob for A/B timing of the placement)
+  ix->prebuilt = std::move(keep);
   return SG_OK;
 }
 

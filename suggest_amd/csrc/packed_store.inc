@@ -306,7 +306,7 @@ int pack_store(const HostIndex& h, Replica* r, int g8_mode) {
       // an index that gains less than 3 % keeps one format — and the kernels that know of one format only
       if (g8_mode == 1 && (double)tot[1] > 0.97 * (double)tot[0]) { term_fmt = nullptr; counts = c16; }
       else if (tot[1] >= 0x7FFFFFFFull) { set_error("the packed posting store addresses chunks below 2^31"); return SG_E_UNSUPPORTED; }
-      if (getenv("SG_VERBOSE")) fprintf(stderr, "[suggest_hip] packed store: %llu chunks with 16-bit gaps, %llu with 8-bit gaps for the dense terms%s\n", tot[0], tot[1],
+      if (env_int("SG_VERBOSE", 0, 1, 0)) fprintf(stderr, "[suggest_hip] packed store: %llu chunks with 16-bit gaps, %llu with 8-bit gaps for the dense terms%s\n", tot[0], tot[1],
                                         term_fmt ? "" : " (not taken)");
     }
     size_t tb = 0;

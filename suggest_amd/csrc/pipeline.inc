@@ -53,12 +53,8 @@
 //   words 132..1023 the groups' streamed lists {first chunk, chunks}, group after group: the first 446
 // The rare query with more lists takes an OVERFLOW BLOCK (a cursor over a pool of n / 8 blocks; pool empty: the fused kernel
 // answers): lists 446..957.
-#ifndef SG_PIPE_REC_WORDS
 #define SG_PIPE_REC_WORDS 1024u
-#endif
-#ifndef SG_PIPE_REC_FIRST
 #define SG_PIPE_REC_FIRST 384u       // words of a record every stream workgroup stages at once
-#endif
 #define SG_PIPE_REC_STRIDE SG_PIPE_REC_WORDS
 #define SG_PIPE_REC_HDR 132u
 #define SG_PIPE_REC_LISTS ((SG_PIPE_REC_WORDS - SG_PIPE_REC_HDR) / 2u)

@@ -3,7 +3,10 @@
 #pragma once
 
 #include <atomic>
+#include <cerrno>
 #include <cstdint>
+#include <cstdio>
+#include <cstdlib>
 #include <string>
 #include <unordered_map>
 #include <vector>
@@ -128,5 +131,25 @@ uint32_t lm_next_count(const HostLM& lm, const LmNext& nx, uint32_t word);
 double lm_next_score(const HostLM& lm, const LmNext& nx, uint32_t word);
 void lm_tokenize(const HostLM& lm, const uint8_t* text, size_t n, std::vector<std::string>& out);
 void set_error(const std::string& msg);
+
+// Values from outside the program (environment, sg_index_tune): a whole string, base 10, that fits an int32 — or nothing.
+inline bool parse_int32(const char* s, int32_t* out) {
+  char* end = nullptr;
+  errno = 0;
+  const long v = strtol(s, &end, 10);
+  if (end == s || *end || errno || v < INT32_MIN || v > INT32_MAX) return false;
+  *out = (int32_t)v;
+  return true;
+}
+// A process-wide switch from the environment.  Unset or empty: def; not an integer of lo .. hi: a line on stderr and def (there is
+// no call to fail).  The index's own knobs are the table of knobs.inc.
+inline int32_t env_int(const char* name, int32_t lo, int32_t hi, int32_t def) {
+  const char* e = getenv(name);
+  if (!e || !*e) return def;
+  int32_t v;
+  if (parse_int32(e, &v) && v >= lo && v <= hi) return v;
+  fprintf(stderr, "[suggest_hip] %s=%s: not an integer of %d .. %d, taking %d\n", name, e, lo, hi, def);
+  return def;
+}
 
 }  // namespace sg

@@ -111,6 +111,19 @@ def pinned_array(shape, dtype):
     return np.frombuffer(buf, dtype=dtype, count=count).reshape(shape)
 
 
+def knobs(index=None):
+    """The knob table (sg_debug_knob), a dict per row: name, lo, hi, default, where it may come from (env, tune),
+    pins_shape, tuner, pow2 and, of `index` (an NGramIndex) if given, its value there and whether it was set explicitly."""
+    L, rows = _lib.lib(), []
+    with (index._use() if index is not None else contextlib.nullcontext()) as h:
+        name, out = C.create_string_buffer(32), (C.c_int32 * 6)()
+        while L.sg_debug_knob(h, len(rows), name, out) == 0:
+            lo, hi, default, flags, value, explicit = (int(x) for x in out)
+            rows.append(dict(name=name.value.decode(), lo=lo, hi=hi, default=default, env=bool(flags & 1), tune=bool(flags & 2),
+                             pins_shape=bool(flags & 4), tuner=bool(flags & 8), pow2=bool(flags & 16), value=value, explicit=bool(explicit)))
+    return rows
+
+
 class NGramIndex:
     def __init__(self, docs=None, description=None, blob=None, offs=None, device=0, upload=True, _handle=None, build="host", min_segments=0):
         """build="host": sg_index_build (CPU tokenise + CSR); build="device": sg_index_build_device (same arrays, built on the

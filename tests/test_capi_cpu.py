@@ -322,3 +322,198 @@ def test_scratch_pipe_layout_is_disjoint_and_sized():
                    "ovf": (ovf, ovf_cap * ovf_words * 4, 16), "cand_n": (cand_n, piece * 4, 16), "fb_list": (fb_list, (n_q + 1) * 4, 16)}
             assert total % 16 == 0, ctx
             _assert_carved(reg, total)
+
+
+# ---- the knob table (csrc/knobs.inc) ----
+
+INT32_MAX = 2**31 - 1
+# name: (lowest, highest, default, routes).  Pinned here so that a changed range or default is a decision, not an accident.
+KNOB_TABLE = {
+    "SG_LOG2_CNT": (9, 14, 11, "ET"), "SG_T_FLOOR": (2, 64, 8, "ET"), "SG_FILTER_LEVEL": (0, 7, 4, "ET"), "SG_TIGHTEN": (0, 2, 2, "ET"),
+    "SG_ROOMY": (0, 2, 2, "ET"), "SG_ORDER": (0, INT32_MAX, 1, "ET"), "SG_PRETOK": (0, INT32_MAX, 2048, "ET"),
+    "SG_SPLIT_CHUNKS": (0, INT32_MAX, 65536, "ET"), "SG_PARTS_CNT_BONUS": (0, 3, 2, "ET"), "SG_G8": (0, 2, 0, "E"), "SG_PIPE": (0, 2, 2, "ET"),
+    "SG_PIPE_NW": (2, 8, 8, "ET"), "SG_PIPE_LOG2_CNT": (9, 13, 13, "ET"), "SG_PIPE_DT_BYTES": (1024, 32768, 8192, "ET"),
+    "SG_PIPE_SHAPE_AUTO": (1, 1, 1, "T"), "SG_PIPE_SHAPE_BIAS": (-2, 0, 0, "T"), "SG_PIPE_SUB": (3, 5, 4, "ET"),
+    "SG_PIPE_CAND_CAP": (1, 4096, 64, "ET"), "SG_PIPE_WIDE": (0, 1, 0, "ET"), "SG_PLAN2": (0, 1, 1, "ET"),
+}
+SHAPE_KNOBS = ("SG_PIPE_NW", "SG_PIPE_LOG2_CNT", "SG_PIPE_DT_BYTES")
+TUNER_KNOBS = ("SG_LOG2_CNT", "SG_FILTER_LEVEL") + SHAPE_KNOBS
+PROCESS_SWITCHES = {"SG_HOST_THREADS", "SG_COALESCE_LANES", "SG_COALESCE_SPIN_US", "SG_COALESCE_TREE", "SG_BUILD_THREADS",
+                    "SG_BUILD_SHARED_COUNTERS", "SG_NO_LONG_QUERIES", "SG_VERBOSE", "SG_DEBUG_SKIP"}
+
+
+def _knobs(ix=None):
+    from suggest_amd.index import knobs
+    return {r["name"]: r for r in knobs(ix)}
+
+
+def _tune_index(ix):
+    """sg_debug_tune_index: what the first upload does to the knobs, without a GPU -> (rc, out[6], message)"""
+    import ctypes as C
+    from suggest_amd import _lib
+    st, out = (C.c_double * 2)(), (C.c_int32 * 6)()
+    with ix._use() as h:
+        rc = _lib.lib().sg_debug_tune_index(h, st, out)
+    return rc, list(out), _lib.lib().sg_last_error().decode()
+
+
+def _tune(ix, name, value):
+    from suggest_amd import _lib
+    with ix._use() as h:
+        rc = _lib.lib().sg_index_tune(h, name.encode(), int(value))
+    return rc, _lib.lib().sg_last_error().decode()
+
+
+@pytest.fixture
+def no_knobs_in_env(monkeypatch):
+    for name in KNOB_TABLE:
+        monkeypatch.delenv(name, raising=False)
+    return monkeypatch
+
+
+def test_knob_table_is_the_pinned_one():
+    rows = _knobs()
+    assert {n: (r["lo"], r["hi"], r["default"], "E" * r["env"] + "T" * r["tune"]) for n, r in rows.items()} == KNOB_TABLE
+    assert tuple(n for n, r in rows.items() if r["pins_shape"]) == SHAPE_KNOBS
+    assert {n for n, r in rows.items() if r["tuner"]} == set(TUNER_KNOBS)
+    assert [n for n, r in rows.items() if r["pow2"]] == ["SG_PIPE_NW"]
+    assert all(r["value"] == r["default"] and not r["explicit"] for r in rows.values())
+
+
+def test_environment_and_tune_accept_and_reject_alike(cars_lines, no_knobs_in_env):
+    """Every row at and just outside the ends of its range (SG_PIPE_NW: also between its powers of two; the environment: also text
+    that is no integer): both routes take a value or refuse it with SG_E_INVALID alike, a value taken is the index's afterwards, a
+    refused one leaves the index untuned, and a row that one route does not serve is refused there in so many words."""
+    from suggest_amd import NGramIndex
+    monkeypatch, desc, docs = no_knobs_in_env, _desc(CARS_DESC), cars_lines[:100]
+    for name, row in _knobs().items():
+        values = [v for v in (row["lo"] - 1, row["lo"], row["hi"], row["hi"] + 1) if -2**31 <= v <= INT32_MAX]
+        values += [3, 6] if row["pow2"] else []
+        for v in values + ["abc", "4x"]:
+            legal = isinstance(v, int) and row["lo"] <= v <= row["hi"] and not (row["pow2"] and v & (v - 1))
+            ix = NGramIndex(docs, desc, upload=False)
+            monkeypatch.setenv(name, str(v))
+            rc, _, msg = _tune_index(ix)
+            assert (rc == 0) == (legal and row["env"]), (name, v, rc, msg)
+            if rc == 0:
+                got = _knobs(ix)[name]
+                assert got["value"] == v and got["explicit"], (name, v, got)
+            else:
+                assert rc == -1 and name in msg, (name, v, rc, msg)
+                assert ("not from the environment" in msg) == (not row["env"]), (name, v, msg)
+                assert str(v) in msg or not row["env"], (name, v, msg)
+                assert _tune_index(ix)[0] == -1, (name, v, "a refused value must leave the index untuned")
+                monkeypatch.delenv(name)
+                assert _tune_index(ix)[0] == 0 and not _knobs(ix)[name]["explicit"], (name, v, "nothing of the refused attempt may stay")
+            monkeypatch.delenv(name, raising=False)
+            ix.close()
+            if not isinstance(v, int):
+                continue
+            ix = NGramIndex(docs, desc, upload=False)
+            rc, msg = _tune(ix, name, v)
+            assert (rc == 0) == (legal and row["tune"]), (name, v, rc, msg)
+            if rc == 0:
+                got = _knobs(ix)[name]
+                assert got["value"] == v and got["explicit"], (name, v, got)
+            else:
+                assert rc == -1 and name in msg, (name, v, rc, msg)
+                assert ("not set through sg_index_tune" in msg) == (not row["tune"]), (name, v, msg)
+                assert not _knobs(ix)[name]["explicit"], (name, v)
+            ix.close()
+    ix = NGramIndex(docs, desc, upload=False)
+    assert _tune(ix, "SG_NO_SUCH_KNOB", 1)[0] == -1
+    monkeypatch.setenv("SG_T_FLOOR", "")            # an empty variable counts as not set
+    assert _tune_index(ix)[0] == 0 and not _knobs(ix)["SG_T_FLOOR"]["explicit"]
+
+
+def test_explicit_knobs_beat_the_tuner(cars_lines, no_knobs_in_env):
+    """cars: the tuner chooses filter level 2, 2^11 counters and the smallest stream workgroup (test_tuner_choices_are_pinned).  A knob
+    set before the first upload — through sg_index_tune or the environment — is still there after it; the others are the tuner's."""
+    from suggest_amd import NGramIndex
+    monkeypatch, desc = no_knobs_in_env, _desc(CARS_DESC)
+    rc, out, _ = _tune_index(NGramIndex(cars_lines, desc, upload=False))
+    assert rc == 0 and out == [11, 2, 0, 2, 11, 2048]
+    ix = NGramIndex(cars_lines, desc, upload=False).tune(SG_FILTER_LEVEL=4, SG_LOG2_CNT=12)
+    rc, out, _ = _tune_index(ix)
+    assert rc == 0 and out == [12, 4, 0, 2, 11, 2048], out
+    rows = _knobs(ix)
+    assert rows["SG_FILTER_LEVEL"]["explicit"] and rows["SG_LOG2_CNT"]["explicit"] and not rows["SG_PIPE_NW"]["explicit"]
+    assert rows["SG_PIPE_SHAPE_AUTO"]["value"] == 1            # (the tuner's stream workgroup pins nothing)
+    ix = NGramIndex(cars_lines, desc, upload=False).tune(SG_PIPE_NW=8)
+    rc, out, _ = _tune_index(ix)
+    assert rc == 0 and out == [11, 2, 0, 8, 11, 2048], out
+    monkeypatch.setenv("SG_FILTER_LEVEL", "4")
+    monkeypatch.setenv("SG_LOG2_CNT", "12")
+    rc, out, _ = _tune_index(NGramIndex(cars_lines, desc, upload=False))
+    assert rc == 0 and out == [12, 4, 0, 2, 11, 2048], out
+
+
+def test_shape_knobs_pin_the_stream_workgroup_and_auto_hands_it_back(cars_lines, no_knobs_in_env):
+    from suggest_amd import NGramIndex
+    monkeypatch, desc, docs = no_knobs_in_env, _desc(CARS_DESC), cars_lines[:100]
+    for name, value in zip(SHAPE_KNOBS, (4, 12, 4096)):
+        ix = NGramIndex(docs, desc, upload=False)
+        assert _knobs(ix)["SG_PIPE_SHAPE_AUTO"]["value"] == 1
+        ix.tune(**{name: value})
+        assert _knobs(ix)["SG_PIPE_SHAPE_AUTO"]["value"] == 0, name
+        assert _tune_index(ix)[0] == 0 and _knobs(ix)["SG_PIPE_SHAPE_AUTO"]["value"] == 0, name     # (the first upload keeps it)
+        ix.tune(SG_PIPE_SHAPE_AUTO=1)
+        assert _knobs(ix)["SG_PIPE_SHAPE_AUTO"]["value"] == 1 and _knobs(ix)[name]["value"] == value, name
+        ix = NGramIndex(docs, desc, upload=False)
+        monkeypatch.setenv(name, str(value))
+        assert _tune_index(ix)[0] == 0 and _knobs(ix)["SG_PIPE_SHAPE_AUTO"]["value"] == 0, name
+        monkeypatch.delenv(name)
+    ix = NGramIndex(docs, desc, upload=False).tune(SG_T_FLOOR=4, SG_PIPE_SUB=3, SG_PIPE=1)      # (any other knob pins nothing)
+    assert _tune_index(ix)[0] == 0 and _knobs(ix)["SG_PIPE_SHAPE_AUTO"]["value"] == 1
+
+
+def test_the_prose_names_what_the_table_names():
+    """The sg_index_tune comment of the header and DESIGN.md §4c name every row of the table, and every SG_* name in them is a row or
+    one of the process-wide switches."""
+    header = open(os.path.join(ROOT, "include", "suggest_hip.h")).read()
+    decl = header.index("int sg_index_tune(")
+    comment = header[header.rindex("/*", 0, decl):decl]
+    design = open(os.path.join(ROOT, "DESIGN.md")).read()
+    section = design[design.index("### 4c."):design.index("### 4d.")]
+    rows = set(_knobs())
+    for where, text in (("suggest_hip.h", comment), ("DESIGN.md §4c", section)):
+        named = set(re.findall(r"SG_[A-Z0-9_]+", text))
+        assert rows <= named, (where, rows - named)
+        assert named <= rows | PROCESS_SWITCHES, (where, named - rows - PROCESS_SWITCHES)
+    for name, row in _knobs().items():         # the table's line of each row carries its range and default
+        line = next(l for l in section.splitlines() if l.startswith("| `%s` |" % name))
+        cells = [c.strip() for c in line.split("|")]
+        lo, hi = ("2", "8") if row["pow2"] else (str(row["lo"]).replace("-", "−"), "2^31−1" if row["hi"] == INT32_MAX else str(row["hi"]))
+        assert cells[2].startswith(lo) and cells[2].endswith(hi) and cells[3] == str(row["default"]), (name, cells)
+        assert cells[4] == " ".join(("E",) * row["env"] + ("T",) * row["tune"]) and cells[5] == "P" * row["pins_shape"] and cells[6] == "A" * row["tuner"], (name, cells)
+
+
+def test_the_fuzzer_draws_legal_knob_values():
+    """tools/fuzz_parity.py sets its knobs through the environment: every SG_* name it can draw is a row that the environment serves,
+    every value inside the row's range (an illegal one would now fail the trial's upload).  Other keys are the fuzzer's own."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("fuzz_parity", os.path.join(ROOT, "tools", "fuzz_parity.py"))
+    fz = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(fz)
+    rows = _knobs()
+
+    def check(name, value, ctx):
+        if not name.startswith("SG_"):
+            return
+        row = rows.get(name)
+        assert row is not None and row["env"], (ctx, name)
+        v = int(value)
+        assert str(v) == value and row["lo"] <= v <= row["hi"] and not (row["pow2"] and v & (v - 1)), (ctx, name, value)
+
+    for name, choices in fz.KNOBS:
+        for value in choices:
+            check(name, value, "KNOBS")
+    trials = 0
+    for seed in list(range(1, 301)) + [300004, 700812, 610200998, 77700102924]:
+        t = fz.make_trial(seed)
+        if t is None:
+            continue
+        trials += 1
+        for name, value in t["env"].items():
+            check(name, value, seed)
+    assert trials > 200

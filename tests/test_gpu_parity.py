@@ -369,9 +369,9 @@ def test_saturating_bucket_and_candidate_overflow():
     assert np.array_equal(ids[valid], oi[valid])
 
 
-@pytest.mark.parametrize("knobs", [dict(SG_T_FLOOR="1", SG_FILTER_LEVEL="0", SG_LOG2_CNT="9", SG_SPLIT_CHUNKS="0", SG_TIGHTEN="1", SG_ROOMY="0"),
+@pytest.mark.parametrize("knobs", [dict(SG_T_FLOOR="2", SG_FILTER_LEVEL="0", SG_LOG2_CNT="9", SG_SPLIT_CHUNKS="0", SG_TIGHTEN="1", SG_ROOMY="0"),
                                    dict(SG_T_FLOOR="3", SG_FILTER_LEVEL="3", SG_LOG2_CNT="12", SG_SPLIT_CHUNKS="8", SG_TIGHTEN="0", SG_ROOMY="1"),
-                                   dict(SG_T_FLOOR="100", SG_FILTER_LEVEL="1", SG_LOG2_CNT="10", SG_SPLIT_CHUNKS="200", SG_TIGHTEN="1", SG_ROOMY="1"),
+                                   dict(SG_T_FLOOR="64", SG_FILTER_LEVEL="1", SG_LOG2_CNT="10", SG_SPLIT_CHUNKS="200", SG_TIGHTEN="1", SG_ROOMY="1"),
                                    dict(SG_T_FLOOR="8", SG_FILTER_LEVEL="4", SG_LOG2_CNT="11", SG_TIGHTEN="0", SG_ROOMY="0")])
 def test_results_do_not_depend_on_tuning_knobs(monkeypatch, knobs):
     """The lossy counters are only a filter (every flagged doc is verified exactly), so list-skipping depth,
