@@ -245,6 +245,29 @@ uint32_t sg_lm_order(const sg_lm* lm);
 int sg_lm_build_google(const uint8_t* text, uint64_t len, uint32_t order, const char* start_symbol, const char* end_symbol,
                        const char* const* alphabet, uint32_t n_alphabet, const char* const* separators, uint32_t n_separators,
                        const char* out_dir);
+/* The same corpus straight to a ready model, on the GPU `device`, with no files in between: sg_lm_build_google followed by
+ * sg_lm_load_google_ex on what it wrote (NGramBuilder.Build over NewSentenceRetriever, pkg/lm/ngram_builder.go:19-64,
+ * sentence_retriever.go:54-81; lm.NewTokenizer; buildDictionary's numbering, binary.go:140-198; the vector builder,
+ * ngram_vector_builder.go).  id_order 1 numbers the words by (count desc, bytes asc), id_order 0 by first appearance in the
+ * wrapped token stream — the line order sg_lm_build_google writes.  Decoding, lower-casing, classifying, hashing, counting and the
+ * sort and reduce of every level run on the device; the host numbers the distinct words and receives the finished levels, which
+ * are uploaded on first use like a loaded model's.  order is 1 .. 8; at most 1 GiB of text (SG_E_UNSUPPORTED above);
+ * an empty start or end symbol, or one with a space, tab or newline, is SG_E_INVALID; an alphabet that holds U+0020 is
+ * SG_E_UNSUPPORTED.  len == 0 or a text without a token gives the empty model the file path gives; len == 0 touches no
+ * device.  On failure *out is untouched. */
+int sg_lm_build_device(const uint8_t* text, uint64_t len, uint32_t order, const char* start_symbol, const char* end_symbol,
+                       const char* const* alphabet, uint32_t n_alphabet, const char* const* separators, uint32_t n_separators,
+                       int id_order, int device, sg_lm** out);
+/* Any model in the production format that sg_lm_load_binary reads: lm_path = nGramModel.Store (ngram_model.go:100-121,
+ * packed_array.go:96-116) — "0.0.2", the order byte, per level "container-bytes value-bytes total\n" and the little-endian
+ * containers and values of sg_lm_level; cdb_path = BuildCDBDictionary (pkg/dictionary/helpers.go:52-100) — key = word id as 4
+ * bytes little endian, value = the word.  The minimal perfect hash the reference appends to the .lm (buildMPH, binary.go:200-210) is NOT
+ * written: the pair reloads here, Go's RetrieveLMFromBinary needs that section.  A file that cannot be written is SG_E_INVALID with
+ * its path in the message; the .lm is written first, so a failed store may leave it (or a partial file) behind. */
+int sg_lm_store_binary(const sg_lm* lm, const char* lm_path, const char* cdb_path);
+/* Test hook, process-wide (like sg_debug_poison): sg_lm_build_device keeps only the low `bits` bits of a word's hash, 0 = all 64 —
+ * words then collide in its vocabulary table and are told apart by their bytes alone. */
+int sg_debug_lm_build_hash_bits(uint32_t bits);
 void sg_lm_retain(sg_lm* lm);
 void sg_lm_release(sg_lm* lm);
 uint32_t sg_lm_num_words(const sg_lm* lm);

@@ -28,6 +28,7 @@ EXPORTS = [
     "sg_host_alloc", "sg_host_free", "sg_suggest_submit", "sg_suggest_submit_on", "sg_autocomplete_submit", "sg_ticket_wait",
     "sg_metric_tables_create", "sg_metric_tables_retain", "sg_metric_tables_release", "sg_suggest_batch_tables", "sg_suggest_batch_from", "sg_index_launch_stats", "sg_index_pipe_stats", "sg_index_pipe_volumes",
     "sg_lm_score_text_batch", "sg_lm_score_text_batch_device", "sg_lm_score_word_ids_batch",
+    "sg_lm_build_device", "sg_lm_store_binary", "sg_debug_lm_build_hash_bits",
 ]
 SG_COUNT_LM_ERROR = 0xFFFFFFFC
 
@@ -99,6 +100,9 @@ def lib():
     if hasattr(L, "sg_lm_order"): L.sg_lm_order.argtypes = [vp]
     if hasattr(L, "sg_lm_order"): L.sg_lm_order.restype = u32
     if hasattr(L, "sg_lm_build_google"): L.sg_lm_build_google.argtypes = [C.c_char_p, u64, u32, C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), u32, C.POINTER(C.c_char_p), u32, C.c_char_p]
+    if hasattr(L, "sg_lm_build_device"): L.sg_lm_build_device.argtypes = [vp, u64, u32, C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), u32, C.POINTER(C.c_char_p), u32, i32, i32, C.POINTER(vp)]
+    if hasattr(L, "sg_lm_store_binary"): L.sg_lm_store_binary.argtypes = [vp, C.c_char_p, C.c_char_p]
+    if hasattr(L, "sg_debug_lm_build_hash_bits"): L.sg_debug_lm_build_hash_bits.argtypes = [u32]
     if hasattr(L, "sg_lm_retain"): L.sg_lm_retain.argtypes = [vp]
     if hasattr(L, "sg_lm_retain"): L.sg_lm_retain.restype = None
     if hasattr(L, "sg_lm_release"): L.sg_lm_release.argtypes = [vp]

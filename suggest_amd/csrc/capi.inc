@@ -222,6 +222,20 @@ const LowerPair kLowerPairs[] = {
 #include "unicode_lower.inc"
 };
 
+// alphabet.CreateAlphabet(spec).Has as the device word tokeniser reads it (d_lm_alpha_has): a bitmap below 128, inclusive ranges
+// above — from the runes the specification lists, not from a probe of every code point.  lm_upload and lm_build.inc use it.
+void lm_alphabet_tables(const std::vector<std::string>& spec, uint64_t ascii[2], std::vector<uint2>& ranges) {
+  ascii[0] = ascii[1] = 0;
+  ranges.clear();
+  std::vector<uint32_t> runes;
+  host_alphabet_runes(spec, runes);
+  for (uint32_t r : runes) {
+    if (r < 128u) ascii[r >> 6] |= 1ull << (r & 63u);
+    else if (!ranges.empty() && ranges.back().y + 1u == r) ranges.back().y = r;
+    else ranges.push_back(make_uint2(r, r));
+  }
+}
+
 // symbol tables, lower-case table, wrap and pad of the description: what the device tokeniser reads
 int upload_description(const HostIndex& h, Replica* r, DeviceIndex& d) {
   int rc;
@@ -793,6 +807,7 @@ int launch(sg_index* index, Replica* rep, const LaunchReq& r) {
 }  // namespace
 
 #include "index_build.inc"
+#include "lm_build.inc"
 #include "forward_index.inc"
 #include "packed_store.inc"
 
@@ -2226,6 +2241,51 @@ int sg_lm_build_google(const uint8_t* text, uint64_t len, uint32_t order, const 
   return rc;
 }
 
+int sg_lm_build_device(const uint8_t* text, uint64_t len, uint32_t order, const char* start_symbol, const char* end_symbol,
+                       const char* const* alphabet, uint32_t n_alphabet, const char* const* separators, uint32_t n_separators,
+                       int id_order, int device, sg_lm** out) {
+  SG_GUARD_BEGIN
+  if ((!text && len) || !start_symbol || !end_symbol || !out || (n_alphabet && !alphabet) || (n_separators && !separators)) { set_error("null argument"); return SG_E_INVALID; }
+  if (order < 1 || order > 8) { set_error("nGramOrder should be 1 .. 8"); return SG_E_INVALID; }
+  if (id_order != 0 && id_order != 1) { set_error("id_order is 0 (first appearance) or 1 (count desc, word asc)"); return SG_E_INVALID; }
+  for (const char* sym : {start_symbol, end_symbol}) {           // (what the Google files between builder and loader could not carry either)
+    if (!*sym) { set_error("the start and end symbols must not be empty"); return SG_E_INVALID; }
+    if (strpbrk(sym, " \t\n")) { set_error("the start and end symbols must not contain a space, tab or newline"); return SG_E_INVALID; }
+  }
+  if (len > ((uint64_t)1 << 30)) { set_error("corpus above 1 GiB: beyond the device builder"); return SG_E_UNSUPPORTED; }
+  std::unique_ptr<sg_lm> lm(new (std::nothrow) sg_lm());
+  if (!lm) { set_error("out of host memory"); return SG_E_NOMEM; }
+  HostLM& h = lm->host;
+  std::vector<std::string> seps;
+  for (uint32_t i = 0; i < n_alphabet; i++) h.alphabet.emplace_back(alphabet[i]);
+  for (uint32_t i = 0; i < n_separators; i++) seps.emplace_back(separators[i]);
+  if (host_alphabet_has(h.alphabet, ' ')) { set_error("an alphabet with U+0020 is beyond the device builder (the tokeniser trims it)"); return SG_E_UNSUPPORTED; }
+  h.order = order;
+  if (len == 0) lm_build_empty(h, order);
+  else if (int rc = lm_build_on_device(text, len, order, start_symbol, end_symbol, seps, id_order, device, h)) return rc;
+  h.start_symbol = lm_word_id(h, start_symbol);
+  h.end_symbol = lm_word_id(h, end_symbol);
+  *out = lm.release();
+  return SG_OK;
+  SG_GUARD_END(SG_RC)
+}
+
+int sg_lm_store_binary(const sg_lm* lm, const char* lm_path, const char* cdb_path) {
+  SG_GUARD_BEGIN
+  if (!lm || !lm_path || !cdb_path) { set_error("null argument"); return SG_E_INVALID; }
+  std::string err;
+  const int rc = lm_store_binary(lm->host, lm_path, cdb_path, err);
+  if (rc) set_error(err);
+  return rc;
+  SG_GUARD_END(SG_RC)
+}
+
+int sg_debug_lm_build_hash_bits(uint32_t bits) {
+  if (bits > 64u) { set_error("hash bits: 0 (all 64) .. 64"); return SG_E_INVALID; }
+  g_lm_build_hash_bits.store(bits, std::memory_order_relaxed);
+  return SG_OK;
+}
+
 void sg_lm_retain(sg_lm* lm) { if (lm) lm->refs.fetch_add(1); }
 void sg_lm_release(sg_lm* lm) {
   if (!lm || lm->refs.fetch_sub(1) != 1) return;
@@ -2311,11 +2371,7 @@ static int lm_upload(sg_lm* lm, int device) {
     const HostLM& h = lm->host;
     std::vector<uint2> ranges;
     uint64_t alpha_ascii[2] = {0, 0};
-    for (uint32_t r = 0; r < 128; r++) if (host_alphabet_has(h.alphabet, r)) alpha_ascii[r >> 6] |= 1ull << (r & 63u);
-    for (uint32_t r = 128; r < 0x110000u; r++) {
-      if (!host_alphabet_has(h.alphabet, r)) continue;
-      if (!ranges.empty() && ranges.back().y + 1u == r) ranges.back().y = r; else ranges.push_back(make_uint2(r, r));
-    }
+    lm_alphabet_tables(h.alphabet, alpha_ascii, ranges);
     void* ar = nullptr;
     LM_ALLOC(ar, std::max<size_t>(ranges.size() * 8, 16));
     if (!ranges.empty()) HIP_TRY(hipMemcpy(ar, ranges.data(), ranges.size() * 8, hipMemcpyHostToDevice));

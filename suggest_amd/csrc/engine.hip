@@ -2500,13 +2500,14 @@ struct SpellArgs {
   uint32_t start_symbol;
 };
 
-__device__ __forceinline__ bool d_lm_alpha_has(const SpellArgs& p, uint32_t r) {
+// (P: SpellArgs, or the builder's own small tables of lm_build.inc — any struct with these fields)
+template <class P> __device__ __forceinline__ bool d_lm_alpha_has(const P& p, uint32_t r) {
   if (r < 128u) return (p.alpha_ascii[r >> 6] >> (r & 63u)) & 1ull;
   uint32_t lo = 0, hi = p.n_alpha_ranges;
   while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (p.alpha_ranges[mid].y < r) lo = mid + 1; else hi = mid; }
   return lo < p.n_alpha_ranges && p.alpha_ranges[lo].x <= r;
 }
-__device__ __forceinline__ uint32_t d_lm_lower(const SpellArgs& p, uint32_t r) {
+template <class P> __device__ __forceinline__ uint32_t d_lm_lower(const P& p, uint32_t r) {
   if (r < 0x80u) return (r - 'A' < 26u) ? r + 32u : r;
   uint32_t lo = 0, hi = p.n_lower;
   while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (p.lower_from[mid] < r) lo = mid + 1; else hi = mid; }

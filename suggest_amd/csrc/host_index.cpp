@@ -155,6 +155,18 @@ bool host_alphabet_has(const std::vector<std::string>& spec, uint32_t r) {
   return false;
 }
 
+void host_alphabet_runes(const std::vector<std::string>& spec, std::vector<uint32_t>& out) {
+  out.clear();
+  for (const auto& part : spec) {                              // (the enumeration of alphabet_part_has)
+    if (part == "english") for (uint32_t r = 'a'; r <= 'z'; r++) out.push_back(r);
+    else if (part == "numbers") for (uint32_t r = '0'; r <= '9'; r++) out.push_back(r);
+    else if (part == "russian") { for (uint32_t r = 0x430; r <= 0x44F; r++) out.push_back(r); out.push_back(0x451); }
+    else decode_all(part, out);
+  }
+  std::sort(out.begin(), out.end());
+  out.erase(std::unique(out.begin(), out.end()), out.end());
+}
+
 uint64_t mix64(uint64_t k) {  // splitmix64 finaliser
   k ^= k >> 30; k *= 0xBF58476D1CE4E5B9ull;
   k ^= k >> 27; k *= 0x94D049BB133111EBull;

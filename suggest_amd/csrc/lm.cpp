@@ -233,6 +233,72 @@ void lm_level_packed(const HostLM& lm, uint32_t level, std::vector<uint64_t>& co
   *total = (uint32_t)lv.total;
 }
 
+// nGramModel.Store (ngram_model.go:100-121, packed_array.go:96-116) into <name>.lm and BuildCDBDictionary
+// (pkg/dictionary/helpers.go:52-100) into <name>.cdb: what lm_load_binary reads back.  .lm: "0.0.2", the order, per level a line
+// "container-bytes value-bytes total\n" and the two little-endian arrays of lm_level_packed.  .cdb: D. J. Bernstein's constant
+// database, key = word id as 4 bytes little endian, value = the word, records in id order — 256 (position, slots) header pairs,
+// the records, then per table twice as many (hash, position) slots as it has records, filled from (hash >> 8) % slots on.
+// The minimal perfect hash the reference appends to .lm is NOT written: lm_load_binary does not read it (the dictionary gives
+// the words in id order), Go's RetrieveLMFromBinary does.
+int lm_store_binary(const HostLM& lm, const char* lm_path, const char* cdb_path, std::string& err) {
+  auto put_u32 = [](std::string& s, uint32_t v) { for (int i = 0; i < 4; i++) s.push_back((char)(v >> (8 * i))); };
+  auto write_all = [&](const char* path, const std::string& head, const std::string& body) {
+    std::ofstream f(path, std::ios::binary | std::ios::trunc);
+    if (f) { f.write(head.data(), (std::streamsize)head.size()); f.write(body.data(), (std::streamsize)body.size()); f.close(); }
+    if (!f) { err = std::string("failed to write ") + path; return false; }
+    return true;
+  };
+  {
+    std::string out("0.0.2");
+    out.push_back((char)lm.order);
+    std::vector<uint64_t> c, v;
+    for (uint32_t k = 0; k < lm.level.size(); k++) {
+      uint32_t total;
+      lm_level_packed(lm, k, c, v, &total);
+      out += std::to_string(c.size() * 8) + " " + std::to_string(v.size() * 8) + " " + std::to_string(total) + "\n";
+      for (const std::vector<uint64_t>* arr : {&c, &v})
+        for (uint64_t x : *arr) for (int i = 0; i < 8; i++) out.push_back((char)(x >> (8 * i)));
+    }
+    if (!write_all(lm_path, out, std::string())) return SG_E_INVALID;
+  }
+  const size_t n = lm.words.size();
+  std::vector<uint32_t> hash(n), pos(n);
+  std::string recs;
+  uint64_t bytes = 2048;
+  for (const auto& w : lm.words) bytes += 12 + w.size() + 16;   // record + its two table slots
+  if (bytes >= 0xFFFFFFFFull) { err = "dictionary too large for a cdb file (4 GiB)"; return SG_E_UNSUPPORTED; }
+  recs.reserve((size_t)bytes);
+  std::vector<uint32_t> per_table(256, 0);
+  for (size_t i = 0; i < n; i++) {
+    uint32_t h = 5381;
+    for (int j = 0; j < 4; j++) h = ((h << 5) + h) ^ (uint32_t)(((uint32_t)i >> (8 * j)) & 0xFFu);
+    hash[i] = h;
+    pos[i] = (uint32_t)(2048 + recs.size());
+    put_u32(recs, 4); put_u32(recs, (uint32_t)lm.words[i].size()); put_u32(recs, (uint32_t)i);
+    recs += lm.words[i];
+    per_table[h & 255u]++;
+  }
+  std::vector<std::vector<uint32_t>> members(256);
+  for (size_t i = 0; i < n; i++) members[hash[i] & 255u].push_back((uint32_t)i);
+  std::string header, tables;
+  uint32_t tpos = (uint32_t)(2048 + recs.size());
+  for (uint32_t t = 0; t < 256; t++) {
+    const uint32_t slots = per_table[t] * 2;
+    put_u32(header, slots ? tpos : 0u); put_u32(header, slots);
+    if (!slots) continue;
+    std::vector<std::pair<uint32_t, uint32_t>> tab(slots, {0u, 0u});
+    for (uint32_t i : members[t]) {
+      uint32_t s = (hash[i] >> 8) % slots;
+      while (tab[s].second) s = (s + 1) % slots;
+      tab[s] = {hash[i], pos[i]};
+    }
+    for (const auto& e : tab) { put_u32(tables, e.first); put_u32(tables, e.second); }
+    tpos += 8 * slots;
+  }
+  if (!write_all(cdb_path, header, recs + tables)) return SG_E_INVALID;
+  return SG_OK;
+}
+
 double lm_model_score(const HostLM& lm, const uint32_t* ids, size_t n) {   // NGramModel.Score
   const size_t order = std::min<size_t>(lm.order, n);
   uint32_t counts[10] = {0};

@@ -88,6 +88,7 @@ uint32_t host_next_rune(const uint8_t* s, size_t n, size_t* adv);   // Go range 
 uint32_t host_lower_rune(uint32_t r);                                // unicode.ToLower (simple mappings)
 uint32_t host_utf8_width(uint32_t r);
 bool host_alphabet_has(const std::vector<std::string>& spec, uint32_t r);   // alphabet.CreateAlphabet(spec).Has(r)
+void host_alphabet_runes(const std::vector<std::string>& spec, std::vector<uint32_t>& out);   // every rune it has, ascending
 
 // ---- language model of the spellchecker caller (lm.cpp) ----
 constexpr uint32_t kUnknownWord = 0xFFFFFFFFu;      // pkg/lm/indexer.go:16
@@ -118,6 +119,7 @@ int lm_load_google(const char* dir, uint32_t order, const char* start_symbol, co
                    int id_order, HostLM& lm, std::string& err);
 int lm_load_binary(const char* lm_path, const char* cdb_path, const char* start_symbol, const char* end_symbol,
                    const std::vector<std::string>& alphabet, HostLM& lm, std::string& err);
+int lm_store_binary(const HostLM& lm, const char* lm_path, const char* cdb_path, std::string& err);
 void lm_level_packed(const HostLM& lm, uint32_t level, std::vector<uint64_t>& containers, std::vector<uint64_t>& values, uint32_t* total);
 int lm_build_google_files(const uint8_t* text, size_t n, uint32_t order, const char* start_symbol, const char* end_symbol,
                           const std::vector<std::string>& alphabet, const std::vector<std::string>& separators, const char* out_dir,

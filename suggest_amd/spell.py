@@ -55,6 +55,30 @@ class LanguageModel:
         _lib.check(_lib.lib().sg_lm_build_google(raw, len(raw), int(order), _enc(start_symbol), _enc(end_symbol), alpha, len(alphabet),
                                                  seps, len(separators), _enc(directory)))
 
+    @classmethod
+    def from_corpus(cls, text, order=3, start_symbol="<S>", end_symbol="</S>", alphabet=("english", "russian", "numbers", "-."),
+                    separators=("\n",), id_order="count", device=0):
+        """The model of a corpus, built on the GPU (sg_lm_build_device): what build_files + LanguageModel(directory, id_order=...)
+        give, with no files in between.  id_order "count": (count desc, word asc), the production numbering; "lines": first
+        appearance, the line order build_files writes."""
+        raw = text if isinstance(text, (bytes, bytearray, memoryview)) else _enc(text)
+        buf = np.frombuffer(raw, dtype=np.uint8)
+        alpha = (C.c_char_p * len(alphabet))(*[_enc(a) for a in alphabet])
+        seps = (C.c_char_p * len(separators))(*[_enc(a) for a in separators])
+        h = C.c_void_p()
+        L = _lib.lib()
+        _lib.check(L.sg_lm_build_device(buf.ctypes.data if buf.size else None, buf.size, int(order), _enc(start_symbol), _enc(end_symbol),
+                                        alpha, len(alphabet), seps, len(separators), {"lines": 0, "count": 1}[id_order], int(device), C.byref(h)))
+        self = cls.__new__(cls)
+        self._h = h
+        self.order = int(L.sg_lm_order(h))
+        return self
+
+    def save(self, binary, dictionary):
+        """Write the model as <binary> (.lm, nGramModel.Store) and <dictionary> (.cdb, BuildCDBDictionary): the pair
+        LanguageModel(binary=..., dictionary=...) loads.  The reference's MPH section is not written (sg_lm_store_binary)."""
+        _lib.check(_lib.lib().sg_lm_store_binary(self._h, _enc(binary), _enc(dictionary)))
+
     def close(self):
         if getattr(self, "_h", None):
             _lib.lib().sg_lm_release(self._h)
