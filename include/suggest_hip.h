@@ -389,6 +389,13 @@ int sg_debug_pipe_layout(uint32_t n_q, uint32_t cand_cap, uint64_t out[12]);
 /* [r6] Test hook: out[0] = the device ordinal of replica number `replica`, out[1..7] = the device its posting store, seg_off, orig_of,
  * forward-index records and terms, term table and counter block are resident on (-1: null).  All must equal out[0]. */
 int sg_debug_replica_devices(sg_index* index, uint32_t replica, int32_t out[8]);
+/* Test hook: one array of replica number `replica` copied back as it lies in HBM, undecoded (tests/packed_ref.py restates the formats
+ * and compares; tests/test_gpu_store.py).  which = 0 the packed posting chunks and the 64-chunk slack row behind them, 1 the packed
+ * seg_off (bit 31 = the term's 8-bit format, as stored), 2 orig_of, 3 x_of, 4 seg_base (segments + 1 entries), 5 cut_sample, 6 the
+ * forward-index records, 7 the forward-index term ids, 8 fx_base (0 bytes where the index has none); 9 / 10 the postings / seg_off of
+ * the host CSR they are all derived from (`replica` ignored; no GPU needed).  *out_bytes = the array's size; with out != NULL it is
+ * copied (SG_E_INVALID if cap_bytes is smaller).  SG_E_INVALID: not uploaded, no such replica, unknown array.  Reads only. */
+int sg_debug_index_array(sg_index* index, uint32_t replica, uint32_t which, void* out, uint64_t cap_bytes, uint64_t* out_bytes);
 
 /* Sets a tuning knob of the index, before or after its first upload: SG_LOG2_CNT, SG_T_FLOOR, SG_FILTER_LEVEL, SG_TIGHTEN, SG_ROOMY,
  * SG_ORDER, SG_PRETOK, SG_SPLIT_CHUNKS, SG_PARTS_CNT_BONUS; the pipeline's SG_PIPE, SG_PIPE_SUB, SG_PIPE_CAND_CAP, SG_PIPE_WIDE,

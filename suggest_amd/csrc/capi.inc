@@ -1144,6 +1144,55 @@ int sg_debug_replica_devices(sg_index* ix, uint32_t replica, int32_t out[8]) {
   SG_GUARD_END(SG_RC)
 }
 
+// Test hook: one array of replica number `replica` as it lies in HBM, undecoded (tests/packed_ref.py holds the second statement of
+// the formats and compares), or one of the two host CSR arrays everything on the device is derived from.  `which`: 0 the packed
+// chunks + the slack row, 1 the packed seg_off (bit-31 flags as stored), 2 orig_of, 3 x_of, 4 seg_base (S + 1), 5 cut_sample,
+// 6 fwd_rec, 7 fwd_terms, 8 fx_base (0 bytes when null), 9 / 10 the host CSR's postings / seg_off (no replica, no GPU needed).
+// *out_bytes = the array's size; it is copied when `out` is not null (cap_bytes below the size: SG_E_INVALID).  Reads only.
+int sg_debug_index_array(sg_index* ix, uint32_t replica, uint32_t which, void* out, uint64_t cap_bytes, uint64_t* out_bytes) {
+  SG_GUARD_BEGIN
+  if (!ix || !out_bytes) { set_error("null argument"); return SG_E_INVALID; }
+  const HostIndex& h = ix->host;
+  const void* src = nullptr;
+  uint64_t bytes = 0;
+  Replica* r = nullptr;
+  if (which == 9u) { src = h.postings.data(); bytes = (uint64_t)h.postings.size() * 4; }
+  else if (which == 10u) { src = h.seg_off.data(); bytes = (uint64_t)h.seg_off.size() * 4; }
+  else if (which > 10u) { set_error("sg_debug_index_array: unknown array"); return SG_E_INVALID; }
+  else {
+    { std::lock_guard<std::mutex> lock(ix->mu); if (replica < ix->replicas.size()) r = ix->replicas[replica].get(); }
+    if (!r) { set_error("sg_debug_index_array: index not uploaded / no such replica"); return SG_E_INVALID; }
+    const DeviceIndex& d = r->dix;
+    const uint64_t n_docs = d.n_docs, S = d.S;
+    switch (which) {
+      case 0: src = d.postings; bytes = (r->packed_chunks + 64) * 16; break;
+      case 1: src = d.seg_off; bytes = (uint64_t)d.n_terms * (S + 1) * 4; break;
+      case 2: src = d.orig_of; bytes = n_docs * 4; break;
+      case 3: src = r->x_of; bytes = n_docs * 4; break;
+      case 4: src = d.seg_base; bytes = (S + 1) * 4; break;
+      case 5: src = d.cut_sample; bytes = ~0ull; break;          // (as long as it was allocated)
+      case 6: src = d.fwd_rec; bytes = n_docs * 8; break;
+      case 7: src = d.fwd_terms; bytes = ~0ull; break;           // (the same: a whole number of 16-byte chunks)
+      default: src = d.fx_base; bytes = src ? (S + 1) * 4 : 0; break;
+    }
+    if (bytes) {    // every array is one allocation of the replica: never read past what dev_alloc gave it
+      uint64_t have = 0;
+      for (size_t i = 0; i < r->allocs.size(); i++) if (r->allocs[i] == src) have = r->alloc_bytes[i];
+      if (bytes == ~0ull) bytes = have;
+      if (!src || bytes > have) { set_error("sg_debug_index_array: the array is not an allocation of the replica"); return SG_E_INVALID; }
+    }
+  }
+  *out_bytes = bytes;
+  if (!out || !bytes) return SG_OK;
+  if (cap_bytes < bytes) { set_error("sg_debug_index_array: buffer too small"); return SG_E_INVALID; }
+  if (!r) { memcpy(out, src, (size_t)bytes); return SG_OK; }
+  DeviceGuard dg;
+  HIP_TRY(dg.set(r->device));
+  HIP_TRY(hipMemcpy(out, src, (size_t)bytes, hipMemcpyDeviceToHost));
+  return SG_OK;
+  SG_GUARD_END(SG_RC)
+}
+
 // Sets a knob of the table (knobs.inc), before or after the first upload.  Results never depend on the knobs; not synchronised with
 // launches in flight (a tool for sweeps, tools/sweep_knobs.py).
 int sg_index_tune(sg_index* ix, const char* knob, int value) {

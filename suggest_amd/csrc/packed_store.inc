@@ -327,7 +327,7 @@ int pack_store(const HostIndex& h, Replica* r, int g8_mode) {
   const uint64_t n_cs = total_chunks / 16 + 2;
   uint32_t* cs = nullptr;
   if ((rc = dev_alloc(r, (size_t)n_cs, &cs))) return rc;
-  HIP_TRY(hipMemset(cs, 0xFF, (size_t)n_cs * 4));
+  HIP_TRY(hipMemset(cs, 0xFF, std::max<size_t>((size_t)n_cs * 4, 16)));      // (all of the allocation: sg_debug_index_array reads it back whole)
   if (n_lists) {
     hipLaunchKernelGGL(pk_pack<true>, dim3(pk_grid), dim3(64), 0, 0, d.postings, d.seg_off, S, n_lists, (const uint32_t*)x_of, (uint32_t*)nullptr,
                        (const uint32_t*)new_off, packed, false, (const uint8_t*)term_fmt);

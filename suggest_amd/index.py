@@ -191,6 +191,25 @@ class NGramIndex:
             _lib.check(_lib.lib().sg_index_forward(h, int(first), int(n), int(cap), card.ctypes.data, nt.ctypes.data, keys.ctypes.data))
         return card, nt, keys
 
+    # name -> selector of sg_debug_index_array (all arrays of 32-bit words)
+    RAW_ARRAYS = {"packed": 0, "seg_off": 1, "orig_of": 2, "x_of": 3, "seg_base": 4, "cut_sample": 5, "fwd_rec": 6, "fwd_terms": 7,
+                  "fx_base": 8, "host_postings": 9, "host_seg_off": 10}
+
+    def raw_array(self, name, replica=0):
+        """Test hook (sg_debug_index_array): one array of a replica as it lies in HBM, undecoded, as a numpy array — "packed"
+        [chunks + 64, 4] words, "fwd_rec" [n_docs, 2], "fwd_terms" [chunks, 4], the others flat; "fx_base" is empty where the
+        index has none.  "host_postings" / "host_seg_off": the host CSR they are derived from (no upload needed)."""
+        which = self.RAW_ARRAYS[name]
+        n = C.c_uint64()
+        with self._use() as h:
+            _lib.check(_lib.lib().sg_debug_index_array(h, int(replica), which, None, 0, C.byref(n)))
+            out = np.zeros(n.value // 4, dtype=np.uint32)
+            if out.size:
+                _lib.check(_lib.lib().sg_debug_index_array(h, int(replica), which, out.ctypes.data, out.nbytes, C.byref(n)))
+        if name in ("packed", "fwd_terms"):
+            return out.reshape(-1, 4)
+        return out.reshape(-1, 2) if name == "fwd_rec" else out
+
     def tune(self, **knobs):
         """sg_index_tune: e.g. tune(SG_T_FLOOR=6, SG_FILTER_LEVEL=5) — results never depend on the knobs"""
         with self._use() as h:
