@@ -2507,7 +2507,7 @@ static int predict_on_device(sg_index* index, sg_lm* lm, Replica* rep, const uin
                o_zero_end = c.size(),
                o_from = c.take((size_t)n_q * 4), o_to = c.take((size_t)n_q * 4), o_sel = c.take((size_t)n_q * 4), o_stat = c.take(n_q),
                o_ctx = c.take((size_t)n_q * 32), o_clen = c.take(n_q), o_hasw = c.take(n_q), o_wlen = c.take((size_t)n_q * 4),
-               o_woff = c.take((size_t)(n_q + 1) * 8), o_words = c.take((size_t)q_bytes * 2 + 16);
+               o_woff = c.take((size_t)(n_q + 1) * 8), o_words = c.take((size_t)q_bytes * lm->slot_mul + 16);
   void* blk = nullptr;
   if (int rc = stream_scratch(rep->device, st, c.size(), &blk, SCRATCH_PREDICT)) return rc;
   char* dev = (char*)blk;
@@ -2530,7 +2530,7 @@ static int predict_on_device(sg_index* index, sg_lm* lm, Replica* rep, const uin
   p.alpha_ranges = lm->d_alpha_ranges; p.n_alpha_ranges = lm->n_alpha_ranges; p.alpha_ascii[0] = lm->alpha_ascii[0]; p.alpha_ascii[1] = lm->alpha_ascii[1];
   p.lower_from = rep->dix.lower_from; p.lower_to = rep->dix.lower_to; p.n_lower = rep->dix.n_lower;
   p.vocab = lm->d_vocab; p.vocab_mask = lm->vocab_mask; p.vocab_bytes = lm->d_vocab_bytes; p.vocab_off = lm->d_vocab_off;
-  p.start_symbol = h.start_symbol;
+  p.start_symbol = h.start_symbol; p.slot_mul = lm->slot_mul;
   p.lm_from = (uint32_t*)(dev + o_from); p.lm_to = (uint32_t*)(dev + o_to); p.status = (uint8_t*)(dev + o_stat);
   p.a_ids = (const uint32_t*)(dev + o_aids); p.a_cnt = (const uint32_t*)(dev + o_acnt);
   p.f_ids = (const uint32_t*)(dev + o_fids); p.f_cnt = (const uint32_t*)(dev + o_fcnt);

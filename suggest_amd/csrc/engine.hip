@@ -2490,7 +2490,7 @@ struct SpellArgs {
   // ---- spell_tokenize_kernel: the word tokeniser and the word ids, on the device ----
   const uint8_t* q_blob; const uint64_t* q_offs;  // the queries
   uint32_t* ctx_w; uint8_t* ctx_len_w; uint8_t* has_word_w;   // out (what ctx / ctx_len / has_word point at)
-  uint8_t* w_blob; uint64_t* w_off; uint32_t* w_len;          // out: the last word of query i is w_blob[w_off[i] .. + w_len[i]), somewhere in the query's slot w_blob[2 * q_offs[i] .. 2 * q_offs[i + 1])
+  uint8_t* w_blob; uint64_t* w_off; uint32_t* w_len;          // out: the last word of query i is w_blob[w_off[i] .. + w_len[i]), somewhere in the query's slot w_blob[slot_mul * q_offs[i] .. slot_mul * q_offs[i + 1])
   const uint2* alpha_ranges; uint32_t n_alpha_ranges;          // the model alphabet's runes >= 128 as inclusive ranges, ascending
   uint64_t alpha_ascii[2];                                     // ... and below 128 as a bitmap
   const uint32_t* lower_from; const uint32_t* lower_to; uint32_t n_lower;   // simple lower-case pairs (the index replica's)
@@ -2498,6 +2498,7 @@ struct SpellArgs {
   uint32_t vocab_mask;
   const uint8_t* vocab_bytes; const uint32_t* vocab_off;       // the words, id order (a hit is confirmed byte by byte)
   uint32_t start_symbol;
+  uint32_t slot_mul;                                           // bytes of a query's slot in w_blob per byte of the query (2; 3 when U+FFFD is in the alphabet)
 };
 
 // (P: SpellArgs, or the builder's own small tables of lm_build.inc — any struct with these fields)
@@ -2541,7 +2542,8 @@ __device__ uint32_t d_word_id(const SpellArgs& p, uint64_t h, const uint8_t* w, 
 // tokeniser (strings.ToLower, strings.Trim(" "), maximal runs of alphabet runes — pkg/analysis word tokenizer as the model
 // builds it), the last word, the ids of the words before it (the vocabulary hash, hits confirmed on the bytes), and the
 // wrap / trim rules of LanguageModel.Next.  The tokens are written lower-cased into the query's slot of w_blob, one behind the
-// other (two bytes of slot per query byte: a lower-case mapping can lengthen a rune's encoding, 2 -> 3 bytes at most).
+// other (slot_mul bytes of slot per query byte.  Two as a rule: a lower-case mapping can lengthen a rune's encoding, 2 -> 3 bytes
+// at most.  Three when U+FFFD is a letter of the model's alphabet: every invalid byte is then a letter of three bytes).
 // [r4] The queries of a block of 256 threads are consecutive in q_blob: the block copies their bytes into LDS with coalesced
 // loads, every thread scans ITS query there and writes its tokens into an LDS image of its slot, and the slots go out
 // coalesced.  Read and written byte by byte in global memory — 64 lanes at 64 addresses 20-odd bytes apart, a dependent
@@ -2551,7 +2553,7 @@ __device__ uint32_t d_word_id(const SpellArgs& p, uint64_t h, const uint8_t* w, 
 // hash — for the first eight and, in a ring of eight, the latest ones; the vocabulary lookups of the context words follow in
 // lockstep over the wave (token t of every lane together).  Looked up where a token ended — a different byte position in
 // every lane — the wave ran d_word_id's chain of dependent loads once per lane and token: most of the kernel's 0.09 ms.
-// Tokens are written one behind the other (the slot has two bytes per query byte), so the last word is wherever it was
+// Tokens are written one behind the other (the slot has slot_mul bytes per query byte), so the last word is wherever it was
 // written: w_off points there.
 __device__ __forceinline__ void spell_tokenize_one(const SpellArgs& p, uint32_t i, const uint8_t* q, uint32_t qlen, uint8_t* slot, uint64_t o0) {
   uint32_t a = 0, b = qlen;
@@ -2621,7 +2623,7 @@ __device__ __forceinline__ void spell_tokenize_one(const SpellArgs& p, uint32_t 
     for (int t = 0; t < 8; t++) if ((j & 7u) == (uint32_t)t) v = j < 8u ? first[t] : ring[t];
     return v;
   };
-  p.w_off[i] = 2 * o0 + (uint64_t)lw_o;
+  p.w_off[i] = (uint64_t)p.slot_mul * o0 + (uint64_t)lw_o;
   p.has_word_w[i] = n_tok ? 1 : 0;
   uint8_t cl = 0;
   uint32_t seq[8];
@@ -2647,7 +2649,9 @@ __global__ __launch_bounds__(256) void spell_tokenize_kernel(const SpellArgs p) 
   if (i0 >= p.n_q) return;
   const uint64_t B0 = p.q_offs[i0], B1 = p.q_offs[i1];          // the block's bytes: uniform
   const uint32_t nb = (uint32_t)min(B1 - B0, (uint64_t)0xFFFFFFFFu);
-  const bool staged = B1 - B0 <= (uint64_t)SG_STOK_BYTES;
+  // staged when the block's slots fit the LDS image: SG_STOK_BYTES query bytes at two bytes of slot each, two thirds of it at three
+  const uint32_t mul = p.slot_mul;
+  const bool staged = (B1 - B0) * mul <= (uint64_t)sizeof(s_slot);
   uint32_t shift = 0;
   if (staged) {                                                  // dword loads from the 4-byte boundary at or below the first byte
     const uintptr_t addr0 = (uintptr_t)(p.q_blob + B0);
@@ -2659,14 +2663,18 @@ __global__ __launch_bounds__(256) void spell_tokenize_kernel(const SpellArgs p) 
   __syncthreads();
   if (i < p.n_q) {
     const uint64_t o0 = p.q_offs[i], o1 = p.q_offs[i + 1];
-    if (staged) spell_tokenize_one(p, i, s_in + shift + (uint32_t)(o0 - B0), (uint32_t)(o1 - o0), s_slot + 2u * (uint32_t)(o0 - B0), o0);
-    else spell_tokenize_one(p, i, p.q_blob + o0, (uint32_t)(o1 - o0), p.w_blob + 2 * o0, o0);
+    if (staged) spell_tokenize_one(p, i, s_in + shift + (uint32_t)(o0 - B0), (uint32_t)(o1 - o0), s_slot + mul * (uint32_t)(o0 - B0), o0);
+    else spell_tokenize_one(p, i, p.q_blob + o0, (uint32_t)(o1 - o0), p.w_blob + (uint64_t)mul * o0, o0);
   }
   if (!staged) return;                                           // (uniform)
   __syncthreads();
-  // the slots out: w_blob + 2 B0 is 2-byte aligned at least (the scratch block is 16-byte aligned)
-  uint16_t* dst = (uint16_t*)(p.w_blob + 2 * B0);
-  for (uint32_t k = tid; k < nb; k += blockDim.x) dst[k] = ((const uint16_t*)s_slot)[k];
+  if (mul == 2u) {                                               // (uniform) the slots out: an even multiple of B0 is 2-byte aligned at least (the scratch block is 16-byte aligned)
+    uint16_t* dst = (uint16_t*)(p.w_blob + (uint64_t)mul * B0);
+    for (uint32_t k = tid; k < nb; k += blockDim.x) dst[k] = ((const uint16_t*)s_slot)[k];
+  } else {                                                       // an odd multiple has no alignment to speak of: byte by byte
+    uint8_t* dst = p.w_blob + (uint64_t)mul * B0;
+    for (uint32_t k = tid; k < mul * nb; k += blockDim.x) dst[k] = s_slot[k];
+  }
 }
 
 __global__ void spell_next_kernel(const SpellArgs p) {

@@ -177,7 +177,7 @@ class LanguageModel:
 
     def Tokenize(self, text):                                  # lm.NewTokenizer(alphabet).Tokenize
         raw = _enc(text)
-        buf = C.create_string_buffer(len(raw) * 2 + 64)
+        buf = C.create_string_buffer(len(raw) * 3 + 64)            # (an invalid byte is U+FFFD, three bytes, when that is a letter)
         n = _lib.lib().sg_lm_tokenize(self._h, raw, len(raw), buf, len(buf))
         return buf.value.split(b"\n") if n else []
 

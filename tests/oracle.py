@@ -337,7 +337,7 @@ class OracleLM:
 
     def tokenize(self, text):
         raw = _b(text)
-        buf = C.create_string_buffer(len(raw) * 2 + 64)
+        buf = C.create_string_buffer(len(raw) * 3 + 64)            # (an invalid byte is U+FFFD, three bytes, when that is a letter)
         n = lib().or_lm_tokenize(self._h, raw, len(raw), buf, len(buf))
         return buf.value.split(b"\n") if n else []
 
