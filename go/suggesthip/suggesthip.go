@@ -1110,3 +1110,40 @@ func (s *SpellChecker) ScoreSentences(lines []string) ([]float64, error) {
 	}
 	return out, nil
 }
+
+// StoreReference writes the index as the <name>.hd / <name>.dl pair the reference's NewFSBuilder opens (Writer.Commit,
+// pkg/index/indexer_writer.go:88-167; index.NewEncoder, pkg/index/codec.go:17-51): what the `indexer` command leaves behind.
+// device >= 0 encodes the posting lists on that GPU, device < 0 on the host; the bytes are the same (sg_index_store_reference).
+func (i *Index) StoreReference(hdPath, dlPath string, device int) error {
+	e := i.e
+	if err := e.retain(); err != nil {
+		return err
+	}
+	defer e.release()
+	chd, cdl := C.CString(hdPath), C.CString(dlPath)
+	defer C.free(unsafe.Pointer(chd))
+	defer C.free(unsafe.Pointer(cdl))
+	return ccall(func() C.int {
+		return C.sg_index_store_reference(e.h, chd, cdl, C.int(device))
+	})
+}
+
+// StoreCDBDictionary writes the dictionary the reference's services open beside the index (dictionary.BuildCDBDictionary,
+// pkg/dictionary/helpers.go:52-95): key = docID as 4 bytes little endian, value = the line (sg_dictionary_store_cdb).
+func StoreCDBDictionary(lines []string, cdbPath string) error {
+	var blob []byte
+	offs := make([]C.uint64_t, 1, len(lines)+1)
+	for _, l := range lines {
+		blob = append(blob, l...)
+		offs = append(offs, C.uint64_t(len(blob)))
+	}
+	var bp *C.uint8_t
+	if len(blob) > 0 {
+		bp = (*C.uint8_t)(unsafe.Pointer(&blob[0]))
+	}
+	cp := C.CString(cdbPath)
+	defer C.free(unsafe.Pointer(cp))
+	return ccall(func() C.int {
+		return C.sg_dictionary_store_cdb(bp, &offs[0], C.uint32_t(len(lines)), cp)
+	})
+}

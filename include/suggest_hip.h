@@ -82,6 +82,25 @@ int sg_index_build_ex(const uint8_t* utf8, const uint64_t* offs, uint32_t n_docs
  * pkg/index/codec.go:39-51) — into the same CSR.  `desc` must be the IndexDescription the files were built with. */
 int sg_index_load_reference(const char* hd_path, const char* dl_path, const sg_desc* desc, sg_index** out);
 
+/* Writer.Commit (pkg/index/indexer_writer.go:88-167) + index.NewEncoder (pkg/index/codec.go:17-51): saves the index as the
+ * <name>.hd / <name>.dl pair sg_index_load_reference and the reference's NewFSBuilder open — what the reference's `indexer`
+ * command leaves behind.  device >= 0 encodes the posting lists on that GPU (VB, skip blocks of 64, roaring after RunOptimize;
+ * DESIGN.md §4f), device < 0 with the host encoder; both write the same bytes.  Works on any handle — host-built, device-built,
+ * loaded from reference files — and needs no sg_index_upload: the device path stages the host CSR into memory of its own, on a
+ * stream of its own, frees it before it returns and touches no replica.  The terms are written segment ascending, then in the
+ * order of sg_index_lists (the reference's order is Go-map random).  SG_E_INVALID: a file cannot be written (the .dl is written
+ * first; a failed store may leave it behind); SG_E_UNSUPPORTED: the .dl would reach 4 GiB (PostingListPosition is a uint32: the
+ * reference would wrap it silently). */
+int sg_index_store_reference(sg_index* index, const char* hd_path, const char* dl_path, int device);
+/* dictionary.BuildCDBDictionary (pkg/dictionary/helpers.go:52-95): key = docID as 4 LE bytes, value = the line — the <name>.cdb
+ * the reference's services open beside the index.  docs[i] = utf8[offs[i]..offs[i+1]), records in docID order. */
+int sg_dictionary_store_cdb(const uint8_t* utf8, const uint64_t* offs, uint32_t n_docs, const char* cdb_path);
+/* Test hook like the other sg_debug_* entries (tools/index_store_timing.py reads it; bindings need not mirror it): seconds the
+ * calling thread's last sg_index_store_reference spent — out = {encoding: the kernels, or the host encoder, each with the position
+ * scan and without the list table both modes build first; staging: the kernels' input tables and the copies to and from the
+ * device, 0 on the host; building and writing the header; the whole call}.  No reference counterpart. */
+int sg_debug_index_store_times(double out[4]);
+
 /* Copies the CSR index into the HBM of `device` (one replica per GPU; per-process).  The first upload makes the primary
  * replica (the one sg_suggest_batch / sg_autocomplete_batch run on); uploading to a device that already holds a replica is
  * a no-op.  A device-built index (sg_index_build_device) whose first upload goes to the building device keeps the posting

@@ -537,6 +537,24 @@ inline std::shared_ptr<Builder> NewFSBuilder(const IndexDescription& d, int devi
   return std::make_shared<detail::FSBuilder>(d, device);
 }
 
+// Index — indexer.go:14-45 and the `indexer` command: indexes the dictionary and writes GetHeaderFile(), GetDocumentListFile()
+// (Writer.Commit, indexer_writer.go:88-167) and the dictionary as GetDictionaryFile() (BuildCDBDictionary, helpers.go:52-95) —
+// the files NewFSBuilder and OpenCDBDictionary open.  device >= 0: built and encoded on that GPU; device < 0: on the host.
+inline void Index(const IndexDescription& d, const std::shared_ptr<dictionary::Dictionary>& dict, int device = 0) {
+  std::string blob;
+  std::vector<uint64_t> offs(1, 0);
+  dict->Iterate([&](dictionary::Key, const dictionary::Value& w) {
+    blob += w;
+    offs.push_back(blob.size());
+  });
+  detail::DescC dc(d);
+  sg_index* h = nullptr;
+  NGramIndex::Check(sg_index_build_ex((const uint8_t*)blob.data(), offs.data(), (uint32_t)(offs.size() - 1), &dc.d, 0, device, &h));
+  NGramIndex ix(h);
+  NGramIndex::Check(sg_index_store_reference(h, d.GetHeaderFile().c_str(), d.GetDocumentListFile().c_str(), device));
+  NGramIndex::Check(sg_dictionary_store_cdb((const uint8_t*)blob.data(), offs.data(), (uint32_t)(offs.size() - 1), d.GetDictionaryFile().c_str()));
+}
+
 // ---------------------------------------------------------------------------------------------
 // Service — service.go:20-173
 // ---------------------------------------------------------------------------------------------

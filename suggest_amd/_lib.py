@@ -29,6 +29,7 @@ EXPORTS = [
     "sg_metric_tables_create", "sg_metric_tables_retain", "sg_metric_tables_release", "sg_suggest_batch_tables", "sg_suggest_batch_from", "sg_index_launch_stats", "sg_index_pipe_stats", "sg_index_pipe_volumes",
     "sg_lm_score_text_batch", "sg_lm_score_text_batch_device", "sg_lm_score_word_ids_batch",
     "sg_lm_build_device", "sg_lm_store_binary", "sg_debug_lm_build_hash_bits",
+    "sg_index_store_reference", "sg_dictionary_store_cdb", "sg_debug_index_store_times",
 ]
 SG_COUNT_LM_ERROR = 0xFFFFFFFC
 
@@ -66,6 +67,9 @@ def lib():
     if hasattr(L, "sg_index_build_ex"): L.sg_index_build_ex.argtypes = [vp, vp, u32, C.POINTER(SgDesc), u32, i32, C.POINTER(vp)]
     if hasattr(L, "sg_index_digest"): L.sg_index_digest.argtypes = [vp, vp]
     if hasattr(L, "sg_index_load_reference"): L.sg_index_load_reference.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(SgDesc), C.POINTER(vp)]
+    if hasattr(L, "sg_index_store_reference"): L.sg_index_store_reference.argtypes = [vp, C.c_char_p, C.c_char_p, i32]
+    if hasattr(L, "sg_dictionary_store_cdb"): L.sg_dictionary_store_cdb.argtypes = [vp, vp, u32, C.c_char_p]
+    if hasattr(L, "sg_debug_index_store_times"): L.sg_debug_index_store_times.argtypes = [vp]
     if hasattr(L, "sg_index_upload"): L.sg_index_upload.argtypes = [vp, i32]
     if hasattr(L, "sg_index_replicate"): L.sg_index_replicate.argtypes = [vp, vp, u32]
     if hasattr(L, "sg_index_tune"): L.sg_index_tune.argtypes = [vp, C.c_char_p, i32]

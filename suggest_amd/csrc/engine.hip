@@ -2917,3 +2917,4 @@ __global__ __launch_bounds__(64) void pairsort_test_kernel(const uint32_t* keys,
 }  // namespace sg
 
 #include "capi.inc"
+#include "index_store.inc"

@@ -241,7 +241,6 @@ void lm_level_packed(const HostLM& lm, uint32_t level, std::vector<uint64_t>& co
 // The minimal perfect hash the reference appends to .lm is NOT written: lm_load_binary does not read it (the dictionary gives
 // the words in id order), Go's RetrieveLMFromBinary does.
 int lm_store_binary(const HostLM& lm, const char* lm_path, const char* cdb_path, std::string& err) {
-  auto put_u32 = [](std::string& s, uint32_t v) { for (int i = 0; i < 4; i++) s.push_back((char)(v >> (8 * i))); };
   auto write_all = [&](const char* path, const std::string& head, const std::string& body) {
     std::ofstream f(path, std::ios::binary | std::ios::trunc);
     if (f) { f.write(head.data(), (std::streamsize)head.size()); f.write(body.data(), (std::streamsize)body.size()); f.close(); }
@@ -261,11 +260,18 @@ int lm_store_binary(const HostLM& lm, const char* lm_path, const char* cdb_path,
     }
     if (!write_all(lm_path, out, std::string())) return SG_E_INVALID;
   }
-  const size_t n = lm.words.size();
+  return cdb_write_dictionary(cdb_path, lm.words.size(), [&](size_t i, size_t* len) { *len = lm.words[i].size(); return lm.words[i].data(); }, err);
+}
+
+// The cdb writer of lm_store_binary and sg_dictionary_store_cdb: 256 (position, slots) header pairs, the records (key length 4,
+// value length, key = record number little endian, value) in record order, then per table twice as many (hash, position) slots as
+// it has records, filled from (hash >> 8) % slots on; hash = 5381, h * 33 ^ c over the key bytes.
+int cdb_write_dictionary(const char* path, size_t n, const std::function<const char*(size_t, size_t*)>& value, std::string& err) {
+  auto put_u32 = [](std::string& s, uint32_t v) { for (int i = 0; i < 4; i++) s.push_back((char)(v >> (8 * i))); };
   std::vector<uint32_t> hash(n), pos(n);
   std::string recs;
   uint64_t bytes = 2048;
-  for (const auto& w : lm.words) bytes += 12 + w.size() + 16;   // record + its two table slots
+  for (size_t i = 0; i < n; i++) { size_t len; value(i, &len); bytes += 12 + len + 16; }   // record + its two table slots
   if (bytes >= 0xFFFFFFFFull) { err = "dictionary too large for a cdb file (4 GiB)"; return SG_E_UNSUPPORTED; }
   recs.reserve((size_t)bytes);
   std::vector<uint32_t> per_table(256, 0);
@@ -274,8 +280,10 @@ int lm_store_binary(const HostLM& lm, const char* lm_path, const char* cdb_path,
     for (int j = 0; j < 4; j++) h = ((h << 5) + h) ^ (uint32_t)(((uint32_t)i >> (8 * j)) & 0xFFu);
     hash[i] = h;
     pos[i] = (uint32_t)(2048 + recs.size());
-    put_u32(recs, 4); put_u32(recs, (uint32_t)lm.words[i].size()); put_u32(recs, (uint32_t)i);
-    recs += lm.words[i];
+    size_t len;
+    const char* v = value(i, &len);
+    put_u32(recs, 4); put_u32(recs, (uint32_t)len); put_u32(recs, (uint32_t)i);
+    recs.append(v, len);
     per_table[h & 255u]++;
   }
   std::vector<std::vector<uint32_t>> members(256);
@@ -295,7 +303,12 @@ int lm_store_binary(const HostLM& lm, const char* lm_path, const char* cdb_path,
     for (const auto& e : tab) { put_u32(tables, e.first); put_u32(tables, e.second); }
     tpos += 8 * slots;
   }
-  if (!write_all(cdb_path, header, recs + tables)) return SG_E_INVALID;
+  std::ofstream f(path, std::ios::binary | std::ios::trunc);
+  if (f) {
+    f.write(header.data(), (std::streamsize)header.size()); f.write(recs.data(), (std::streamsize)recs.size());
+    f.write(tables.data(), (std::streamsize)tables.size()); f.close();
+  }
+  if (!f) { err = std::string("failed to write ") + path; return SG_E_INVALID; }
   return SG_OK;
 }
 

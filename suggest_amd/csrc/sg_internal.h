@@ -7,6 +7,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <functional>
 #include <string>
 #include <unordered_map>
 #include <vector>
@@ -75,6 +76,27 @@ bool term_string_key(const HostIndex& ix, const std::string& term, uint64_t* key
 void build_term_table(HostIndex& ix);
 // loads reference-built <name>.hd / <name>.dl (ref_index_reader.cpp)
 int load_reference_index(const char* hd_path, const char* dl_path, const sg_desc* desc, HostIndex& ix, std::string& err);
+
+// ---- saving an index as reference-format <name>.hd / <name>.dl (index_store.cpp; the device encoder: index_store.inc) ----
+struct StoreList {   // one non-empty (segment, term) list; the header order is segment ascending, then the order of sg_index_lists
+  uint64_t src;      // its first posting in HostIndex::postings
+  uint32_t term, segment;
+  uint32_t len;      // stored (de-duplicated) length
+  uint32_t raw;      // PostingListLen: with the repeats of `dups` (and of a marker entry, doc == 0xFFFFFFFF) — picks the codec
+  uint32_t dup_begin, dup_n;   // dups[dup_begin .. dup_begin + dup_n): this list's repeats, the marker entry left out
+};
+int store_lists(const HostIndex& ix, std::vector<StoreList>& out, std::string& err);
+// the plain host encoder: size[i] bytes of list i, back to back in `dl`
+void store_encode_host(const HostIndex& ix, const std::vector<StoreList>& lists, std::vector<uint32_t>& size, std::vector<uint8_t>& dl);
+// exclusive scan of the sizes in header order; SG_E_UNSUPPORTED where the .dl would reach 4 GiB (PostingListPosition is a uint32)
+int store_positions(const std::vector<uint32_t>& size, std::vector<uint32_t>& pos, uint64_t* total, std::string& err);
+// writes the .dl bytes and the gob header; seconds[0] = the header's share of the time (null: not wanted)
+int store_write_files(const HostIndex& ix, const std::vector<StoreList>& lists, const std::vector<uint32_t>& size,
+                      const std::vector<uint32_t>& pos, const uint8_t* dl, uint64_t dl_bytes, const char* hd_path, const char* dl_path,
+                      double* header_seconds, std::string& err);
+// D. J. Bernstein's constant database with key = record number as 4 bytes little endian (dictionary.BuildCDBDictionary,
+// pkg/dictionary/helpers.go:52-95): value(i, &len) = the bytes of record i
+int cdb_write_dictionary(const char* path, size_t n, const std::function<const char*(size_t, size_t*)>& value, std::string& err);
 
 // metric maths in IEEE double, evaluation order of pkg/metric/*.go (host copies; engine.hip has
 // the device twins)
