@@ -1147,3 +1147,46 @@ func StoreCDBDictionary(lines []string, cdbPath string) error {
 		return C.sg_dictionary_store_cdb(bp, &offs[0], C.uint32_t(len(lines)), cp)
 	})
 }
+
+// StoreBinary writes the spellchecker's language model as the <name>.lm / <name>.cdb pair `lm build-lm` leaves behind
+// (StoreBinaryLM, pkg/lm/binary.go:18-57).  mph adds the minimal perfect hash RetrieveLMFromBinary reads after the model
+// (pkg/mph/mph.go): the file the reference's spellchecker service opens (sg_lm_store_binary_ex).
+func (s *SpellChecker) StoreBinary(lmPath, cdbPath string, mph bool) error {
+	s.mu.RLock()
+	if s.closed {
+		s.mu.RUnlock()
+		return errClosed
+	}
+	C.sg_lm_retain(s.lm)
+	s.mu.RUnlock()
+	defer func() { C.sg_lm_release(s.lm); runtime.KeepAlive(s) }()
+	cl, cc := C.CString(lmPath), C.CString(cdbPath)
+	defer C.free(unsafe.Pointer(cl))
+	defer C.free(unsafe.Pointer(cc))
+	flags := C.uint32_t(0)
+	if mph {
+		flags = C.SG_LM_STORE_MPH
+	}
+	return ccall(func() C.int {
+		return C.sg_lm_store_binary_ex(s.lm, cl, cc, flags)
+	})
+}
+
+// StoreNGrams writes the model as the Google n-gram files <dir>/1-gm .. <dir>/N-gm (googleNGramFormatWriter.Write,
+// pkg/lm/ngram_writer.go:32-76): what the reference's ngram-count step writes and build-lm reads.  device >= 0 formats the
+// lines on that GPU, device < 0 on the host; the files are the same (sg_lm_store_google).
+func (s *SpellChecker) StoreNGrams(dir string, device int) error {
+	s.mu.RLock()
+	if s.closed {
+		s.mu.RUnlock()
+		return errClosed
+	}
+	C.sg_lm_retain(s.lm)
+	s.mu.RUnlock()
+	defer func() { C.sg_lm_release(s.lm); runtime.KeepAlive(s) }()
+	cd := C.CString(dir)
+	defer C.free(unsafe.Pointer(cd))
+	return ccall(func() C.int {
+		return C.sg_lm_store_google(s.lm, cd, C.int(device))
+	})
+}

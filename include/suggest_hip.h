@@ -280,10 +280,33 @@ int sg_lm_build_device(const uint8_t* text, uint64_t len, uint32_t order, const 
 /* Any model in the production format that sg_lm_load_binary reads: lm_path = nGramModel.Store (ngram_model.go:100-121,
  * packed_array.go:96-116) — "0.0.2", the order byte, per level "container-bytes value-bytes total\n" and the little-endian
  * containers and values of sg_lm_level; cdb_path = BuildCDBDictionary (pkg/dictionary/helpers.go:52-100) — key = word id as 4
- * bytes little endian, value = the word.  The minimal perfect hash the reference appends to the .lm (buildMPH, binary.go:200-210) is NOT
- * written: the pair reloads here, Go's RetrieveLMFromBinary needs that section.  A file that cannot be written is SG_E_INVALID with
- * its path in the message; the .lm is written first, so a failed store may leave it (or a partial file) behind. */
+ * bytes little endian, value = the word.  sg_lm_store_binary writes the model section alone, which reloads here; the minimal
+ * perfect hash the reference appends to the .lm (buildMPH, binary.go:200-210) and Go's RetrieveLMFromBinary reads straight after
+ * the model (table.Load, binary.go:59-98) is written by sg_lm_store_binary_ex with SG_LM_STORE_MPH: mph.Build + mph.Store
+ * (pkg/mph/mph.go:40-145,159-192) restated on the host, bucket order of Go 1.14's sort.Slice included — u32 n, n values, u32 n,
+ * n auxiliary i32, little endian; an empty dictionary gives the two zero lengths.  A dictionary that lists a word twice, or a
+ * bucket no seed below 2^31 places, is SG_E_UNSUPPORTED before a file is touched.  flags == 0 is sg_lm_store_binary; an unknown
+ * flag is SG_E_INVALID.  A file that cannot be written is SG_E_INVALID with its path in the message; the .lm is written first,
+ * so a failed store may leave it (or a partial file) behind. */
+#define SG_LM_STORE_MPH 1u
 int sg_lm_store_binary(const sg_lm* lm, const char* lm_path, const char* cdb_path);
+int sg_lm_store_binary_ex(const sg_lm* lm, const char* lm_path, const char* cdb_path, uint32_t flags);
+/* googleNGramFormatWriter.Write (pkg/lm/ngram_writer.go:12,32-76) for a model that is already counted: <out_dir>/<k>-gm for
+ * k = 1 .. order, lines "w1 .. wk\tcount\n" — what the reference's ngram-count step writes and its build-lm step reads.  1-gm has
+ * a line per word in id order, k-gm is in level entry order (by context entry, then by word id); the reference's order is Go-map
+ * random, so any order is a valid file, and this one makes sg_lm_load_google_ex(out_dir, id_order = 0) give the model back array
+ * for array.  device >= 0 formats the lines on that GPU (a size pass, a 64-bit prefix sum, a write pass; a stream and memory of
+ * the call's own, nothing of scoring or Predict touched, a model resident on another device no obstacle); device < 0 runs the
+ * plain host writer; both write identical files.  Refused with SG_E_UNSUPPORTED and the level in the message, before a file is
+ * created: a level with entries whose context is missing from the level below (their leading words are not recoverable), an
+ * entry that ends in the unknown word, a level 1 that is not one entry per word in id order.  A model from sg_lm_build_device
+ * has none of these.  A file that cannot be created or written is SG_E_INVALID with its path. */
+int sg_lm_store_google(const sg_lm* lm, const char* out_dir, int device);
+/* Test hooks.  sg_debug_lm_store_slice_bytes, process-wide (like sg_debug_lm_build_hash_bits): the device writer formats a level
+ * in slices of entries whose text fits 256 MiB; this lowers the budget, 0 restores it.  sg_debug_lm_store_times: seconds of the
+ * calling thread's last sg_lm_store_google — staging, kernels (host writer: formatting), copy-back, file writes. */
+int sg_debug_lm_store_slice_bytes(uint32_t bytes);
+int sg_debug_lm_store_times(double out[4]);
 /* Test hook, process-wide (like sg_debug_poison): sg_lm_build_device keeps only the low `bits` bits of a word's hash, 0 = all 64 —
  * words then collide in its vocabulary table and are told apart by their bytes alone. */
 int sg_debug_lm_build_hash_bits(uint32_t bits);

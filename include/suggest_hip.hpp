@@ -694,6 +694,13 @@ class LanguageModel {  // language_model.go:8-14 over NewGoogleNGramReader(order
   }
   size_t Size() const { return sg_lm_num_words(h_); }
 
+  // StoreBinaryLM (pkg/lm/binary.go:18-57): <name>.lm + <name>.cdb; mph adds the minimal perfect hash RetrieveLMFromBinary reads
+  void StoreBinary(const std::string& lmPath, const std::string& cdbPath, bool mph = false) const {
+    NGramIndex::Check(sg_lm_store_binary_ex(h_, lmPath.c_str(), cdbPath.c_str(), mph ? SG_LM_STORE_MPH : 0u));
+  }
+  // googleNGramFormatWriter.Write (ngram_writer.go:32-76): <dir>/1-gm .. <dir>/N-gm; device >= 0 formats the lines on that GPU
+  void StoreNGrams(const std::string& dir, int device = -1) const { NGramIndex::Check(sg_lm_store_google(h_, dir.c_str(), device)); }
+
   // ScoreSentence for a batch of token lists on the GPU `device` (sg_lm_score_word_ids_batch)
   std::vector<double> ScoreSentences(const std::vector<std::vector<std::string>>& sentences, int device = 0) const {
     std::vector<WordID> ids;

@@ -30,7 +30,9 @@ EXPORTS = [
     "sg_lm_score_text_batch", "sg_lm_score_text_batch_device", "sg_lm_score_word_ids_batch",
     "sg_lm_build_device", "sg_lm_store_binary", "sg_debug_lm_build_hash_bits",
     "sg_index_store_reference", "sg_dictionary_store_cdb", "sg_debug_index_store_times",
+    "sg_lm_store_binary_ex", "sg_lm_store_google", "sg_debug_lm_store_slice_bytes", "sg_debug_lm_store_times",
 ]
+SG_LM_STORE_MPH = 1
 SG_COUNT_LM_ERROR = 0xFFFFFFFC
 
 
@@ -107,6 +109,10 @@ def lib():
     if hasattr(L, "sg_lm_build_google"): L.sg_lm_build_google.argtypes = [C.c_char_p, u64, u32, C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), u32, C.POINTER(C.c_char_p), u32, C.c_char_p]
     if hasattr(L, "sg_lm_build_device"): L.sg_lm_build_device.argtypes = [vp, u64, u32, C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), u32, C.POINTER(C.c_char_p), u32, i32, i32, C.POINTER(vp)]
     if hasattr(L, "sg_lm_store_binary"): L.sg_lm_store_binary.argtypes = [vp, C.c_char_p, C.c_char_p]
+    if hasattr(L, "sg_lm_store_binary_ex"): L.sg_lm_store_binary_ex.argtypes = [vp, C.c_char_p, C.c_char_p, u32]
+    if hasattr(L, "sg_lm_store_google"): L.sg_lm_store_google.argtypes = [vp, C.c_char_p, i32]
+    if hasattr(L, "sg_debug_lm_store_slice_bytes"): L.sg_debug_lm_store_slice_bytes.argtypes = [u32]
+    if hasattr(L, "sg_debug_lm_store_times"): L.sg_debug_lm_store_times.argtypes = [vp]
     if hasattr(L, "sg_debug_lm_build_hash_bits"): L.sg_debug_lm_build_hash_bits.argtypes = [u32]
     if hasattr(L, "sg_lm_retain"): L.sg_lm_retain.argtypes = [vp]
     if hasattr(L, "sg_lm_retain"): L.sg_lm_retain.restype = None

@@ -2319,15 +2319,18 @@ int sg_lm_build_device(const uint8_t* text, uint64_t len, uint32_t order, const 
   SG_GUARD_END(SG_RC)
 }
 
-int sg_lm_store_binary(const sg_lm* lm, const char* lm_path, const char* cdb_path) {
+int sg_lm_store_binary_ex(const sg_lm* lm, const char* lm_path, const char* cdb_path, uint32_t flags) {
   SG_GUARD_BEGIN
   if (!lm || !lm_path || !cdb_path) { set_error("null argument"); return SG_E_INVALID; }
+  if (flags & ~(uint32_t)SG_LM_STORE_MPH) { set_error("unknown flag: SG_LM_STORE_MPH is the only one"); return SG_E_INVALID; }
   std::string err;
-  const int rc = lm_store_binary(lm->host, lm_path, cdb_path, err);
+  const int rc = lm_store_binary(lm->host, lm_path, cdb_path, flags, err);
   if (rc) set_error(err);
   return rc;
   SG_GUARD_END(SG_RC)
 }
+
+int sg_lm_store_binary(const sg_lm* lm, const char* lm_path, const char* cdb_path) { return sg_lm_store_binary_ex(lm, lm_path, cdb_path, 0); }
 
 int sg_debug_lm_build_hash_bits(uint32_t bits) {
   if (bits > 64u) { set_error("hash bits: 0 (all 64) .. 64"); return SG_E_INVALID; }

@@ -2918,3 +2918,4 @@ __global__ __launch_bounds__(64) void pairsort_test_kernel(const uint32_t* keys,
 
 #include "capi.inc"
 #include "index_store.inc"
+#include "lm_store.inc"

@@ -238,9 +238,13 @@ void lm_level_packed(const HostLM& lm, uint32_t level, std::vector<uint64_t>& co
 // "container-bytes value-bytes total\n" and the two little-endian arrays of lm_level_packed.  .cdb: D. J. Bernstein's constant
 // database, key = word id as 4 bytes little endian, value = the word, records in id order — 256 (position, slots) header pairs,
 // the records, then per table twice as many (hash, position) slots as it has records, filled from (hash >> 8) % slots on.
-// The minimal perfect hash the reference appends to .lm is NOT written: lm_load_binary does not read it (the dictionary gives
-// the words in id order), Go's RetrieveLMFromBinary does.
-int lm_store_binary(const HostLM& lm, const char* lm_path, const char* cdb_path, std::string& err) {
+// The minimal perfect hash the reference appends to .lm (table.Load in RetrieveLMFromBinary) is written with SG_LM_STORE_MPH
+// (mph_section, lm_store.cpp), built before a file is touched; lm_load_binary does not read it: the dictionary gives the words
+// in id order.
+int lm_store_binary(const HostLM& lm, const char* lm_path, const char* cdb_path, uint32_t flags, std::string& err) {
+  std::string mph;
+  if (flags & SG_LM_STORE_MPH)
+    if (int rc = mph_section(lm.words, mph, err)) return rc;
   auto write_all = [&](const char* path, const std::string& head, const std::string& body) {
     std::ofstream f(path, std::ios::binary | std::ios::trunc);
     if (f) { f.write(head.data(), (std::streamsize)head.size()); f.write(body.data(), (std::streamsize)body.size()); f.close(); }
@@ -258,7 +262,7 @@ int lm_store_binary(const HostLM& lm, const char* lm_path, const char* cdb_path,
       for (const std::vector<uint64_t>* arr : {&c, &v})
         for (uint64_t x : *arr) for (int i = 0; i < 8; i++) out.push_back((char)(x >> (8 * i)));
     }
-    if (!write_all(lm_path, out, std::string())) return SG_E_INVALID;
+    if (!write_all(lm_path, out, mph)) return SG_E_INVALID;
   }
   return cdb_write_dictionary(cdb_path, lm.words.size(), [&](size_t i, size_t* len) { *len = lm.words[i].size(); return lm.words[i].data(); }, err);
 }

@@ -141,7 +141,7 @@ int lm_load_google(const char* dir, uint32_t order, const char* start_symbol, co
                    int id_order, HostLM& lm, std::string& err);
 int lm_load_binary(const char* lm_path, const char* cdb_path, const char* start_symbol, const char* end_symbol,
                    const std::vector<std::string>& alphabet, HostLM& lm, std::string& err);
-int lm_store_binary(const HostLM& lm, const char* lm_path, const char* cdb_path, std::string& err);
+int lm_store_binary(const HostLM& lm, const char* lm_path, const char* cdb_path, uint32_t flags, std::string& err);   // flags: SG_LM_STORE_*
 void lm_level_packed(const HostLM& lm, uint32_t level, std::vector<uint64_t>& containers, std::vector<uint64_t>& values, uint32_t* total);
 int lm_build_google_files(const uint8_t* text, size_t n, uint32_t order, const char* start_symbol, const char* end_symbol,
                           const std::vector<std::string>& alphabet, const std::vector<std::string>& separators, const char* out_dir,
@@ -155,6 +155,26 @@ uint32_t lm_next_count(const HostLM& lm, const LmNext& nx, uint32_t word);
 double lm_next_score(const HostLM& lm, const LmNext& nx, uint32_t word);
 void lm_tokenize(const HostLM& lm, const uint8_t* text, size_t n, std::vector<std::string>& out);
 void set_error(const std::string& msg);
+
+// ---- the model's other two reference formats (lm_store.cpp; the device n-gram writer: lm_store.inc) ----
+uint32_t mph_hash(uint32_t seed, const std::string& word);                  // mph.go:236-247
+// mph.Build (pkg/mph/mph.go:40-145) over the words in id order: Get(word) = values[..] is its id
+int mph_build(const std::vector<std::string>& words, std::vector<uint32_t>& values, std::vector<int32_t>& auxiliary, std::string& err);
+int mph_section(const std::vector<std::string>& words, std::string& out, std::string& err);   // mph.Store's bytes
+constexpr uint32_t kGmSliceBytes = 256u << 20;      // text of a level formatted, copied back and appended to its file at a time
+uint32_t lm_gm_slice_budget(int64_t set);           // the budget in force; set >= 0: the test hook's value first (0 = kGmSliceBytes)
+int lm_gm_check(const HostLM& lm, std::string& err);                        // SG_E_UNSUPPORTED: a model that cannot be spelled as lines
+void lm_gm_parents(const LmLevel& lv, std::vector<uint32_t>& parent);       // parent[e] = the bucket that holds entry e
+std::string lm_gm_path(const char* out_dir, size_t k);
+struct GmFile {                                     // one <k>-gm being written; errors carry the path
+  FILE* f = nullptr;
+  std::string path;
+  ~GmFile();
+  int open(const std::string& p, std::string& err);
+  int write(const void* data, size_t n, std::string& err);
+  int close(std::string& err);
+};
+int lm_store_google_host(const HostLM& lm, const char* out_dir, double seconds[4], std::string& err);
 
 // Values from outside the program (environment, sg_index_tune): a whole string, base 10, that fits an int32 — or nothing.
 inline bool parse_int32(const char* s, int32_t* out) {

@@ -6,6 +6,7 @@ pkg/spellchecker.SpellChecker.Predict over the MI355X engine.
   sc.Predict("i am sa", 5, 0.5)              # -> ["sam", ...]            (spellchecker.go:40-92)
 """
 import ctypes as C
+import os
 
 import numpy as np
 
@@ -14,6 +15,11 @@ from .index import IndexDescription, NGramIndex, _c_desc, _enc, pack_strings
 
 # cmd/spellchecker/cmd/eval.go:16-23
 SPELLCHECKER_INDEX = dict(name="words", ngram_size=3, wrap=("^", "$"), pad="$", alphabet=("english", "russian", "numbers", "$^'"))
+
+
+# save_ngrams(device=None): the writer profiles/lm_store_timing.json shows faster at both sizes timed — the device writer, on
+# GPU 0 like from_corpus: 0.011 s against 0.071 s for a 1 M-token model, 0.060 s against 0.261 s for a 4 M-token one
+DEFAULT_NGRAM_DEVICE = 0
 
 
 class LanguageModel:
@@ -74,10 +80,19 @@ class LanguageModel:
         self.order = int(L.sg_lm_order(h))
         return self
 
-    def save(self, binary, dictionary):
+    def save(self, binary, dictionary, mph=False):
         """Write the model as <binary> (.lm, nGramModel.Store) and <dictionary> (.cdb, BuildCDBDictionary): the pair
-        LanguageModel(binary=..., dictionary=...) loads.  The reference's MPH section is not written (sg_lm_store_binary)."""
-        _lib.check(_lib.lib().sg_lm_store_binary(self._h, _enc(binary), _enc(dictionary)))
+        LanguageModel(binary=..., dictionary=...) loads.  mph=True appends the minimal perfect hash the reference's
+        RetrieveLMFromBinary reads after the model (sg_lm_store_binary_ex with SG_LM_STORE_MPH): the file Go opens."""
+        _lib.check(_lib.lib().sg_lm_store_binary_ex(self._h, _enc(binary), _enc(dictionary), _lib.SG_LM_STORE_MPH if mph else 0))
+
+    def save_ngrams(self, directory, device=None):
+        """Write the model as Google n-gram files <directory>/{1..order}-gm (sg_lm_store_google): what the reference's build-lm
+        step reads, and what LanguageModel(directory, id_order="lines") loads back array for array.  device >= 0 formats the
+        lines on that GPU, -1 runs the host writer; both write identical files.  None: GPU 0 — the device writer is 4 to 6 times
+        faster than the host writer at both sizes timed (profiles/lm_store_timing.json); without a GPU pass -1."""
+        dev = DEFAULT_NGRAM_DEVICE if device is None else int(device)
+        _lib.check(_lib.lib().sg_lm_store_google(self._h, _enc(os.fspath(directory)), dev))
 
     def close(self):
         if getattr(self, "_h", None):
