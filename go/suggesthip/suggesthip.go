@@ -1190,3 +1190,215 @@ func (s *SpellChecker) StoreNGrams(dir string, device int) error {
 		return C.sg_lm_store_google(s.lm, cd, C.int(device))
 	})
 }
+
+// Sharded is a dictionary sharded by docID range behind one handle (sg_sharded): for dictionaries past one Index's limits
+// (2^29 documents per upload, 2^26 per device build, one GPU's HBM per replica).  One call searches every shard and the
+// per-shard top-k rows are merged on the GPU under the reference's order (score desc, docID asc); Keys are dictionary-wide
+// docIDs.  Batch calls only: thin wrappers, no coalescing.  With documents that repeat a term the reference's secondary
+// duplicate rows can differ from an unsharded index's (suggest_hip.h).
+type Sharded struct {
+	mu     sync.RWMutex
+	h      *C.sg_sharded
+	closed bool
+}
+
+func newSharded(h *C.sg_sharded) *Sharded {
+	s := &Sharded{h: h}
+	runtime.SetFinalizer(s, func(s *Sharded) { s.Close() })
+	return s
+}
+
+// BuildSharded cuts the dictionary into nShards contiguous docID ranges, builds each (onDevice: on its own GPU) and uploads
+// shard s to devices[s % len(devices)] (sg_sharded_build).
+func BuildSharded(dict dictionary.Dictionary, d suggest.IndexDescription, nShards int, devices []int, onDevice bool) (*Sharded, error) {
+	var blob []byte
+	offs := []C.uint64_t{0}
+	if err := dict.Iterate(func(_ dictionary.Key, v dictionary.Value) error {
+		blob = append(blob, v...)
+		offs = append(offs, C.uint64_t(len(blob)))
+		return nil
+	}); err != nil {
+		return nil, err
+	}
+	if len(devices) == 0 {
+		devices = []int{0}
+	}
+	devs := make([]C.int, len(devices))
+	for i, dev := range devices {
+		devs[i] = C.int(dev)
+	}
+	arr, freeAlpha := cstrings(d.Alphabet)
+	defer freeAlpha()
+	w0, w1, pad := C.CString(d.Wrap[0]), C.CString(d.Wrap[1]), C.CString(d.Pad)
+	defer C.free(unsafe.Pointer(w0))
+	defer C.free(unsafe.Pointer(w1))
+	defer C.free(unsafe.Pointer(pad))
+	desc := (*C.sg_desc)(C.malloc(C.size_t(unsafe.Sizeof(C.sg_desc{}))))
+	defer C.free(unsafe.Pointer(desc))
+	desc.ngram_size, desc.wrap_start, desc.wrap_end, desc.pad = C.uint32_t(d.NGramSize), w0, w1, pad
+	desc.alphabet, desc.n_alphabet = arr, C.uint32_t(len(d.Alphabet))
+	var bp *C.uint8_t
+	if len(blob) > 0 {
+		bp = (*C.uint8_t)(unsafe.Pointer(&blob[0]))
+	}
+	buildDevice := C.int(-1)
+	if onDevice {
+		buildDevice = 0
+	}
+	var h *C.sg_sharded
+	if err := ccall(func() C.int {
+		return C.sg_sharded_build(bp, &offs[0], C.uint32_t(len(offs)-1), desc, C.uint32_t(nShards), &devs[0], C.uint32_t(len(devs)), buildDevice, &h)
+	}); err != nil {
+		return nil, err
+	}
+	return newSharded(h), nil
+}
+
+// AdoptSharded takes shards that are already built and uploaded (sg_sharded_adopt retains each): docLo[s] = the dictionary
+// docID of shard s's document 0.
+func AdoptSharded(shards []*Index, docLo []uint64) (*Sharded, error) {
+	if len(shards) == 0 || len(shards) != len(docLo) {
+		return nil, errors.New("suggesthip: one docLo per shard, one shard at least")
+	}
+	hs := make([]*C.sg_index, len(shards))
+	lo := make([]C.uint64_t, len(shards))
+	for i, ix := range shards {
+		if err := ix.e.retain(); err != nil {
+			for _, prev := range shards[:i] {
+				prev.e.release()
+			}
+			return nil, err
+		}
+		hs[i], lo[i] = ix.e.h, C.uint64_t(docLo[i])
+	}
+	var h *C.sg_sharded
+	err := ccall(func() C.int {
+		return C.sg_sharded_adopt(&hs[0], &lo[0], C.uint32_t(len(hs)), &h)
+	})
+	for _, ix := range shards {
+		ix.e.release()
+	}
+	runtime.KeepAlive(shards)
+	if err != nil {
+		return nil, err
+	}
+	return newSharded(h), nil
+}
+
+func (s *Sharded) use() error {
+	s.mu.RLock()
+	defer s.mu.RUnlock()
+	if s.closed {
+		return errClosed
+	}
+	C.sg_sharded_retain(s.h)
+	return nil
+}
+
+// SuggestBatch is Index.SuggestBatch over every shard (sg_sharded_suggest_batch): status[q] != 0 marks a query without an
+// answer (an SG_COUNT_* flag), the other rows are valid.  Metrics with a device twin only.
+func (s *Sharded) SuggestBatch(queries []string, similarity float64, m metric.Metric, k int) ([][]suggest.Candidate, []uint32, error) {
+	code, known := metricCode(m)
+	if !known {
+		return nil, nil, errors.New("suggesthip: a sharded search takes jaccard, cosine, dice, exact or overlap")
+	}
+	n := len(queries)
+	if n == 0 || k <= 0 {
+		return nil, nil, nil
+	}
+	var blob []byte
+	offs := []C.uint64_t{0}
+	for _, q := range queries {
+		blob = append(blob, q...)
+		offs = append(offs, C.uint64_t(len(blob)))
+	}
+	ids := make([]C.uint32_t, n*k)
+	scores := make([]C.double, n*k)
+	counts := make([]C.uint32_t, n)
+	var bp *C.uint8_t
+	if len(blob) > 0 {
+		bp = (*C.uint8_t)(unsafe.Pointer(&blob[0]))
+	}
+	if err := s.use(); err != nil {
+		return nil, nil, err
+	}
+	err := ccall(func() C.int {
+		return C.sg_sharded_suggest_batch(s.h, bp, &offs[0], C.uint32_t(n), code, C.double(similarity), C.uint32_t(k), &ids[0], &scores[0], &counts[0])
+	})
+	C.sg_sharded_release(s.h)
+	runtime.KeepAlive(s)
+	if err != nil {
+		return nil, nil, err
+	}
+	out := make([][]suggest.Candidate, n)
+	status := make([]uint32, n)
+	for q := 0; q < n; q++ {
+		c := uint32(counts[q])
+		if c >= C.SG_COUNT_LM_ERROR {
+			status[q] = c
+			continue
+		}
+		out[q] = make([]suggest.Candidate, c)
+		for j := uint32(0); j < c; j++ {
+			out[q][j] = suggest.Candidate{Key: uint32(ids[q*k+int(j)]), Score: float64(scores[q*k+int(j)])}
+		}
+	}
+	return out, status, nil
+}
+
+// AutocompleteBatch returns per query the `limit` smallest dictionary docIDs that complete it (sg_sharded_autocomplete_batch);
+// status as SuggestBatch.
+func (s *Sharded) AutocompleteBatch(queries []string, limit int) ([][]suggest.Candidate, []uint32, error) {
+	n := len(queries)
+	if n == 0 || limit <= 0 {
+		return nil, nil, nil
+	}
+	var blob []byte
+	offs := []C.uint64_t{0}
+	for _, q := range queries {
+		blob = append(blob, q...)
+		offs = append(offs, C.uint64_t(len(blob)))
+	}
+	ids := make([]C.uint32_t, n*limit)
+	counts := make([]C.uint32_t, n)
+	var bp *C.uint8_t
+	if len(blob) > 0 {
+		bp = (*C.uint8_t)(unsafe.Pointer(&blob[0]))
+	}
+	if err := s.use(); err != nil {
+		return nil, nil, err
+	}
+	err := ccall(func() C.int {
+		return C.sg_sharded_autocomplete_batch(s.h, bp, &offs[0], C.uint32_t(n), C.uint32_t(limit), &ids[0], &counts[0])
+	})
+	C.sg_sharded_release(s.h)
+	runtime.KeepAlive(s)
+	if err != nil {
+		return nil, nil, err
+	}
+	out := make([][]suggest.Candidate, n)
+	status := make([]uint32, n)
+	for q := 0; q < n; q++ {
+		c := uint32(counts[q])
+		if c >= C.SG_COUNT_LM_ERROR {
+			status[q] = c
+			continue
+		}
+		out[q] = make([]suggest.Candidate, c)
+		for j := uint32(0); j < c; j++ {
+			out[q][j] = suggest.Candidate{Key: uint32(ids[q*limit+int(j)])}
+		}
+	}
+	return out, status, nil
+}
+
+// Close drops the handle's reference: the shards go when the calls in flight have returned.
+func (s *Sharded) Close() error {
+	s.mu.Lock()
+	defer s.mu.Unlock()
+	if !s.closed {
+		s.closed = true
+		C.sg_sharded_release(s.h)
+	}
+	return nil
+}

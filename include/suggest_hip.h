@@ -73,7 +73,8 @@ int sg_index_build_device(const uint8_t* utf8, const uint64_t* offs, uint32_t n_
 
 /* Either builder (device < 0: host) with at least `min_segments` cardinality segments: the shards of a dictionary split by
  * docID range (suggest_amd/distributed.py) agree on the global number, so that every shard clips the
- * window [MinY, MaxY] at the same segment (suggester.go:57-59) as the unsharded index would. */
+ * window [MinY, MaxY] at the same segment (suggester.go:57-59) as the unsharded index would.  This builds ONE shard:
+ * sg_sharded_build builds, uploads and searches all of them behind one handle; sg_sharded_adopt takes shards built here. */
 int sg_index_build_ex(const uint8_t* utf8, const uint64_t* offs, uint32_t n_docs, const sg_desc* desc, uint32_t min_segments,
                       int device, sg_index** out);
 
@@ -105,7 +106,8 @@ int sg_debug_index_store_times(double out[4]);
  * replica (the one sg_suggest_batch / sg_autocomplete_batch run on); uploading to a device that already holds a replica is
  * a no-op.  A device-built index (sg_index_build_device) whose first upload goes to the building device keeps the posting
  * store where the build left it (no D2H + H2D round trip).  Safe to call concurrently.  SG_E_UNSUPPORTED: the packed
- * posting store numbers documents below 2^29 (shard larger dictionaries by docID range: sg_index_build_ex). */
+ * posting store numbers documents below 2^29 (a larger dictionary is sharded by docID range behind one handle:
+ * sg_sharded_build, below). */
 int sg_index_upload(sg_index* index, int device);
 
 /* Multi-GPU (BASELINE north_star: "query batches shard naturally across the 8 GPUs of one node"): ONE host
@@ -146,6 +148,70 @@ int sg_suggest_batch_multi(sg_index* index, const uint8_t* q_utf8, const uint64_
                            double similarity, uint32_t k, uint32_t* out_ids, double* out_scores, uint32_t* out_counts);
 int sg_autocomplete_batch_multi(sg_index* index, const uint8_t* q_utf8, const uint64_t* q_offs, uint32_t n_q,
                                 uint32_t limit, uint32_t* out_ids, uint32_t* out_counts);
+
+/* ---- a dictionary sharded by docID range behind one handle ---------------------------
+ * For dictionaries past one index's limits — 2^29 documents per upload, 2^26 per device build, one GPU's HBM per replica: W
+ * shards, each an sg_index over the documents [doc_lo, doc_lo + n) under local docIDs, on one GPU or several.  One call searches
+ * the whole batch on every shard and a merge launch (sg_shard_merge_kernel) combines the per-shard top-k rows on the device of
+ * shard 0 under the reference's total order (score desc, docID asc; collector.go:20-26); rows come back with dictionary-wide
+ * docIDs, which may use all of uint32 while every shard stays below 2^29 documents.  A query that any shard flags (SG_COUNT_*)
+ * stays flagged, its row zeroed; slots past a row's count are zero.
+ * That order is total, so the rows equal the unsharded index's for dictionaries without documents that repeat a term.  With such
+ * documents the primary entries are the same, but the reference's SECONDARY duplicate rows depend on the relative
+ * lengths of posting lists, which differ inside a shard: those rows can differ from the unsharded index's (they always equal the
+ * merge of the shards' own rows).
+ * Concurrency: the host-buffer calls of one handle share its streams and staging and take turns behind a mutex in the handle;
+ * the device-resident call writes nothing of the handle and may run from any number of threads and streams at once. */
+typedef struct sg_sharded sg_sharded;
+#define SG_MAX_SHARDS 64u        /* a design limit: 8 GPUs with 8 shards each */
+
+/* Cuts docs [0, n_docs) into n_shards (1 .. SG_MAX_SHARDS) contiguous docID ranges, builds every non-empty one with the global
+ * number of cardinality segments (the shards short of it are built again with min_segments, as sg_index_build_ex does), and
+ * uploads shard s to devices[s % n_devices].  Ranges differ in size by at most one, by the rule of distributed.shard_bounds: the
+ * first n_docs % n_shards ranges hold one more.  A range without documents (n_shards > n_docs) is not built: it adds no rows and
+ * no flag (range 0 always is, so that an empty dictionary answers like an empty index).  build_device >= 0: the path of
+ * sg_index_build_device on the shard's own device; < 0: the host builder.  An entry of `devices` is a lane: the shards of one
+ * lane are searched one after the other on one stream, lanes side by side; a device listed twice makes two lanes (only
+ * useful to exercise the path for rows from another device on a one-GPU box). */
+int sg_sharded_build(const uint8_t* utf8, const uint64_t* offs, uint32_t n_docs, const sg_desc* desc, uint32_t n_shards,
+                     const int* devices, uint32_t n_devices, int build_device, sg_sharded** out);
+
+/* Adopts handles that are already built and uploaded, and retains each: doc_lo[s] = the dictionary docID of shard s's document
+ * 0.  For shards loaded with sg_index_load_reference, or built elsewhere.  A lane per device.  SG_E_INVALID: n_shards outside
+ * 1 .. SG_MAX_SHARDS, doc_lo that does not ascend, a range doc_lo[s] + n_docs_s that reaches into the next shard's or passes
+ * 2^32, a handle that is not uploaded, shards whose n_segments or descriptions differ. */
+int sg_sharded_adopt(sg_index* const* shards, const uint64_t* doc_lo, uint32_t n_shards, sg_sharded** out);
+
+void sg_sharded_retain(sg_sharded* sharded);
+void sg_sharded_release(sg_sharded* sharded);
+/* The shards that stand, in docID order: fills up to cap entries of out_doc_lo / out_devices (either may be NULL), returns their number. */
+uint32_t sg_sharded_shards(const sg_sharded* sharded, uint64_t* out_doc_lo, int* out_devices, uint32_t cap);
+
+/* sg_suggest_batch over every shard, merged: host buffers, synchronous.  The queries are uploaded once per device; the batch
+ * goes through in slices of queries whose [shard][query][k] block of ids, scores and counts stays within 256 MiB; rows of a
+ * device other than shard 0's are copied there asynchronously behind their searches and ordered by events. */
+int sg_sharded_suggest_batch(sg_sharded* sharded, const uint8_t* q_utf8, const uint64_t* q_offs, uint32_t n_q, int metric,
+                             double similarity, uint32_t k, uint32_t* out_ids, double* out_scores, uint32_t* out_counts);
+/* The same on buffers resident in HBM, asynchronous on `stream` — searches and merge are enqueued there, the shards' rows stay
+ * in HBM.  Needs every shard on the device that owns the buffers: SG_E_UNSUPPORTED otherwise. */
+int sg_sharded_suggest_batch_device(sg_sharded* sharded, const void* d_q_utf8, const void* d_q_offs, uint32_t n_q, int metric,
+                                    double similarity, uint32_t k, void* d_out_ids, void* d_out_scores, void* d_out_counts,
+                                    void* stream);
+/* sg_autocomplete_batch over every shard: the shards own ascending docID ranges, so the merged row is their rows one after the
+ * other, cut at `limit`. */
+int sg_sharded_autocomplete_batch(sg_sharded* sharded, const uint8_t* q_utf8, const uint64_t* q_offs, uint32_t n_q,
+                                  uint32_t limit, uint32_t* out_ids, uint32_t* out_counts);
+/* Test hooks (bindings need not mirror them).  sg_debug_shard_slice_bytes, process-wide: lowers the 256 MiB budget of the
+ * [shard][query][k] block — a slice holds max(1, budget / (shards * (k * 12 + 4))) queries, k * 4 + 4 for autocomplete —
+ * 0 restores it.  sg_debug_shard_merge: the merge launch alone over host arrays laid out as that block — ids, scores
+ * [n_shards][n_q][k] with local docIDs, counts [n_shards][n_q], doc_lo [n_shards]; autocomplete != 0: no scores (scores and
+ * out_scores may be NULL); sg_debug_shard_merge_time: the milliseconds between two events around the launch of the calling
+ * thread's last sg_debug_shard_merge (tools/shard_timing.py reads it). */
+int sg_debug_shard_slice_bytes(uint32_t bytes);
+int sg_debug_shard_merge(int device, const uint32_t* ids, const double* scores, const uint32_t* counts, const uint64_t* doc_lo,
+                         uint32_t n_shards, uint32_t n_q, uint32_t k, int autocomplete, uint32_t* out_ids, double* out_scores,
+                         uint32_t* out_counts);
+int sg_debug_shard_merge_time(double* out_ms);
 
 /* Suggester.Suggest / Autocomplete.Autocomplete as the reference calls them: ONE query per call, from many goroutines at
  * once (pkg/suggest/suggester.go:46, autocomplete.go:40, service_test.go:36-79).  Blocking; concurrent callers are

@@ -537,6 +537,103 @@ inline std::shared_ptr<Builder> NewFSBuilder(const IndexDescription& d, int devi
   return std::make_shared<detail::FSBuilder>(d, device);
 }
 
+// ---------------------------------------------------------------------------------------------
+// ShardedIndex — a dictionary sharded by docID range behind one sg_sharded handle (suggest_hip.h): for dictionaries past
+// one NGramIndex's limits.  Suggest / Autocomplete as NGramIndex has them; Keys are dictionary-wide docIDs.  No reference
+// counterpart.  With documents that repeat a term the reference's secondary duplicate rows can differ from an unsharded index's.
+// ---------------------------------------------------------------------------------------------
+class ShardedIndex {
+ public:
+  explicit ShardedIndex(sg_sharded* h) : h_(h) {}
+  // shard s of n_shards goes to devices[s % devices.size()]; buildOnDevice: every shard is built on its own GPU
+  ShardedIndex(const std::shared_ptr<dictionary::Dictionary>& dict, const IndexDescription& d, uint32_t n_shards,
+               const std::vector<int>& devices = {0}, bool buildOnDevice = false) {
+    std::string blob;
+    std::vector<uint64_t> offs(1, 0);
+    dict->Iterate([&](dictionary::Key, const dictionary::Value& w) {
+      blob += w;
+      offs.push_back(blob.size());
+    });
+    detail::DescC dc(d);
+    NGramIndex::Check(sg_sharded_build((const uint8_t*)blob.data(), offs.data(), (uint32_t)(offs.size() - 1), &dc.d, n_shards, devices.data(),
+                                       (uint32_t)devices.size(), buildOnDevice ? 0 : -1, &h_));
+  }
+  // shards that are already built and uploaded; doc_lo[s] = the dictionary docID of shard s's document 0
+  static std::shared_ptr<ShardedIndex> Adopt(const std::vector<std::shared_ptr<NGramIndex>>& shards, const std::vector<uint64_t>& doc_lo) {
+    if (shards.size() != doc_lo.size()) throw Error("one doc_lo per shard");
+    std::vector<sg_index*> hs;
+    for (auto& s : shards) hs.push_back(s->Handle());
+    sg_sharded* h = nullptr;
+    NGramIndex::Check(sg_sharded_adopt(hs.data(), doc_lo.data(), (uint32_t)hs.size(), &h));
+    return std::make_shared<ShardedIndex>(h);
+  }
+  ~ShardedIndex() { if (h_) sg_sharded_release(h_); }
+  ShardedIndex(const ShardedIndex&) = delete;
+  ShardedIndex& operator=(const ShardedIndex&) = delete;
+  sg_sharded* Handle() const { return h_; }
+
+  std::vector<Candidate> Suggest(const std::string& query, double similarity, metric::Metric m, int topK) const {
+    return SuggestBatch({query}, similarity, m, topK)[0];
+  }
+  std::vector<Candidate> Autocomplete(const std::string& query, int limit) const { return AutocompleteBatch({query}, limit)[0]; }
+
+  std::vector<std::vector<Candidate>> SuggestBatch(const std::vector<std::string>& queries, double similarity, metric::Metric m,
+                                                   int topK) const {
+    std::vector<uint64_t> offs;
+    const std::string blob = Pack(queries, offs);
+    const size_t n = queries.size(), k = (size_t)(topK > 0 ? topK : 0);
+    std::vector<uint32_t> ids(n * k), counts(n);
+    std::vector<double> scores(n * k);
+    NGramIndex::Check(sg_sharded_suggest_batch(h_, (const uint8_t*)blob.data(), offs.data(), (uint32_t)n, m.id, similarity, (uint32_t)k,
+                                               ids.data(), scores.data(), counts.data()));
+    std::vector<std::vector<Candidate>> out(n);
+    for (size_t i = 0; i < n; i++) {
+      if (counts[i] == SG_COUNT_REF_PANIC) throw Error("reference behaviour: panic: makechan: size out of range");
+      if (counts[i] == SG_COUNT_REF_DEADLOCK) throw Error("reference behaviour: deadlock (unbuffered channel, suggester.go:62)");
+      if (counts[i] == SG_COUNT_TOO_LONG) throw Error("query has more than SG_MAX_QUERY_TERMS n-grams");
+      for (uint32_t j = 0; j < counts[i]; j++) out[i].push_back(Candidate{ids[i * k + j], scores[i * k + j]});
+    }
+    return out;
+  }
+
+  std::vector<std::vector<Candidate>> AutocompleteBatch(const std::vector<std::string>& queries, int limit) const {
+    std::vector<uint64_t> offs;
+    const std::string blob = Pack(queries, offs);
+    const size_t n = queries.size(), k = (size_t)(limit > 0 ? limit : 0);
+    std::vector<uint32_t> ids(n * k), counts(n);
+    NGramIndex::Check(sg_sharded_autocomplete_batch(h_, (const uint8_t*)blob.data(), offs.data(), (uint32_t)n, (uint32_t)k, ids.data(),
+                                                    counts.data()));
+    std::vector<std::vector<Candidate>> out(n);
+    for (size_t i = 0; i < n; i++) {
+      if (counts[i] == SG_COUNT_TOO_LONG) throw Error("query has more than SG_MAX_QUERY_TERMS n-grams");
+      for (uint32_t j = 0; j < counts[i]; j++) out[i].push_back(Candidate{ids[i * k + j], 0.0});
+    }
+    return out;
+  }
+
+  // (doc_lo, device) of the shards that stand, in docID order
+  std::vector<std::pair<uint64_t, int>> Shards() const {
+    uint64_t lo[SG_MAX_SHARDS];
+    int dev[SG_MAX_SHARDS];
+    const uint32_t n = sg_sharded_shards(h_, lo, dev, SG_MAX_SHARDS);
+    std::vector<std::pair<uint64_t, int>> out;
+    for (uint32_t s = 0; s < n && s < SG_MAX_SHARDS; s++) out.emplace_back(lo[s], dev[s]);
+    return out;
+  }
+
+ private:
+  static std::string Pack(const std::vector<std::string>& qs, std::vector<uint64_t>& offs) {
+    std::string blob;
+    offs.assign(1, 0);
+    for (auto& q : qs) {
+      blob += q;
+      offs.push_back(blob.size());
+    }
+    return blob;
+  }
+  sg_sharded* h_ = nullptr;
+};
+
 // Index — indexer.go:14-45 and the `indexer` command: indexes the dictionary and writes GetHeaderFile(), GetDocumentListFile()
 // (Writer.Commit, indexer_writer.go:88-167) and the dictionary as GetDictionaryFile() (BuildCDBDictionary, helpers.go:52-95) —
 // the files NewFSBuilder and OpenCDBDictionary open.  device >= 0: built and encoded on that GPU; device < 0: on the host.

@@ -31,7 +31,10 @@ EXPORTS = [
     "sg_lm_build_device", "sg_lm_store_binary", "sg_debug_lm_build_hash_bits",
     "sg_index_store_reference", "sg_dictionary_store_cdb", "sg_debug_index_store_times",
     "sg_lm_store_binary_ex", "sg_lm_store_google", "sg_debug_lm_store_slice_bytes", "sg_debug_lm_store_times",
+    "sg_sharded_build", "sg_sharded_adopt", "sg_sharded_retain", "sg_sharded_release", "sg_sharded_shards", "sg_sharded_suggest_batch",
+    "sg_sharded_suggest_batch_device", "sg_sharded_autocomplete_batch", "sg_debug_shard_slice_bytes", "sg_debug_shard_merge", "sg_debug_shard_merge_time",
 ]
+SG_MAX_SHARDS = 64
 SG_LM_STORE_MPH = 1
 SG_COUNT_LM_ERROR = 0xFFFFFFFC
 
@@ -164,6 +167,20 @@ def lib():
     if hasattr(L, "sg_metric_tables_release"): L.sg_metric_tables_release.restype = None
     if hasattr(L, "sg_suggest_batch_tables"): L.sg_suggest_batch_tables.argtypes = [vp, vp, vp, u32, vp, u32, vp, vp, vp]
     if hasattr(L, "sg_suggest_batch_from"): L.sg_suggest_batch_from.argtypes = [vp, vp, vp, u32, i32, dbl, vp, u32, u32, vp, vp, vp, vp]
+    if hasattr(L, "sg_sharded_build"): L.sg_sharded_build.argtypes = [vp, vp, u32, C.POINTER(SgDesc), u32, vp, u32, i32, C.POINTER(vp)]
+    if hasattr(L, "sg_sharded_adopt"): L.sg_sharded_adopt.argtypes = [vp, vp, u32, C.POINTER(vp)]
+    if hasattr(L, "sg_sharded_retain"): L.sg_sharded_retain.argtypes = [vp]
+    if hasattr(L, "sg_sharded_retain"): L.sg_sharded_retain.restype = None
+    if hasattr(L, "sg_sharded_release"): L.sg_sharded_release.argtypes = [vp]
+    if hasattr(L, "sg_sharded_release"): L.sg_sharded_release.restype = None
+    if hasattr(L, "sg_sharded_shards"): L.sg_sharded_shards.argtypes = [vp, vp, vp, u32]
+    if hasattr(L, "sg_sharded_shards"): L.sg_sharded_shards.restype = u32
+    if hasattr(L, "sg_sharded_suggest_batch"): L.sg_sharded_suggest_batch.argtypes = [vp, vp, vp, u32, i32, dbl, u32, vp, vp, vp]
+    if hasattr(L, "sg_sharded_suggest_batch_device"): L.sg_sharded_suggest_batch_device.argtypes = [vp, vp, vp, u32, i32, dbl, u32, vp, vp, vp, vp]
+    if hasattr(L, "sg_sharded_autocomplete_batch"): L.sg_sharded_autocomplete_batch.argtypes = [vp, vp, vp, u32, u32, vp, vp]
+    if hasattr(L, "sg_debug_shard_slice_bytes"): L.sg_debug_shard_slice_bytes.argtypes = [u32]
+    if hasattr(L, "sg_debug_shard_merge"): L.sg_debug_shard_merge.argtypes = [i32, vp, vp, vp, vp, u32, u32, u32, i32, vp, vp, vp]
+    if hasattr(L, "sg_debug_shard_merge_time"): L.sg_debug_shard_merge_time.argtypes = [C.POINTER(dbl)]
     _lib = L
     return L
 
