@@ -1128,6 +1128,42 @@ func (i *Index) StoreReference(hdPath, dlPath string, device int) error {
 	})
 }
 
+// OpenReference opens the <name>.hd / <name>.dl pair the reference's indexer (or StoreReference) wrote — NewFSBuilder,
+// pkg/suggest/ngram_index_builder.go:44-83 — and uploads it to the GPU `device`.  decodeDevice >= 0 decodes the posting lists
+// on that GPU, decodeDevice < 0 with the host reader; the index is the same word for word (sg_index_load_reference_ex).
+func OpenReference(hdPath, dlPath string, d suggest.IndexDescription, device, decodeDevice int) (*Index, error) {
+	arr, freeAlpha := cstrings(d.Alphabet)
+	defer freeAlpha()
+	w0, w1, pad := C.CString(d.Wrap[0]), C.CString(d.Wrap[1]), C.CString(d.Pad)
+	defer C.free(unsafe.Pointer(w0))
+	defer C.free(unsafe.Pointer(w1))
+	defer C.free(unsafe.Pointer(pad))
+	desc := (*C.sg_desc)(C.malloc(C.size_t(unsafe.Sizeof(C.sg_desc{}))))
+	defer C.free(unsafe.Pointer(desc))
+	desc.ngram_size, desc.wrap_start, desc.wrap_end, desc.pad = C.uint32_t(d.NGramSize), w0, w1, pad
+	desc.alphabet, desc.n_alphabet = arr, C.uint32_t(len(d.Alphabet))
+	chd, cdl := C.CString(hdPath), C.CString(dlPath)
+	defer C.free(unsafe.Pointer(chd))
+	defer C.free(unsafe.Pointer(cdl))
+	var h *C.sg_index
+	if err := ccall(func() C.int { return C.sg_index_load_reference_ex(chd, cdl, desc, C.int(decodeDevice), &h) }); err != nil {
+		return nil, err
+	}
+	if err := ccall(func() C.int { return C.sg_index_upload(h, C.int(device)) }); err != nil {
+		C.sg_index_release(h)
+		return nil, err
+	}
+	e := &engine{h: h, reqs: make(chan *request, 4096), closing: make(chan struct{}), done: make(chan struct{}),
+		tables: map[tablesKey]*tableEntry{}}
+	var st C.sg_stats
+	C.sg_index_stats(h, &st)
+	e.segments = int(st.n_segments)
+	go e.dispatch()
+	ix := &Index{e: e}
+	runtime.SetFinalizer(ix, func(i *Index) { i.Close() })
+	return ix, nil
+}
+
 // StoreCDBDictionary writes the dictionary the reference's services open beside the index (dictionary.BuildCDBDictionary,
 // pkg/dictionary/helpers.go:52-95): key = docID as 4 bytes little endian, value = the line (sg_dictionary_store_cdb).
 func StoreCDBDictionary(lines []string, cdbPath string) error {

@@ -82,6 +82,21 @@ int sg_index_build_ex(const uint8_t* utf8, const uint64_t* offs, uint32_t n_docs
  * index the reference itself built — <name>.hd (gob header) and <name>.dl (VB / skip-VB / roaring posting lists,
  * pkg/index/codec.go:39-51) — into the same CSR.  `desc` must be the IndexDescription the files were built with. */
 int sg_index_load_reference(const char* hd_path, const char* dl_path, const sg_desc* desc, sg_index** out);
+/* The same load with the posting lists decoded on a GPU.  device < 0 is sg_index_load_reference itself: the host
+ * reader, no GPU initialised.  device >= 0 uploads the .dl and decodes its VB / skip-VB / roaring lists there in two passes (count,
+ * then write) with the positions scanned on the host between them; the handle's CSR — postings, offsets, lengths, terms, the
+ * repeats table, the counters — is word for word the host reader's for every file it accepts, and every file it refuses is refused
+ * with the same code and message (SG_E_INVALID names the term of the first malformed list).  The header parse, the term interning,
+ * the position scan and the term table stay on the host.  Needs no sg_index_upload and makes no replica: it works in memory of its
+ * own on a stream of its own and frees it before it returns.  A header that gives one (term, segment) pair two lists, and a
+ * roaring list whose values do not strictly ascend, are decoded by the host's decoders: no writer emits either. */
+int sg_index_load_reference_ex(const char* hd_path, const char* dl_path, const sg_desc* desc, int device, sg_index** out);
+/* Test hook like the other sg_debug_* entries (tools/index_load_timing.py reads it; bindings need not mirror it): milliseconds the
+ * calling thread's last successful sg_index_load_reference_ex spent — out_ms[0 .. min(cap, 7)) = {reading the files; parsing the
+ * header and interning the terms; host-to-device copies with the kernels' input tables; the kernels (device < 0: the host
+ * decoders); device-to-host copies; assembly on the host: positions, repeats, the term table; the whole call}.  No reference
+ * counterpart. */
+int sg_debug_index_load_times(double* out_ms, uint32_t cap);
 
 /* Writer.Commit (pkg/index/indexer_writer.go:88-167) + index.NewEncoder (pkg/index/codec.go:17-51): saves the index as the
  * <name>.hd / <name>.dl pair sg_index_load_reference and the reference's NewFSBuilder open — what the reference's `indexer`

@@ -514,11 +514,14 @@ class RAMBuilder : public Builder {  // NewRAMBuilder: index the dictionary in m
 
 class FSBuilder : public Builder {  // NewFSBuilder: <output>/<name>.hd + .dl written by the reference's indexer
  public:
-  FSBuilder(IndexDescription desc, int device) : desc_(std::move(desc)), device_(device) {}
+  FSBuilder(IndexDescription desc, int device, int decode_device = -1) : desc_(std::move(desc)), device_(device), decode_device_(decode_device) {}
   std::shared_ptr<NGramIndex> Build() override {
     DescC dc(desc_);
     sg_index* h = nullptr;
-    NGramIndex::Check(sg_index_load_reference(desc_.GetHeaderFile().c_str(), desc_.GetDocumentListFile().c_str(), &dc.d, &h));
+    if (decode_device_ < 0)
+      NGramIndex::Check(sg_index_load_reference(desc_.GetHeaderFile().c_str(), desc_.GetDocumentListFile().c_str(), &dc.d, &h));
+    else   // the posting lists decoded on that GPU: the same index word for word
+      NGramIndex::Check(sg_index_load_reference_ex(desc_.GetHeaderFile().c_str(), desc_.GetDocumentListFile().c_str(), &dc.d, decode_device_, &h));
     auto ix = std::make_shared<NGramIndex>(h);
     NGramIndex::Check(sg_index_upload(h, device_));
     return ix;
@@ -526,15 +529,16 @@ class FSBuilder : public Builder {  // NewFSBuilder: <output>/<name>.hd + .dl wr
 
  private:
   IndexDescription desc_;
-  int device_;
+  int device_, decode_device_;
 };
 }  // namespace detail
 
 inline std::shared_ptr<Builder> NewRAMBuilder(std::shared_ptr<dictionary::Dictionary> dict, const IndexDescription& d, int device = 0) {
   return std::make_shared<detail::RAMBuilder>(std::move(dict), d, device);
 }
-inline std::shared_ptr<Builder> NewFSBuilder(const IndexDescription& d, int device = 0) {
-  return std::make_shared<detail::FSBuilder>(d, device);
+// decode_device >= 0: the posting lists are decoded on that GPU (sg_index_load_reference_ex); the default is the host reader
+inline std::shared_ptr<Builder> NewFSBuilder(const IndexDescription& d, int device = 0, int decode_device = -1) {
+  return std::make_shared<detail::FSBuilder>(d, device, decode_device);
 }
 
 // ---------------------------------------------------------------------------------------------

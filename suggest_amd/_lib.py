@@ -30,6 +30,7 @@ EXPORTS = [
     "sg_lm_score_text_batch", "sg_lm_score_text_batch_device", "sg_lm_score_word_ids_batch",
     "sg_lm_build_device", "sg_lm_store_binary", "sg_debug_lm_build_hash_bits",
     "sg_index_store_reference", "sg_dictionary_store_cdb", "sg_debug_index_store_times",
+    "sg_index_load_reference_ex", "sg_debug_index_load_times",
     "sg_lm_store_binary_ex", "sg_lm_store_google", "sg_debug_lm_store_slice_bytes", "sg_debug_lm_store_times",
     "sg_sharded_build", "sg_sharded_adopt", "sg_sharded_retain", "sg_sharded_release", "sg_sharded_shards", "sg_sharded_suggest_batch",
     "sg_sharded_suggest_batch_device", "sg_sharded_autocomplete_batch", "sg_debug_shard_slice_bytes", "sg_debug_shard_merge", "sg_debug_shard_merge_time",
@@ -72,6 +73,8 @@ def lib():
     if hasattr(L, "sg_index_build_ex"): L.sg_index_build_ex.argtypes = [vp, vp, u32, C.POINTER(SgDesc), u32, i32, C.POINTER(vp)]
     if hasattr(L, "sg_index_digest"): L.sg_index_digest.argtypes = [vp, vp]
     if hasattr(L, "sg_index_load_reference"): L.sg_index_load_reference.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(SgDesc), C.POINTER(vp)]
+    if hasattr(L, "sg_index_load_reference_ex"): L.sg_index_load_reference_ex.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(SgDesc), i32, C.POINTER(vp)]
+    if hasattr(L, "sg_debug_index_load_times"): L.sg_debug_index_load_times.argtypes = [vp, u32]
     if hasattr(L, "sg_index_store_reference"): L.sg_index_store_reference.argtypes = [vp, C.c_char_p, C.c_char_p, i32]
     if hasattr(L, "sg_dictionary_store_cdb"): L.sg_dictionary_store_cdb.argtypes = [vp, vp, u32, C.c_char_p]
     if hasattr(L, "sg_debug_index_store_times"): L.sg_debug_index_store_times.argtypes = [vp]

@@ -2918,5 +2918,6 @@ __global__ __launch_bounds__(64) void pairsort_test_kernel(const uint32_t* keys,
 
 #include "capi.inc"
 #include "index_store.inc"
+#include "index_load.inc"
 #include "lm_store.inc"
 #include "shard_merge.inc"

@@ -11,6 +11,7 @@
 // Only the byte formats are restated here; no reference code is used.
 
 #include <algorithm>
+#include <chrono>
 #include <cstdio>
 #include <cstring>
 #include <map>
@@ -43,7 +44,7 @@ struct Reader {
   }
 };
 
-struct TermDesc { std::string term; uint32_t indice = 0, size = 0, pos = 0, len = 0; };
+using TermDesc = RefTerm;
 
 bool read_file(const char* path, std::vector<uint8_t>& out) {
   FILE* f = fopen(path, "rb");
@@ -186,61 +187,94 @@ bool decode_roaring(const uint8_t* b, size_t n, std::vector<uint32_t>& out) {
 
 }  // namespace
 
-// Builds the host CSR (same layout as build_host_index) from reference-built <name>.hd / <name>.dl.
-int load_reference_index(const char* hd_path, const char* dl_path, const sg_desc* desc, HostIndex& ix, std::string& err) {
+// Step 1 of a load: the files read, the gob header parsed, the terms interned, each descriptor checked.
+int ref_open(const char* hd_path, const char* dl_path, const sg_desc* desc, HostIndex& ix, RefFiles& f, std::string& err, double seconds[2]) {
+  using clk = std::chrono::steady_clock;
   int rc = init_description(desc, ix, err);
   if (rc) return rc;
-  std::vector<uint8_t> hd, dl;
+  const auto t0 = clk::now();
+  std::vector<uint8_t> hd;
   if (!read_file(hd_path, hd)) { err = std::string("failed to open header: ") + hd_path; return SG_E_INVALID; }
-  if (!read_file(dl_path, dl)) { err = std::string("failed to open document list: ") + dl_path; return SG_E_INVALID; }
+  if (!read_file(dl_path, f.dl)) { err = std::string("failed to open document list: ") + dl_path; return SG_E_INVALID; }
+  const auto t1 = clk::now();
   std::string version;
   uint32_t indices = 0;
-  std::vector<TermDesc> terms;
-  if (!parse_header(hd, version, indices, terms)) { err = "failed to retrieve header: malformed gob stream"; return SG_E_INVALID; }
+  if (!parse_header(hd, version, indices, f.terms)) { err = "failed to retrieve header: malformed gob stream"; return SG_E_INVALID; }
   if (version != "v5.1") { err = "index version mismatch, expected v5.1 version"; return SG_E_INVALID; }   // index_reader.go:71-73
   const uint32_t S = indices;
   ix.n_segments = S;
   // intern terms: every rune of a stored term must be a symbol of the description
-  struct L { uint32_t t, b, raw; std::vector<uint32_t> v; };
-  std::vector<L> lists;
-  lists.reserve(terms.size());
-  uint32_t max_doc = 0;
-  bool any = false;
-  for (const auto& td : terms) {
+  f.lists.reserve(f.terms.size());
+  for (size_t d = 0; d < f.terms.size(); d++) {
+    const TermDesc& td = f.terms[d];
     if (td.size == 0 || td.indice >= S) continue;
     uint64_t key;
-    if (!term_string_key(ix, td.term, &key)) { err = "stored term '" + td.term + "' does not fit the description's alphabet/pad"; return SG_E_UNSUPPORTED; }
+    if (!term_string_key(ix, td.term, &key)) { f.fail_rc = SG_E_UNSUPPORTED; f.fail_err = "stored term '" + td.term + "' does not fit the description's alphabet/pad"; break; }
     uint32_t t;
     auto it = ix.term_of.find(key);
     if (it == ix.term_of.end()) { t = (uint32_t)ix.term_key.size(); ix.term_key.push_back(key); ix.term_of.emplace(key, t); }
     else t = it->second;
-    if ((uint64_t)td.pos + td.size > dl.size()) { err = "posting list outside the document list file"; return SG_E_INVALID; }
-    L l{t, td.indice, td.len, {}};
-    const uint8_t* b = dl.data() + td.pos;
-    bool ok = td.len <= 65 ? decode_vb(b, td.size, td.len, l.v) : td.len <= 256 ? decode_skipping(b, td.size, td.len, l.v) : decode_roaring(b, td.size, l.v);
-    if (!ok || l.v.empty()) { err = "malformed posting list of term '" + td.term + "'"; return SG_E_INVALID; }
-    max_doc = std::max(max_doc, l.v.back());
-    any = true;
-    ix.n_postings_raw += td.len;
-    lists.push_back(std::move(l));
+    if ((uint64_t)td.pos + td.size > f.dl.size()) { f.fail_rc = SG_E_INVALID; f.fail_err = "posting list outside the document list file"; break; }
+    f.lists.push_back(RefList{t, td.indice, td.len, td.size, td.pos, (uint32_t)d});
   }
-  ix.n_docs = any ? (uint64_t)max_doc + 1 : 0;
+  if (seconds) { seconds[0] = std::chrono::duration<double>(t1 - t0).count(); seconds[1] = std::chrono::duration<double>(clk::now() - t1).count(); }
+  return SG_OK;
+}
+
+// A (term, segment) pair with two descriptors: the host route lets the later one win, so the order of the lists matters.
+bool ref_pair_twice(const HostIndex& ix, const RefFiles& f) {
+  std::vector<bool> seen(ix.term_key.size() * (size_t)ix.n_segments);
+  for (const RefList& l : f.lists) {
+    const size_t at = (size_t)l.term * ix.n_segments + l.segment;
+    if (seen[at]) return true;
+    seen[at] = true;
+  }
+  return false;
+}
+
+// Step 2 on the host: one list decoded, repeats and all.
+bool ref_decode_list(const RefFiles& f, const RefList& l, std::vector<uint32_t>& out) {
+  const uint8_t* b = f.dl.data() + l.pos;
+  out.clear();
+  const bool ok = l.raw <= 65 ? decode_vb(b, l.size, l.raw, out) : l.raw <= 256 ? decode_skipping(b, l.size, l.raw, out) : decode_roaring(b, l.size, out);
+  return ok && !out.empty();
+}
+
+int ref_malformed(const RefFiles& f, const RefList& l, std::string& err) {
+  err = "malformed posting list of term '" + f.terms[l.desc].term + "'";
+  return SG_E_INVALID;
+}
+
+// Runs of equal docIDs = a doc repeating the term: v de-duplicated in place, the repeats appended to ix.dups.
+void ref_dedup(HostIndex& ix, const RefList& l, std::vector<uint32_t>& v) {
+  std::vector<uint32_t> ded;
+  ded.reserve(v.size());
+  for (size_t i = 0; i < v.size();) {
+    size_t j = i;
+    while (j < v.size() && v[j] == v[i]) j++;
+    ded.push_back(v[i]);
+    if (j - i > 1) ix.dups.push_back(DupEntry{l.term, l.segment, v[i], (uint32_t)(j - i)});
+    i = j;
+  }
+  ref_marker(ix, l, ded.size());
+  v.swap(ded);
+}
+
+void ref_marker(HostIndex& ix, const RefList& l, size_t stored) {
+  if (l.raw > 256 && l.raw > stored)                      // roaring dropped the repeats: keep the raw length (codec dispatch)
+    ix.dups.push_back(DupEntry{l.term, l.segment, 0xFFFFFFFFu, (uint32_t)(l.raw - stored) + 1});
+}
+
+// Step 3, first half: list_len, the counters, seg_off and a zeroed posting store from the stored length of every list.
+int ref_layout(HostIndex& ix, const RefFiles& f, const uint32_t* stored, std::string& err) {
+  const uint32_t S = ix.n_segments;
   const size_t nT = ix.term_key.size();
   ix.list_len.assign(nT * (size_t)S, 0);
-  for (auto& l : lists) {                                   // runs of equal docIDs = a doc repeating the term
-    std::vector<uint32_t> ded;
-    for (size_t i = 0; i < l.v.size();) {
-      size_t j = i;
-      while (j < l.v.size() && l.v[j] == l.v[i]) j++;
-      ded.push_back(l.v[i]);
-      if (j - i > 1) ix.dups.push_back(DupEntry{l.t, l.b, l.v[i], (uint32_t)(j - i)});
-      i = j;
-    }
-    if (l.raw > 256 && l.raw > ded.size())                  // roaring dropped the repeats: keep the raw length (codec dispatch)
-      ix.dups.push_back(DupEntry{l.t, l.b, 0xFFFFFFFFu, (uint32_t)(l.raw - ded.size()) + 1});
-    l.v.swap(ded);
-    ix.list_len[(size_t)l.t * S + l.b] = (uint32_t)l.v.size();
-    ix.n_postings += l.v.size();
+  for (size_t i = 0; i < f.lists.size(); i++) {
+    const RefList& l = f.lists[i];
+    ix.list_len[(size_t)l.term * S + l.segment] = stored[i];
+    ix.n_postings += stored[i];
+    ix.n_postings_raw += l.raw;
     ix.n_lists++;
   }
   ix.seg_off.assign(nT * (size_t)(S + 1) + 1, 0);
@@ -251,18 +285,52 @@ int load_reference_index(const char* hd_path, const char* dl_path, const sg_desc
     if (chunk >= 0xFFFFFFF0ull) { err = "posting store exceeds 2^32 16-byte chunks"; return SG_E_UNSUPPORTED; }
   }
   ix.postings.assign((size_t)chunk * 4, 0);
-  for (const auto& l : lists) {
-    uint32_t* p = ix.postings.data() + (size_t)ix.seg_off[(size_t)l.t * (S + 1) + l.b] * 4;
-    std::copy(l.v.begin(), l.v.end(), p);
-    for (size_t i = l.v.size(); i < ((l.v.size() + 3) & ~(size_t)3); i++) p[i] = l.v.back();
-  }
+  return SG_OK;
+}
+
+void ref_put_list(HostIndex& ix, const RefList& l, const std::vector<uint32_t>& v) {
+  uint32_t* p = ix.postings.data() + (size_t)ix.seg_off[(size_t)l.term * (ix.n_segments + 1) + l.segment] * 4;
+  std::copy(v.begin(), v.end(), p);
+  for (size_t i = v.size(); i < ((v.size() + 3) & ~(size_t)3); i++) p[i] = v.back();
+}
+
+// Step 3, second half: the repeats sorted, the term table.
+void ref_finish(HostIndex& ix) {
   std::sort(ix.dups.begin(), ix.dups.end(), [](const DupEntry& x, const DupEntry& y) {
     if (x.term != y.term) return x.term < y.term;
     if (x.segment != y.segment) return x.segment < y.segment;
     return x.doc < y.doc;
   });
   build_term_table(ix);
+}
+
+// Steps 2 and 3 on the host: every list into a vector of its own, de-duplicated, copied into the CSR.
+int ref_decode_host(HostIndex& ix, const RefFiles& f, std::string& err, double seconds[2]) {
+  using clk = std::chrono::steady_clock;
+  const auto t0 = clk::now();
+  std::vector<std::vector<uint32_t>> v(f.lists.size());
+  uint32_t max_doc = 0;
+  for (size_t i = 0; i < f.lists.size(); i++) {
+    if (!ref_decode_list(f, f.lists[i], v[i])) return ref_malformed(f, f.lists[i], err);
+    max_doc = std::max(max_doc, v[i].back());
+  }
+  if (f.fail_rc) { err = f.fail_err; return f.fail_rc; }
+  const auto t1 = clk::now();
+  ix.n_docs = f.lists.empty() ? 0 : (uint64_t)max_doc + 1;
+  std::vector<uint32_t> stored(f.lists.size());
+  for (size_t i = 0; i < f.lists.size(); i++) { ref_dedup(ix, f.lists[i], v[i]); stored[i] = (uint32_t)v[i].size(); }
+  if (int rc = ref_layout(ix, f, stored.data(), err)) return rc;
+  for (size_t i = 0; i < f.lists.size(); i++) ref_put_list(ix, f.lists[i], v[i]);
+  ref_finish(ix);
+  if (seconds) { seconds[0] = std::chrono::duration<double>(t1 - t0).count(); seconds[1] = std::chrono::duration<double>(clk::now() - t1).count(); }
   return SG_OK;
+}
+
+// Builds the host CSR (same layout as build_host_index) from reference-built <name>.hd / <name>.dl.
+int load_reference_index(const char* hd_path, const char* dl_path, const sg_desc* desc, HostIndex& ix, std::string& err, double* seconds) {
+  RefFiles f;
+  if (int rc = ref_open(hd_path, dl_path, desc, ix, f, err, seconds)) return rc;
+  return ref_decode_host(ix, f, err, seconds ? seconds + 2 : nullptr);
 }
 
 }  // namespace sg

@@ -74,8 +74,36 @@ int build_host_index(const uint8_t* utf8, const uint64_t* offs, uint32_t n_docs,
 int init_description(const sg_desc* desc, HostIndex& ix, std::string& err);
 bool term_string_key(const HostIndex& ix, const std::string& term, uint64_t* key);
 void build_term_table(HostIndex& ix);
-// loads reference-built <name>.hd / <name>.dl (ref_index_reader.cpp)
-int load_reference_index(const char* hd_path, const char* dl_path, const sg_desc* desc, HostIndex& ix, std::string& err);
+// loads reference-built <name>.hd / <name>.dl (ref_index_reader.cpp); seconds (may be null): [4] file read, header parse and
+// term interning, list decode, assembly
+int load_reference_index(const char* hd_path, const char* dl_path, const sg_desc* desc, HostIndex& ix, std::string& err, double* seconds = nullptr);
+// ---- its three steps, shared with the device decoder (index_load.inc) ----
+struct RefTerm { std::string term; uint32_t indice = 0, size = 0, pos = 0, len = 0; };   // a termDescription of the header
+struct RefList {     // a descriptor that passed the checks of step 1: size != 0, indice < Indices, pos + size inside the .dl, the alphabet
+  uint32_t term, segment;
+  uint32_t raw;      // PostingListLen: picks the codec
+  uint32_t size, pos;
+  uint32_t desc;     // its RefTerm (the error messages name the term)
+};
+struct RefFiles {
+  std::vector<uint8_t> dl;
+  std::vector<RefTerm> terms;
+  std::vector<RefList> lists;          // header order; up to the first descriptor that was refused
+  int fail_rc = 0;                     // that refusal: returned unless a list before it is malformed (the order the errors are met in)
+  std::string fail_err;
+};
+// 1: read, parse, intern, check; seconds (may be null): [2] file read, the rest
+int ref_open(const char* hd_path, const char* dl_path, const sg_desc* desc, HostIndex& ix, RefFiles& f, std::string& err, double seconds[2]);
+// 2 + 3 on the host; seconds (may be null): [2] decode, assembly
+int ref_decode_host(HostIndex& ix, const RefFiles& f, std::string& err, double seconds[2]);
+bool ref_pair_twice(const HostIndex& ix, const RefFiles& f);
+bool ref_decode_list(const RefFiles& f, const RefList& l, std::vector<uint32_t>& out);            // false: malformed (or empty)
+int ref_malformed(const RefFiles& f, const RefList& l, std::string& err);                        // the message; -> SG_E_INVALID
+void ref_dedup(HostIndex& ix, const RefList& l, std::vector<uint32_t>& v);                       // v de-duplicated, ix.dups appended to
+void ref_marker(HostIndex& ix, const RefList& l, size_t stored);                                 // raw > 256 > stored: the marker entry
+int ref_layout(HostIndex& ix, const RefFiles& f, const uint32_t* stored, std::string& err);      // list_len, counters, seg_off, postings zeroed
+void ref_put_list(HostIndex& ix, const RefList& l, const std::vector<uint32_t>& v);              // a list into its chunks, the last one padded
+void ref_finish(HostIndex& ix);                                                                  // dups sorted, the term table
 
 // ---- saving an index as reference-format <name>.hd / <name>.dl (index_store.cpp; the device encoder: index_store.inc) ----
 struct StoreList {   // one non-empty (segment, term) list; the header order is segment ascending, then the order of sg_index_lists

@@ -168,12 +168,16 @@ class NGramIndex:
             self.upload(device)
 
     @classmethod
-    def from_reference_files(cls, hd_path, dl_path, description, device=0, upload=True):
+    def from_reference_files(cls, hd_path, dl_path, description, device=0, upload=True, decode_device=None):
         """NewFSBuilder (pkg/suggest/ngram_index_builder.go:44-52): open an index the reference built
-        (<name>.hd gob header + <name>.dl posting lists)."""
+        (<name>.hd gob header + <name>.dl posting lists).  decode_device=None: the host reader decodes the lists; an int: that
+        GPU does (sg_index_load_reference_ex) — the same index word for word, the same refusals."""
         desc = _c_desc(description)
         h = C.c_void_p()
-        _lib.check(_lib.lib().sg_index_load_reference(_enc(hd_path), _enc(dl_path), C.byref(desc), C.byref(h)))
+        if decode_device is None:
+            _lib.check(_lib.lib().sg_index_load_reference(_enc(hd_path), _enc(dl_path), C.byref(desc), C.byref(h)))
+        else:
+            _lib.check(_lib.lib().sg_index_load_reference_ex(_enc(hd_path), _enc(dl_path), C.byref(desc), int(decode_device), C.byref(h)))
         return cls(description=description, device=device, upload=upload, _handle=h)
 
     def save(self, hd_path, dl_path, device=None):
