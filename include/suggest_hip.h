@@ -45,7 +45,9 @@ enum sg_error {
   SG_E_UNSUPPORTED = -2,  /* description outside what the packed 64-bit term key can hold */
   SG_E_NOT_UPLOADED = -3,
   SG_E_HIP = -4,          /* HIP runtime error; message has the hipError string */
-  SG_E_NOMEM = -5
+  SG_E_NOMEM = -5         /* out of memory: host (message "out of host memory") or device — every failed hipMalloc of an
+                             upload, build, store, load, language model or metric table ("hipMalloc: <hipError string>");
+                             upload, the language model's upload and sg_metric_tables_create returned SG_E_HIP for it once */
 };
 
 /* Values stored in out_counts[i] instead of a count, for queries the reference itself does not

@@ -1,6 +1,8 @@
 // capi.inc — host side of libsuggest_hip, included by engine.hip (it launches the kernels defined there):
 // the index handle and its per-GPU replicas, launches, the C ABI of include/suggest_hip.h.
 
+#include <hipcub/hipcub.hpp>
+
 // ------------------------------------------------------------------------------------------
 // host side: handle, replicas, launches
 // ------------------------------------------------------------------------------------------
@@ -44,6 +46,94 @@ struct DeviceGuard {
   }
   ~DeviceGuard() { if (prev >= 0 && cur != prev) (void)hipSetDevice(prev); }
 };
+
+// The one owner of device memory that is held, not reused (reuse buffers are GrowBlocks, below): a replica's arrays, a language
+// model's tables, metric tables, the working memory of a build / store / load call.  Its blocks live on the device that was current
+// at the first alloc(); the destructor frees them with that device current and puts the caller's back.  Movable: "commit on
+// success" is to build in a local DeviceBlock and move it into the handle as the last step.  A failed hipMalloc is SG_E_NOMEM.
+struct DeviceBlock {
+  struct Block { void* p; size_t bytes; };
+  std::vector<Block> blocks;
+  int device = -1;
+  uint64_t sum = 0;
+  DeviceBlock() = default;
+  DeviceBlock(DeviceBlock&& o) noexcept { swap(o); }
+  DeviceBlock& operator=(DeviceBlock&& o) noexcept { clear(); swap(o); return *this; }
+  ~DeviceBlock() { clear(); }
+  void swap(DeviceBlock& o) { blocks.swap(o.blocks); std::swap(device, o.device); std::swap(sum, o.sum); }
+  void clear() {
+    if (blocks.empty()) return;
+    DeviceGuard dg;
+    if (dg.set(device) == hipSuccess) for (const Block& b : blocks) (void)hipFree(b.p);
+    blocks.clear(); sum = 0;
+  }
+  template <class T> int alloc(T** out, size_t n) {   // n elements, 16 bytes at least
+    if (device < 0) HIP_TRY(hipGetDevice(&device));
+    void* p = nullptr;
+    const size_t bytes = std::max<size_t>(n * sizeof(T), 16);
+    const hipError_t e = hipMalloc(&p, bytes);
+    if (e != hipSuccess) { set_error(std::string("hipMalloc: ") + hipGetErrorString(e)); return SG_E_NOMEM; }
+    blocks.push_back(Block{p, bytes});
+    sum += bytes;
+    *out = (T*)p;
+    return SG_OK;
+  }
+  // a block holding src[0 .. n): copied before the call returns, or on `st` when one is given (the caller synchronises it)
+  template <class T> int upload(const T* src, size_t n, const T** out, hipStream_t st = nullptr) {
+    T* p = nullptr;
+    if (int rc = alloc(&p, n)) return rc;
+    if (n && st) HIP_TRY(hipMemcpyAsync(p, src, n * sizeof(T), hipMemcpyHostToDevice, st));
+    else if (n) HIP_TRY(hipMemcpy(p, src, n * sizeof(T), hipMemcpyHostToDevice));
+    *out = p;
+    return SG_OK;
+  }
+  template <class T> int upload(const std::vector<T>& src, const T** out, hipStream_t st = nullptr) { return upload(src.data(), src.size(), out, st); }
+  const Block* find(const void* p) const { for (const Block& b : blocks) if (b.p == p) return &b; return nullptr; }
+  size_t bytes_of(const void* p) const { const Block* b = find(p); return b ? b->bytes : 0; }   // 0: not a block of this owner
+  uint64_t total() const { return sum; }
+  void release(const void* p) {   // frees one block (null or unknown: nothing)
+    const Block* b = p ? find(p) : nullptr;
+    if (!b) return;
+    DeviceGuard dg;
+    if (dg.set(device) == hipSuccess) (void)hipFree(b->p);
+    sum -= b->bytes;
+    blocks.erase(blocks.begin() + (b - blocks.data()));
+  }
+};
+
+// hipcub's two-call idiom, once: ask for the working memory's size, take it from `mem` (it goes when `mem` goes), run.  A loop that
+// runs one sort or scan many times over one working block (lm_build.inc, lm_store.inc) calls hipcub itself.
+template <class T>
+int device_exclusive_sum(DeviceBlock& mem, const T* in, T* out, size_t n, hipStream_t st = nullptr) {
+  size_t tb = 0;
+  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, in, out, (int)n, st));
+  uint8_t* tmp;
+  if (int rc = mem.alloc(&tmp, tb)) return rc;
+  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(tmp, tb, in, out, (int)n, st));
+  return SG_OK;
+}
+template <class K, class V>   // stable, ascending by bits [begin_bit, end_bit) of the keys
+int device_sort_pairs(DeviceBlock& mem, const K* keys_in, K* keys_out, const V* vals_in, V* vals_out, size_t n, int begin_bit = 0,
+                      int end_bit = 8 * (int)sizeof(K), hipStream_t st = nullptr) {
+  size_t tb = 0;
+  HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, keys_in, keys_out, vals_in, vals_out, (int)n, begin_bit, end_bit, st));
+  uint8_t* tmp;
+  if (int rc = mem.alloc(&tmp, tb)) return rc;
+  HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, tb, keys_in, keys_out, vals_in, vals_out, (int)n, begin_bit, end_bit, st));
+  return SG_OK;
+}
+// the sum of val[0 .. n) from its exclusive prefix sums: last prefix + last value (n >= 1)
+template <class Out>
+int device_total(const uint32_t* val, const uint32_t* pre, size_t n, Out* out) {
+  uint32_t a = 0, b = 0;
+  HIP_TRY(hipMemcpy(&a, val + n - 1, 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(&b, pre + n - 1, 4, hipMemcpyDeviceToHost));
+  *out = (Out)a + b;
+  return SG_OK;
+}
+
+using clk = std::chrono::steady_clock;   // the stopwatch of the store / load codecs' phase times
+inline double since(clk::time_point t) { return std::chrono::duration<double>(clk::now() - t).count(); }
 
 // ---- the launch controllers (plan_launch): each reads the words of the replica's statistics block it needs from the host's copy,
 // and keeps what it saw last ----
@@ -119,9 +209,7 @@ struct ShapeFloor {
 struct Replica {
   int device = -1;
   DeviceIndex dix{};
-  std::vector<void*> allocs;
-  std::vector<size_t> alloc_bytes;
-  uint64_t device_bytes = 0;
+  DeviceBlock mem;                     // every array of dix and the working memory below: mem.total() is the replica's device_bytes
   // working memory of sg_long_kernel (queries with more than SG_MAX_A n-grams): SG_LONG_SLOTS slots + a lock word each
   uint8_t* long_scratch = nullptr; uint32_t* long_lock = nullptr; uint64_t long_slot_bytes = 0; uint32_t long_max_seg = 0;
   const uint32_t* x_of = nullptr;      // [n_docs] docID -> the packed store's number (packed_store.inc; introspection only)
@@ -176,6 +264,7 @@ struct sg_lm {
   std::atomic<int> refs{1};
   std::mutex mu;                       // guards the lazy upload
   int device = -1;
+  DeviceBlock mem;                     // owns every d_* array below (they are views into it)
   uint64_t* d_values = nullptr;        // every level's (word << 32 | count), level after level
   uint32_t* d_child_begin = nullptr;   // every level's bucket offsets, level after level
   std::vector<uint32_t> level_base;    // first entry of level l in d_values
@@ -191,31 +280,19 @@ struct sg_lm {
   uint32_t slot_mul = 2;
 };
 
+// A reference on an index or a language model that goes at the end of the scope: hold(h) takes one for the duration of a call,
+// Held<H>(h) adopts one the caller already has.
+struct HandleRelease {
+  void operator()(sg_index* i) const { sg_index_release(i); }
+  void operator()(sg_lm* l) const { sg_lm_release(l); }
+};
+template <class H> using Held = std::unique_ptr<H, HandleRelease>;
+inline Held<sg_index> hold(sg_index* i) { sg_index_retain(i); return Held<sg_index>(i); }
+inline Held<sg_lm> hold(sg_lm* l) { sg_lm_retain(l); return Held<sg_lm>(l); }
+
 static void* g_prof_buf = nullptr;   // SG_PHASE_TIMING builds only (sg_debug_set_prof)
 
 namespace {
-
-template <class T>
-int dev_alloc(Replica* r, size_t n, T** out) {
-  void* p = nullptr;
-  const size_t bytes = std::max<size_t>(n * sizeof(T), 16);
-  HIP_TRY(hipMalloc(&p, bytes));
-  r->allocs.push_back(p);
-  r->alloc_bytes.push_back(bytes);
-  r->device_bytes += bytes;
-  *out = (T*)p;
-  return SG_OK;
-}
-
-template <class T>
-int to_device(Replica* r, const T* src, size_t n, const T** out) {
-  T* p = nullptr;
-  int rc = dev_alloc(r, n, &p);
-  if (rc) return rc;
-  if (n) HIP_TRY(hipMemcpy(p, src, n * sizeof(T), hipMemcpyHostToDevice));
-  *out = p;
-  return SG_OK;
-}
 
 struct LowerPair { uint32_t from, to; };
 const LowerPair kLowerPairs[] = {
@@ -237,17 +314,17 @@ void lm_alphabet_tables(const std::vector<std::string>& spec, uint64_t ascii[2],
 }
 
 // symbol tables, lower-case table, wrap and pad of the description: what the device tokeniser reads
-int upload_description(const HostIndex& h, Replica* r, DeviceIndex& d) {
+int upload_description(const HostIndex& h, DeviceBlock& mem, DeviceIndex& d) {
   int rc;
-  if ((rc = to_device(r, h.sym.ascii_sym, 128, &d.ascii_sym))) return rc;
-  if ((rc = to_device(r, h.sym.ascii_alpha, 128, &d.ascii_alpha))) return rc;
-  if ((rc = to_device(r, h.sym.na_rune.data(), h.sym.na_rune.size(), &d.na_rune))) return rc;
-  if ((rc = to_device(r, h.sym.na_sym.data(), h.sym.na_sym.size(), &d.na_sym))) return rc;
-  if ((rc = to_device(r, h.sym.na_alpha.data(), h.sym.na_alpha.size(), &d.na_alpha))) return rc;
+  if ((rc = mem.upload(h.sym.ascii_sym, 128, &d.ascii_sym))) return rc;
+  if ((rc = mem.upload(h.sym.ascii_alpha, 128, &d.ascii_alpha))) return rc;
+  if ((rc = mem.upload(h.sym.na_rune, &d.na_rune))) return rc;
+  if ((rc = mem.upload(h.sym.na_sym, &d.na_sym))) return rc;
+  if ((rc = mem.upload(h.sym.na_alpha, &d.na_alpha))) return rc;
   std::vector<uint32_t> lf, lt;
   for (const auto& p : kLowerPairs) { lf.push_back(p.from); lt.push_back(p.to); }
-  if ((rc = to_device(r, lf.data(), lf.size(), &d.lower_from))) return rc;
-  if ((rc = to_device(r, lt.data(), lt.size(), &d.lower_to))) return rc;
+  if ((rc = mem.upload(lf, &d.lower_from))) return rc;
+  if ((rc = mem.upload(lt, &d.lower_to))) return rc;
   d.n_na = (uint32_t)h.sym.na_rune.size();
   d.n_lower = (uint32_t)lf.size();
   d.q = h.q;
@@ -906,8 +983,8 @@ int fill_replica(sg_index* ix, Replica* r, int device) {
   int rc;
   // the u32 CSR goes up (or is already there), the forward index is derived from it, then the store is packed and the u32
   // arrays are freed (packed_store.inc): what stays resident is ~0.57x the u32 store + the forward index
-  if (!d.postings && (rc = to_device(r, h.postings.data(), h.postings.size(), &d.postings))) return rc;
-  if (!d.seg_off && (rc = to_device(r, h.seg_off.data(), h.seg_off.size(), &d.seg_off))) return rc;
+  if (!d.postings && (rc = r->mem.upload(h.postings, &d.postings))) return rc;
+  if (!d.seg_off && (rc = r->mem.upload(h.seg_off, &d.seg_off))) return rc;
   if ((rc = build_forward_index(h, r))) return rc;
   if ((rc = pack_store(h, r, ix->knobs.g8))) return rc;
   {  // long-query working memory: sized by the largest cardinality segment (one counter per document of a segment)
@@ -918,14 +995,14 @@ int fill_replica(sg_index* ix, Replica* r, int device) {
     r->long_max_seg = max_seg;
     r->long_slot_bytes = LongSlot::bytes(max_seg);
     if (!env_int("SG_NO_LONG_QUERIES", 0, 1, 0)) {
-      if ((rc = dev_alloc(r, (size_t)(r->long_slot_bytes * SG_LONG_SLOTS), &r->long_scratch))) return rc;
-      if ((rc = dev_alloc(r, (size_t)SG_LONG_SLOTS + 4, &r->long_lock))) return rc;
+      if ((rc = r->mem.alloc(&r->long_scratch, (size_t)(r->long_slot_bytes * SG_LONG_SLOTS)))) return rc;
+      if ((rc = r->mem.alloc(&r->long_lock, (size_t)SG_LONG_SLOTS + 4))) return rc;
       HIP_TRY(hipMemset(r->long_lock, 0, (SG_LONG_SLOTS + 4) * 4));
     }
   }
-  if ((rc = to_device(r, h.slots.data(), h.slots.size(), &d.slots))) return rc;
-  if ((rc = upload_description(h, r, d))) return rc;
-  if ((rc = dev_alloc(r, (size_t)SG_STAT_WORDS, &r->d_fill))) return rc;     // the statistics block (StatWord: the 64-bit chunk counter 8-byte aligned)
+  if ((rc = r->mem.upload(h.slots, &d.slots))) return rc;
+  if ((rc = upload_description(h, r->mem, d))) return rc;
+  if ((rc = r->mem.alloc(&r->d_fill, (size_t)SG_STAT_WORDS))) return rc;     // the statistics block (StatWord: the 64-bit chunk counter 8-byte aligned)
   HIP_TRY(hipMemset(r->d_fill, 0, SG_STAT_WORDS * 4));
   HIP_TRY(hipHostMalloc((void**)&r->h_fill, SG_STAT_WORDS * 4, hipHostMallocMapped));
   for (int i = 0; i < SG_STAT_WORDS; i++) r->h_fill[i] = 0;
@@ -942,16 +1019,16 @@ int fill_replica(sg_index* ix, Replica* r, int device) {
     }
     std::sort(ddocs.begin(), ddocs.end());
     ddocs.erase(std::unique(ddocs.begin(), ddocs.end()), ddocs.end());
-    if ((rc = to_device(r, dts.data(), dts.size(), &d.dup_ts))) return rc;
-    if ((rc = to_device(r, ddoc.data(), ddoc.size(), &d.dup_doc))) return rc;
-    if ((rc = to_device(r, dmult.data(), dmult.size(), &d.dup_mult))) return rc;
-    if ((rc = to_device(r, ddocs.data(), ddocs.size(), &d.dup_docs))) return rc;
+    if ((rc = r->mem.upload(dts, &d.dup_ts))) return rc;
+    if ((rc = r->mem.upload(ddoc, &d.dup_doc))) return rc;
+    if ((rc = r->mem.upload(dmult, &d.dup_mult))) return rc;
+    if ((rc = r->mem.upload(ddocs, &d.dup_docs))) return rc;
     std::vector<uint32_t> dbits((size_t)(h.n_docs + 31) / 32 + 1, 0u);
     for (uint32_t dd : ddocs) if ((size_t)(dd >> 5) < dbits.size()) dbits[dd >> 5] |= 1u << (dd & 31u);
-    if ((rc = to_device(r, dbits.data(), dbits.size(), &d.dup_bits))) return rc;
-    if ((rc = to_device(r, ets.data(), ets.size(), &d.extra_ts))) return rc;
-    if ((rc = to_device(r, ecnt.data(), ecnt.size(), &d.extra_cnt))) return rc;
-    if ((rc = to_device(r, h.list_len.data(), h.list_len.size(), &d.list_len))) return rc;
+    if ((rc = r->mem.upload(dbits, &d.dup_bits))) return rc;
+    if ((rc = r->mem.upload(ets, &d.extra_ts))) return rc;
+    if ((rc = r->mem.upload(ecnt, &d.extra_cnt))) return rc;
+    if ((rc = r->mem.upload(h.list_len, &d.list_len))) return rc;
     d.n_dups = (uint32_t)dts.size(); d.n_dup_docs = (uint32_t)ddocs.size(); d.n_extra = (uint32_t)ets.size();
   }
   d.slot_mask = (uint32_t)h.slots.size() - 1;
@@ -972,11 +1049,6 @@ int fill_replica(sg_index* ix, Replica* r, int device) {
   HIP_TRY(hipFuncSetAttribute((const void*)sg_parts_kernel_g8, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes(14, SG_K_LDS, true)));
   HIP_TRY(hipFuncSetAttribute((const void*)sg_parts_kernel_tight_g8, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes(14, SG_K_LDS, true)));
   HIP_TRY(hipFuncSetAttribute((const void*)sg_lm_kernel_g8, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes(14, SG_K_LDS, true)));
-  {  // per-launch scratch comes from the device's stream-ordered pool: keep freed blocks instead of returning them
-    hipMemPool_t pool;
-    uint64_t keep = ~0ull;
-    if (hipDeviceGetDefaultMemPool(&pool, device) == hipSuccess) (void)hipMemPoolSetAttribute(pool, hipMemPoolAttrReleaseThreshold, &keep);
-  }
   HIP_TRY(hipDeviceSynchronize());
   return SG_OK;
 }
@@ -1175,9 +1247,8 @@ int sg_debug_index_array(sg_index* ix, uint32_t replica, uint32_t which, void* o
       case 7: src = d.fwd_terms; bytes = ~0ull; break;           // (the same: a whole number of 16-byte chunks)
       default: src = d.fx_base; bytes = src ? (S + 1) * 4 : 0; break;
     }
-    if (bytes) {    // every array is one allocation of the replica: never read past what dev_alloc gave it
-      uint64_t have = 0;
-      for (size_t i = 0; i < r->allocs.size(); i++) if (r->allocs[i] == src) have = r->alloc_bytes[i];
+    if (bytes) {    // every array is one block of the replica: never read past what it was allocated with
+      const uint64_t have = r->mem.bytes_of(src);
       if (bytes == ~0ull) bytes = have;
       if (!src || bytes > have) { set_error("sg_debug_index_array: the array is not an allocation of the replica"); return SG_E_INVALID; }
     }
@@ -1644,7 +1715,7 @@ struct sg_metric_tables {
   sg_index* index = nullptr;           // (retained: the tables live in its primary replica's HBM)
   int device = -1;
   MetricTab tab{};
-  void* block = nullptr;
+  DeviceBlock mem;                     // one block: tab's arrays are views into it
   std::atomic<int> refs{1};
 };
 
@@ -1667,10 +1738,9 @@ int sg_metric_tables_create(sg_index* index, uint32_t a_max, const int32_t* min_
   DeviceGuard dg;
   HIP_TRY(dg.set(rep->device));
   const size_t o_max = (n_a * 4 + 15) & ~(size_t)15, o_thr = 2 * o_max, o_sc = (o_thr + n_thr * 4 + 15) & ~(size_t)15, total = o_sc + n_sc * 8;
-  std::unique_ptr<sg_metric_tables> t(new sg_metric_tables());
-  HIP_TRY(hipMalloc(&t->block, total));
-  char* b = (char*)t->block;
-  struct Guard { void* p; bool keep = false; ~Guard() { if (!keep) (void)hipFree(p); } } guard{t->block};
+  std::unique_ptr<sg_metric_tables> t(new sg_metric_tables());   // (a step that fails below frees it, its block included)
+  char* b = nullptr;
+  if (int rc = t->mem.alloc(&b, total)) return rc;
   HIP_TRY(hipMemcpy(b, min_y, n_a * 4, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(b + o_max, max_y, n_a * 4, hipMemcpyHostToDevice));
   if (n_thr) HIP_TRY(hipMemcpy(b + o_thr, threshold, n_thr * 4, hipMemcpyHostToDevice));
@@ -1678,7 +1748,6 @@ int sg_metric_tables_create(sg_index* index, uint32_t a_max, const int32_t* min_
   t->tab.min_y = (const int32_t*)b; t->tab.max_y = (const int32_t*)(b + o_max); t->tab.thr = (const int32_t*)(b + o_thr);
   t->tab.score = (const double*)(b + o_sc); t->tab.a_max = a_max; t->tab.S = S;
   t->device = rep->device;
-  guard.keep = true;
   sg_index_retain(index);
   t->index = index;
   *out = t.release();
@@ -1691,12 +1760,9 @@ int sg_metric_tables_create(sg_index* index, uint32_t a_max, const int32_t* min_
 void sg_metric_tables_retain(sg_metric_tables* t) { if (t) t->refs.fetch_add(1); }
 void sg_metric_tables_release(sg_metric_tables* t) {
   if (!t || t->refs.fetch_sub(1) != 1) return;
-  {
-    DeviceGuard dg;
-    if (dg.set(t->device) == hipSuccess) (void)hipFree(t->block);
-  }
-  sg_index_release(t->index);
-  delete t;
+  sg_index* index = t->index;
+  delete t;                            // (the block goes before the index that holds its device's replica)
+  sg_index_release(index);
 }
 
 static int check_tables(sg_index* index, const sg_metric_tables* tables) {
@@ -1776,7 +1842,7 @@ struct AsyncPool {
 };
 Replica::~Replica() {
   delete async_pool;
-  if (device >= 0 && !allocs.empty()) { (void)hipSetDevice(device); for (void* p : allocs) (void)hipFree(p); }
+  mem.clear();
   if (h_fill) (void)hipHostFree(h_fill);
 }
 
@@ -1908,7 +1974,7 @@ int sg_ticket_wait(sg_ticket* t) {
   SG_GUARD_BEGIN
   if (!t) { set_error("null ticket"); return SG_E_INVALID; }
   std::unique_ptr<sg_ticket> own(t);
-  struct Release { sg_index* i; ~Release() { sg_index_release(i); } } release{t->index};
+  const Held<sg_index> release(t->index);                      // (the reference the submit took)
   if (t->slot < 0) return SG_OK;                               // an empty batch
   AsyncSlot* sl = &t->rep->async_pool->slot[t->slot];
   struct Unbusy { Replica* r; AsyncSlot* s; ~Unbusy() { std::lock_guard<std::mutex> lock(r->async_mu); s->busy = false; } } unbusy{t->rep, sl};
@@ -2341,11 +2407,6 @@ int sg_debug_lm_build_hash_bits(uint32_t bits) {
 void sg_lm_retain(sg_lm* lm) { if (lm) lm->refs.fetch_add(1); }
 void sg_lm_release(sg_lm* lm) {
   if (!lm || lm->refs.fetch_sub(1) != 1) return;
-  if (lm->d_values) {
-    (void)hipSetDevice(lm->device); (void)hipFree(lm->d_values); (void)hipFree(lm->d_child_begin);
-    (void)hipFree(lm->d_alpha_ranges); (void)hipFree(lm->d_vocab); (void)hipFree(lm->d_vocab_bytes); (void)hipFree(lm->d_vocab_off);
-    (void)hipFree(lm->d_lower_from); (void)hipFree(lm->d_lower_to);
-  }
   delete lm;
 }
 uint32_t sg_lm_num_words(const sg_lm* lm) { return lm ? (uint32_t)lm->host.words.size() : 0u; }
@@ -2396,8 +2457,8 @@ static int lm_upload(sg_lm* lm, int device) {
     if (lm->device != device) { set_error("language model already resident on another device"); return SG_E_INVALID; }
     return SG_OK;
   }
-  // (built into locals and RAII-owned device buffers, committed to the handle only when every step has succeeded: a
-  //  failed upload leaks nothing and a retry starts from a clean handle; the caller's current device is restored)
+  // (built into locals and a local DeviceBlock, committed to the handle only when every step has succeeded: a failed
+  //  upload leaks nothing and a retry starts from a clean handle; the caller's current device is restored)
   std::vector<uint64_t> flat;
   std::vector<uint32_t> cb, level_base, cb_base;
   for (const LmLevel& lv : lm->host.level) {
@@ -2409,24 +2470,18 @@ static int lm_upload(sg_lm* lm, int device) {
   if (flat.size() >= 0xFFFFFFF0ull) { set_error("language model too large"); return SG_E_UNSUPPORTED; }
   DeviceGuard dg;
   HIP_TRY(dg.set(device));
-  struct Owned {                                     // device blocks of an upload in progress
-    std::vector<void*> p; bool keep = false;
-    ~Owned() { if (!keep) for (void* x : p) (void)hipFree(x); }
-  } owned;
-#define LM_ALLOC(ptr, bytes) do { HIP_TRY(hipMalloc(&(ptr), (bytes))); owned.p.push_back(ptr); } while (0)
-  void *p = nullptr, *q = nullptr;
-  LM_ALLOC(p, std::max<size_t>(flat.size() * 8, 16));
-  if (!flat.empty()) HIP_TRY(hipMemcpy(p, flat.data(), flat.size() * 8, hipMemcpyHostToDevice));
-  LM_ALLOC(q, std::max<size_t>(cb.size() * 4, 16));
-  if (!cb.empty()) HIP_TRY(hipMemcpy(q, cb.data(), cb.size() * 4, hipMemcpyHostToDevice));
+  DeviceBlock mem;                                   // the device blocks of an upload in progress
+  int rc;
+  const uint64_t* p = nullptr;
+  const uint32_t* q = nullptr;
+  if ((rc = mem.upload(flat, &p)) || (rc = mem.upload(cb, &q))) return rc;
   {  // the word tokeniser's tables: alphabet membership (bitmap below 128, inclusive ranges above) ...
     const HostLM& h = lm->host;
     std::vector<uint2> ranges;
     uint64_t alpha_ascii[2] = {0, 0};
     lm_alphabet_tables(h.alphabet, alpha_ascii, ranges);
-    void* ar = nullptr;
-    LM_ALLOC(ar, std::max<size_t>(ranges.size() * 8, 16));
-    if (!ranges.empty()) HIP_TRY(hipMemcpy(ar, ranges.data(), ranges.size() * 8, hipMemcpyHostToDevice));
+    const uint2* ar = nullptr;
+    if ((rc = mem.upload(ranges, &ar))) return rc;
     // ... and the vocabulary: open addressing on a 64-bit hash of the word bytes (FNV-1a, then the splitmix finaliser —
     // d_word_id in engine.hip computes the same), load <= 0.5; a hit is confirmed on the bytes, so the ids are exact.
     // Words that occur twice keep their first id, like the host's id_of.emplace.
@@ -2452,24 +2507,16 @@ static int lm_upload(sg_lm* lm, int device) {
       }
       if (!dup) table[sidx] = make_uint4((uint32_t)hh, (uint32_t)(hh >> 32), (uint32_t)i, 0u);
     }
-    void *vt = nullptr, *vb = nullptr, *vo = nullptr;
-    LM_ALLOC(vt, cap * 16);
-    HIP_TRY(hipMemcpy(vt, table.data(), cap * 16, hipMemcpyHostToDevice));
-    LM_ALLOC(vb, std::max<size_t>(bytes.size(), 16));
-    if (!bytes.empty()) HIP_TRY(hipMemcpy(vb, bytes.data(), bytes.size(), hipMemcpyHostToDevice));
-    LM_ALLOC(vo, (nw + 1) * 4);
-    HIP_TRY(hipMemcpy(vo, off.data(), (nw + 1) * 4, hipMemcpyHostToDevice));
+    const uint4* vt = nullptr;
+    const uint8_t* vb = nullptr;
+    const uint32_t *vo = nullptr, *lfd = nullptr, *ltd = nullptr;
+    if ((rc = mem.upload(table, &vt)) || (rc = mem.upload((const uint8_t*)bytes.data(), bytes.size(), &vb)) || (rc = mem.upload(off, &vo))) return rc;
     // ... and, for sentence scoring, the simple lower-case pairs (Predict takes the index replica's)
     std::vector<uint32_t> lf, lt;
     for (const auto& pr : kLowerPairs) { lf.push_back(pr.from); lt.push_back(pr.to); }
-    void *lfd = nullptr, *ltd = nullptr;
-    LM_ALLOC(lfd, lf.size() * 4);
-    HIP_TRY(hipMemcpy(lfd, lf.data(), lf.size() * 4, hipMemcpyHostToDevice));
-    LM_ALLOC(ltd, lt.size() * 4);
-    HIP_TRY(hipMemcpy(ltd, lt.data(), lt.size() * 4, hipMemcpyHostToDevice));
-#undef LM_ALLOC
+    if ((rc = mem.upload(lf, &lfd)) || (rc = mem.upload(lt, &ltd))) return rc;
     // ---- every step succeeded: commit ----
-    owned.keep = true;
+    lm->mem = std::move(mem);
     lm->n_alpha_ranges = (uint32_t)ranges.size();
     lm->d_alpha_ranges = (uint2*)ar;
     lm->alpha_ascii[0] = alpha_ascii[0]; lm->alpha_ascii[1] = alpha_ascii[1];
@@ -2492,6 +2539,22 @@ static int lm_upload(sg_lm* lm, int device) {
   return SG_OK;
 }
 
+// What Predict and sentence scoring pass to their kernels alike: the model's levels, the alphabet and the vocabulary.
+static SpellArgs lm_spell_args(const sg_lm* lm) {
+  const HostLM& h = lm->host;
+  SpellArgs p{};
+  p.values = lm->d_values; p.child_begin = lm->d_child_begin;
+  for (size_t l = 0; l < h.level.size(); l++) {
+    p.level_base[l] = lm->level_base[l]; p.cb_base[l] = lm->cb_base[l];
+    p.n_parents[l] = l ? (uint32_t)h.level[l - 1].word.size() : 0u;
+  }
+  p.order = h.order;
+  p.alpha_ranges = lm->d_alpha_ranges; p.n_alpha_ranges = lm->n_alpha_ranges; p.alpha_ascii[0] = lm->alpha_ascii[0]; p.alpha_ascii[1] = lm->alpha_ascii[1];
+  p.vocab = lm->d_vocab; p.vocab_mask = lm->vocab_mask; p.vocab_bytes = lm->d_vocab_bytes; p.vocab_off = lm->d_vocab_off;
+  p.start_symbol = h.start_symbol;
+  return p;
+}
+
 // SpellChecker.Predict (pkg/spellchecker/spellchecker.go:40-92) for a batch, on the device end to end: six launches on the
 // caller's stream —
 //   spell_tokenize_kernel   the word tokeniser, the word ids (vocabulary hash) and the wrap / trim rules of
@@ -2504,7 +2567,6 @@ static int lm_upload(sg_lm* lm, int device) {
 // Everything it needs in between lives in one block of the calling thread's per-stream scratch.
 static int predict_on_device(sg_index* index, sg_lm* lm, Replica* rep, const uint8_t* d_q, const uint64_t* d_offs, uint32_t n_q, uint64_t q_bytes,
                              uint32_t top_k, double similarity, uint32_t* d_out_ids, uint32_t* d_out_counts, hipStream_t st) {
-  const HostLM& h = lm->host;
   Carve c;
   const size_t o_aids = c.take((size_t)n_q * top_k * 4), o_acnt = c.take((size_t)n_q * 4), o_fids = c.take((size_t)n_q * top_k * 4), o_fcnt = c.take((size_t)n_q * 4),
                o_zero_end = c.size(),
@@ -2519,21 +2581,14 @@ static int predict_on_device(sg_index* index, sg_lm* lm, Replica* rep, const uin
     if (int rc = poison_fill(dev + o_aids, (size_t)n_q * top_k * 4, PZ_PREDICT, st)) return rc;
     if (int rc = poison_fill(dev + o_fids, (size_t)n_q * top_k * 4, PZ_PREDICT, st)) return rc;
   }
-  SpellArgs p{};
-  p.values = lm->d_values; p.child_begin = lm->d_child_begin;
-  for (size_t l = 0; l < h.level.size(); l++) {
-    p.level_base[l] = lm->level_base[l]; p.cb_base[l] = lm->cb_base[l];
-    p.n_parents[l] = l ? (uint32_t)h.level[l - 1].word.size() : 0u;
-  }
-  p.order = h.order; p.n_q = n_q; p.top_k = top_k;
+  SpellArgs p = lm_spell_args(lm);
+  p.n_q = n_q; p.top_k = top_k;
   p.q_blob = d_q; p.q_offs = d_offs;
   p.ctx_w = (uint32_t*)(dev + o_ctx); p.ctx_len_w = (uint8_t*)(dev + o_clen); p.has_word_w = (uint8_t*)(dev + o_hasw);
   p.ctx = p.ctx_w; p.ctx_len = p.ctx_len_w; p.has_word = p.has_word_w;
   p.w_blob = (uint8_t*)(dev + o_words); p.w_off = (uint64_t*)(dev + o_woff); p.w_len = (uint32_t*)(dev + o_wlen);
-  p.alpha_ranges = lm->d_alpha_ranges; p.n_alpha_ranges = lm->n_alpha_ranges; p.alpha_ascii[0] = lm->alpha_ascii[0]; p.alpha_ascii[1] = lm->alpha_ascii[1];
-  p.lower_from = rep->dix.lower_from; p.lower_to = rep->dix.lower_to; p.n_lower = rep->dix.n_lower;
-  p.vocab = lm->d_vocab; p.vocab_mask = lm->vocab_mask; p.vocab_bytes = lm->d_vocab_bytes; p.vocab_off = lm->d_vocab_off;
-  p.start_symbol = h.start_symbol; p.slot_mul = lm->slot_mul;
+  p.lower_from = rep->dix.lower_from; p.lower_to = rep->dix.lower_to; p.n_lower = rep->dix.n_lower;   // (the index replica's table)
+  p.slot_mul = lm->slot_mul;
   p.lm_from = (uint32_t*)(dev + o_from); p.lm_to = (uint32_t*)(dev + o_to); p.status = (uint8_t*)(dev + o_stat);
   p.a_ids = (const uint32_t*)(dev + o_aids); p.a_cnt = (const uint32_t*)(dev + o_acnt);
   p.f_ids = (const uint32_t*)(dev + o_fids); p.f_cnt = (const uint32_t*)(dev + o_fcnt);
@@ -2579,8 +2634,8 @@ int sg_spell_predict_batch_device(sg_index* index, sg_lm* lm, const void* d_q, c
   int rc = predict_check(index, lm, d_offs, d_out_ids, d_out_counts, top_k, similarity);
   if (rc) return rc;
   if (n_q == 0) return SG_OK;
-  sg_index_retain(index); sg_lm_retain(lm);
-  struct Release { sg_index* i; sg_lm* l; ~Release() { sg_lm_release(l); sg_index_release(i); } } release{index, lm};
+  const auto held_index = hold(index);
+  const auto held_lm = hold(lm);
   Replica* rep = find_replica(index, -1);
   if ((rc = lm_upload(lm, rep->device))) return rc;
   DeviceGuard dg;
@@ -2597,8 +2652,8 @@ int sg_spell_predict_batch(sg_index* index, sg_lm* lm, const uint8_t* q_utf8, co
   int rc = predict_check(index, lm, q_offs, out_ids, out_counts, top_k, similarity);
   if (rc) return rc;
   if (n_q == 0) return SG_OK;
-  sg_index_retain(index); sg_lm_retain(lm);
-  struct Release { sg_index* i; sg_lm* l; ~Release() { sg_lm_release(l); sg_index_release(i); } } release{index, lm};
+  const auto held_index = hold(index);
+  const auto held_lm = hold(lm);
   Replica* rep = find_replica(index, -1);
   if ((rc = lm_upload(lm, rep->device))) return rc;
   const HostBufs b{q_utf8, q_offs, n_q, top_k + 1, out_ids, nullptr, out_counts, nullptr};
@@ -2619,16 +2674,9 @@ static int lm_score_on_device(sg_lm* lm, int device, bool is_text, const uint8_t
   const HostLM& h = lm->host;
   LmScoreArgs a{};
   SpellArgs& p = a.sp;
-  p.values = lm->d_values; p.child_begin = lm->d_child_begin;
-  for (size_t l = 0; l < h.level.size(); l++) {
-    p.level_base[l] = lm->level_base[l]; p.cb_base[l] = lm->cb_base[l];
-    p.n_parents[l] = l ? (uint32_t)h.level[l - 1].word.size() : 0u;
-  }
-  p.order = h.order; p.n_q = n;
-  p.alpha_ranges = lm->d_alpha_ranges; p.n_alpha_ranges = lm->n_alpha_ranges; p.alpha_ascii[0] = lm->alpha_ascii[0]; p.alpha_ascii[1] = lm->alpha_ascii[1];
-  p.lower_from = lm->d_lower_from; p.lower_to = lm->d_lower_to; p.n_lower = lm->n_lower;
-  p.vocab = lm->d_vocab; p.vocab_mask = lm->vocab_mask; p.vocab_bytes = lm->d_vocab_bytes; p.vocab_off = lm->d_vocab_off;
-  p.start_symbol = h.start_symbol;
+  p = lm_spell_args(lm);
+  p.n_q = n;
+  p.lower_from = lm->d_lower_from; p.lower_to = lm->d_lower_to; p.n_lower = lm->n_lower;   // (the model's own table)
   p.q_blob = text;
   a.n = n; a.end_symbol = h.end_symbol; a.total0 = (uint32_t)h.level[0].total; a.n_uni = (uint32_t)h.level[0].word.size();
   a.uni_dense = lm->uni_dense ? 1u : 0u; a.text = is_text ? 1u : 0u; a.slot_mul = lm->slot_mul; a.text_bytes = text_bytes;
@@ -2676,8 +2724,7 @@ int sg_lm_score_text_batch(sg_lm* lm, int device, const uint8_t* text, const uin
   if (rc) return rc;
   if (n == 0) return SG_OK;
   if ((rc = lm_check_offsets(text, offs, n, kLmTextMax))) return rc;
-  sg_lm_retain(lm);
-  struct Release { sg_lm* l; ~Release() { sg_lm_release(l); } } release{lm};
+  const auto held_lm = hold(lm);
   if ((rc = lm_upload(lm, device))) return rc;
   std::vector<uint32_t> words_tmp, unknown_tmp;                  // (the host-buffer path copies both rows back)
   if (!out_words) { words_tmp.resize(n); out_words = words_tmp.data(); }
@@ -2698,8 +2745,7 @@ int sg_lm_score_text_batch_device(sg_lm* lm, int device, const void* d_text, con
   if (n == 0) return SG_OK;
   if (!d_text && text_bytes) { set_error("null text"); return SG_E_INVALID; }
   if (text_bytes > kLmTextMax) { set_error("text batch above 1 GiB"); return SG_E_INVALID; }
-  sg_lm_retain(lm);
-  struct Release { sg_lm* l; ~Release() { sg_lm_release(l); } } release{lm};
+  const auto held_lm = hold(lm);
   if ((rc = lm_upload(lm, device))) return rc;
   DeviceGuard dg;
   HIP_TRY(dg.set(device));
@@ -2714,8 +2760,7 @@ int sg_lm_score_word_ids_batch(sg_lm* lm, int device, const uint32_t* ids, const
   if (rc) return rc;
   if (n == 0) return SG_OK;
   if ((rc = lm_check_offsets(ids, offs, n, (uint64_t)1 << 30))) return rc;
-  sg_lm_retain(lm);
-  struct Release { sg_lm* l; ~Release() { sg_lm_release(l); } } release{lm};
+  const auto held_lm = hold(lm);
   if ((rc = lm_upload(lm, device))) return rc;
   // the host-buffer path moves bytes: the ids as a blob, offsets in bytes from the first sentence's ids on
   std::vector<uint64_t> boffs((size_t)n + 1);
@@ -2735,14 +2780,16 @@ int sg_lm_score_word_ids_batch(sg_lm* lm, int device, const uint32_t* ids, const
 int sg_debug_pairsort(int device, const uint32_t* keys, uint32_t n, uint32_t* out) {
   SG_GUARD_BEGIN
   if (!keys || !out || n > SG_MAX_A) { set_error("bad argument"); return SG_E_INVALID; }
-  HIP_TRY(hipSetDevice(device));
+  DeviceGuard dg;
+  HIP_TRY(dg.set(device));
+  DeviceBlock mem;
   uint32_t *dk = nullptr, *dv = nullptr;
-  HIP_TRY(hipMalloc((void**)&dk, SG_MAX_A * 4)); HIP_TRY(hipMalloc((void**)&dv, SG_MAX_A * 4));
+  int rc;
+  if ((rc = mem.alloc(&dk, SG_MAX_A)) || (rc = mem.alloc(&dv, SG_MAX_A))) return rc;
   HIP_TRY(hipMemcpy(dk, keys, (size_t)n * 4, hipMemcpyHostToDevice));
   hipLaunchKernelGGL(pairsort_test_kernel, dim3(1), dim3(64), 0, 0, dk, n, dv);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpy(out, dv, (size_t)n * 4, hipMemcpyDeviceToHost));
-  (void)hipFree(dk); (void)hipFree(dv);
   return SG_OK;
   SG_GUARD_END(SG_RC)
 }
@@ -2894,7 +2941,7 @@ int sg_index_stats(const sg_index* ix, sg_stats* out) {
   out->posting_bytes = h.postings.size() * 4;
   out->table_bytes = h.seg_off.size() * 4 + h.slots.size() * sizeof(TermSlot);
   out->device_bytes = 0;
-  { std::lock_guard<std::mutex> lock(const_cast<sg_index*>(ix)->mu); for (auto& r : ix->replicas) out->device_bytes += r->device_bytes; }
+  { std::lock_guard<std::mutex> lock(const_cast<sg_index*>(ix)->mu); for (auto& r : ix->replicas) out->device_bytes += r->mem.total(); }
   return SG_OK;
 }
 

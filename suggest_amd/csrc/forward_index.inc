@@ -55,15 +55,14 @@ int build_forward_index(const HostIndex& h, Replica* r) {
   if (S > 0xFFFFu) { set_error("more than 65535 cardinality segments"); return SG_E_UNSUPPORTED; }
   uint2* rec = nullptr;
   int rc;
-  if ((rc = dev_alloc(r, (size_t)n_docs, &rec))) return rc;
+  if ((rc = r->mem.alloc(&rec, (size_t)n_docs))) return rc;
   d.fwd_rec = rec;
-  if (!n_docs || !nT) { uint32_t* t = nullptr; if ((rc = dev_alloc(r, 4, &t))) return rc; d.fwd_terms = t; return SG_OK; }
+  if (!n_docs || !nT) { uint32_t* t = nullptr; if ((rc = r->mem.alloc(&t, 4))) return rc; d.fwd_terms = t; return SG_OK; }
   uint32_t *cnt = nullptr, *card = nullptr, *off = nullptr, *chunks = nullptr;
-  void* tmp = nullptr;
-  struct Free { std::vector<void*> p; ~Free() { for (void* x : p) (void)hipFree(x); } } scratch;
-  auto salloc = [&](void** p, size_t bytes) { hipError_t e = hipMalloc(p, std::max<size_t>(bytes, 16)); if (e == hipSuccess) scratch.p.push_back(*p); return e; };
-  HIP_TRY(salloc((void**)&cnt, (size_t)n_docs * 4)); HIP_TRY(salloc((void**)&card, (size_t)n_docs * 4));
-  HIP_TRY(salloc((void**)&off, ((size_t)n_docs + 1) * 4)); HIP_TRY(salloc((void**)&chunks, ((size_t)n_docs + 1) * 4));
+  DeviceBlock scratch;                                           // freed on return: not part of the replica
+  if ((rc = scratch.alloc(&cnt, (size_t)n_docs)) || (rc = scratch.alloc(&card, (size_t)n_docs)) || (rc = scratch.alloc(&off, (size_t)n_docs + 1)) ||
+      (rc = scratch.alloc(&chunks, (size_t)n_docs + 1)))
+    return rc;
   HIP_TRY(hipMemset(cnt, 0, (size_t)n_docs * 4));
   HIP_TRY(hipMemset(card, 0, (size_t)n_docs * 4));
   const uint64_t n_lists = (uint64_t)nT * S;
@@ -72,17 +71,11 @@ int build_forward_index(const HostIndex& h, Replica* r) {
   HIP_TRY(hipGetLastError());
   hipLaunchKernelGGL(fwd_chunks, dim3((n_docs + 255) / 256), dim3(256), 0, 0, cnt, n_docs, chunks);
   HIP_TRY(hipGetLastError());
-  size_t tb = 0;
-  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, chunks, off, (int)n_docs));
-  HIP_TRY(salloc(&tmp, tb));
-  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(tmp, tb, chunks, off, (int)n_docs));
-  uint32_t last_off = 0, last_chunks = 0;
-  HIP_TRY(hipMemcpy(&last_off, off + (n_docs - 1), 4, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(&last_chunks, chunks + (n_docs - 1), 4, hipMemcpyDeviceToHost));
-  const uint64_t total_chunks = (uint64_t)last_off + last_chunks;
+  uint64_t total_chunks = 0;
+  if ((rc = device_exclusive_sum(scratch, chunks, off, n_docs)) || (rc = device_total(chunks, off, n_docs, &total_chunks))) return rc;
   if ((h.n_postings + 3) / 4 + n_docs >= 0xFFFFFFF0ull) { set_error("forward index exceeds 2^32 16-byte chunks"); return SG_E_UNSUPPORTED; }
   uint32_t* terms = nullptr;
-  if ((rc = dev_alloc(r, (size_t)total_chunks * 4, &terms))) return rc;
+  if ((rc = r->mem.alloc(&terms, (size_t)total_chunks * 4))) return rc;
   HIP_TRY(hipMemset(terms, 0xFF, std::max<size_t>((size_t)total_chunks * 16, 16)));
   hipLaunchKernelGGL(fwd_records, dim3((n_docs + 255) / 256), dim3(256), 0, 0, off, cnt, card, n_docs, rec);
   HIP_TRY(hipGetLastError());

@@ -12,10 +12,9 @@
 //      build_assign      term id written back into the slot
 //   K3 build_emit        one wavefront per document: keys -> term ids, repeated terms of a document folded (side list
 //                        for the reference's duplicate quirk), sort key term*S + cardinality, list_len histogram
-//   K4 hipcub::DeviceRadixSort::SortPairs (stable: docIDs stay ascending inside a list)
+//   K4 device_sort_pairs (hipcub radix sort; stable: docIDs stay ascending inside a list)
 //   K5 two exclusive scans: chunk offsets (lists padded to 16 bytes) and offsets in the sorted stream
 //   K6 build_scatter     sorted stream -> padded posting store; build_seg_off -> seg_off rows
-#include <hipcub/hipcub.hpp>
 
 namespace sg {
 
@@ -217,28 +216,15 @@ __global__ void build_seg_off(const uint32_t* chunk_off, uint32_t n_terms, uint3
 
 namespace {
 
-struct DeviceBlock {   // frees on scope exit
-  std::vector<void*> ptrs;
-  ~DeviceBlock() { for (void* p : ptrs) (void)hipFree(p); }
-  template <class T> int alloc(T** out, size_t n) {
-    void* p = nullptr;
-    hipError_t e = hipMalloc(&p, std::max<size_t>(n * sizeof(T), 16));
-    if (e != hipSuccess) { set_error(std::string("hipMalloc: ") + hipGetErrorString(e)); return SG_E_NOMEM; }
-    ptrs.push_back(p);
-    *out = (T*)p;
-    return SG_OK;
-  }
-};
-
 int build_on_device(sg_index* ix, const uint8_t* utf8, const uint64_t* offs, uint32_t n_docs, int device) {
   HostIndex& h = ix->host;
-  HIP_TRY(hipSetDevice(device));
+  DeviceGuard dg;
+  HIP_TRY(dg.set(device));
   h.n_docs = n_docs;
   BuildArgs b{};
   int rc;
-  Replica tables;                                          // the description tables the tokeniser reads: freed on return
-  tables.device = device;
-  if ((rc = upload_description(h, &tables, b.ix))) return rc;
+  DeviceBlock mem;                                         // working memory, the description tables the tokeniser reads first: freed on return
+  if ((rc = upload_description(h, mem, b.ix))) return rc;
   b.ix.slots = nullptr;
   b.n_docs = n_docs;
   if (n_docs == 0) { h.n_segments = 0; build_term_table(h); return SG_OK; }
@@ -256,7 +242,6 @@ int build_on_device(sg_index* ix, const uint8_t* utf8, const uint64_t* offs, uin
   const uint64_t cap_total = cap_off[n_docs];
   if (cap_total >= 0x7FFFFFF0ull) { set_error("dictionary too large for the device builder"); return SG_E_UNSUPPORTED; }
 
-  DeviceBlock mem;
   uint8_t* d_docs; uint64_t *d_offs, *d_cap;
   uint32_t* d_stats;
   if ((rc = mem.alloc(&d_docs, (size_t)offs[n_docs])) || (rc = mem.alloc(&d_offs, (size_t)n_docs + 1)) ||
@@ -311,13 +296,7 @@ int build_on_device(sg_index* ix, const uint8_t* utf8, const uint64_t* offs, uin
   HIP_TRY(hipMemset(d_counter, 0, 4));
   hipLaunchKernelGGL(build_collect, dim3((unsigned)((n_slots + 255) / 256)), dim3(256), 0, 0, b.table, (uint32_t)n_slots, b.zero_term, d_stamp, d_key, d_counter);
   HIP_TRY(hipGetLastError());
-  {
-    size_t tmp_bytes = 0;
-    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, d_stamp, d_stamp2, d_key, d_key2, (int)n_terms));
-    void* tmp;
-    if ((rc = mem.alloc((uint8_t**)&tmp, tmp_bytes))) return rc;
-    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, tmp_bytes, d_stamp, d_stamp2, d_key, d_key2, (int)n_terms));
-  }
+  if ((rc = device_sort_pairs(mem, d_stamp, d_stamp2, d_key, d_key2, n_terms))) return rc;
   hipLaunchKernelGGL(build_assign, dim3((n_terms + 255) / 256), dim3(256), 0, 0, b.table, b.table_mask, b.zero_term, d_key2, n_terms);
   HIP_TRY(hipGetLastError());
 
@@ -337,13 +316,7 @@ int build_on_device(sg_index* ix, const uint8_t* utf8, const uint64_t* offs, uin
   // K4: stable sort by (term, segment); docIDs were emitted ascending
   uint32_t *d_key_s, *d_doc_s;
   if ((rc = mem.alloc(&d_key_s, (size_t)cap_total)) || (rc = mem.alloc(&d_doc_s, (size_t)cap_total))) return rc;
-  {
-    size_t tmp_bytes = 0;
-    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, b.sort_key, d_key_s, b.sort_doc, d_doc_s, (int)cap_total));
-    void* tmp;
-    if ((rc = mem.alloc((uint8_t**)&tmp, tmp_bytes))) return rc;
-    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, tmp_bytes, b.sort_key, d_key_s, b.sort_doc, d_doc_s, (int)cap_total));
-  }
+  if ((rc = device_sort_pairs(mem, b.sort_key, d_key_s, b.sort_doc, d_doc_s, (size_t)cap_total))) return rc;
 
   // K5
   const uint32_t n_cells = n_terms * S;
@@ -353,15 +326,7 @@ int build_on_device(sg_index* ix, const uint8_t* utf8, const uint64_t* offs, uin
     return rc;
   hipLaunchKernelGGL(build_chunks, dim3((n_cells + 255) / 256), dim3(256), 0, 0, b.list_len, n_cells, d_chunks);
   HIP_TRY(hipGetLastError());
-  {
-    size_t t1 = 0, t2 = 0;
-    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, t1, d_chunks, d_chunk_off, (int)n_cells));
-    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, t2, b.list_len, d_src_off, (int)n_cells));
-    void* tmp;
-    if ((rc = mem.alloc((uint8_t**)&tmp, std::max(t1, t2)))) return rc;
-    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(tmp, t1, d_chunks, d_chunk_off, (int)n_cells));
-    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(tmp, t2, b.list_len, d_src_off, (int)n_cells));
-  }
+  if ((rc = device_exclusive_sum(mem, d_chunks, d_chunk_off, n_cells)) || (rc = device_exclusive_sum(mem, b.list_len, d_src_off, n_cells))) return rc;
   // totals: last offset + last value, summed on the host in 64 bits
   h.list_len.resize(n_cells);
   HIP_TRY(hipMemcpy(h.list_len.data(), b.list_len, (size_t)n_cells * 4, hipMemcpyDeviceToHost));
@@ -374,9 +339,8 @@ int build_on_device(sg_index* ix, const uint8_t* utf8, const uint64_t* offs, uin
   // (no D2H + H2D round trip); the host copy below serves introspection, accounting and replicas on other GPUs
   uint32_t *d_postings, *d_seg_off;
   const size_t seg_n = (size_t)n_terms * (S + 1) + 1;
-  std::unique_ptr<Replica> keep(new Replica());
-  keep->device = device;
-  if ((rc = dev_alloc(keep.get(), (size_t)total_chunks * 4, &d_postings)) || (rc = dev_alloc(keep.get(), seg_n, &d_seg_off))) return rc;
+  DeviceBlock kept;
+  if ((rc = kept.alloc(&d_postings, (size_t)total_chunks * 4)) || (rc = kept.alloc(&d_seg_off, seg_n))) return rc;
   HIP_TRY(hipMemset(d_seg_off, 0, seg_n * 4));
   if (n_valid) {
     hipLaunchKernelGGL(build_scatter, dim3((unsigned)((n_valid + 255) / 256)), dim3(256), 0, 0, d_key_s, d_doc_s, n_valid, b.list_len, d_chunk_off,
@@ -415,6 +379,9 @@ int build_on_device(sg_index* ix, const uint8_t* utf8, const uint64_t* offs, uin
   }
   build_term_table(h);
   HIP_TRY(hipDeviceSynchronize());
+  std::unique_ptr<Replica> keep(new Replica());
+  keep->device = device;
+  keep->mem = std::move(kept);
   keep->dix.postings = d_postings;
   keep->dix.seg_off = d_seg_off;
   ix->prebuilt = std::move(keep);

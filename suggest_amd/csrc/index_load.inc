@@ -378,8 +378,6 @@ uint32_t load_roar_slots(const uint8_t* b, uint64_t n) {  // containers the head
 
 // Steps 2 and 3 with the lists decoded on `device`; seconds: [4] H2D, kernels, D2H, assembly.
 int load_decode_device(HostIndex& ix, const RefFiles& f, int device, std::string& err, double seconds[4]) {
-  using clk = std::chrono::steady_clock;
-  auto since = [](clk::time_point t) { return std::chrono::duration<double>(clk::now() - t).count(); };
   const size_t n = f.lists.size();
   if (n >= (1u << 30)) { err = "2^30 posting lists or more: beyond the device decoder, load with device < 0"; return SG_E_UNSUPPORTED; }
   DeviceGuard dg;
@@ -412,8 +410,8 @@ int load_decode_device(HostIndex& ix, const RefFiles& f, int device, std::string
   const size_t padded = (f.dl.size() + 64 + 15) & ~(size_t)15;
   uint8_t* d_dl;
   uint32_t* d_chunk; uint64_t* d_dup;
-  if ((rc = mem.alloc(&d_dl, padded)) || (rc = store_stage(mem, st, l_pos, &a.l_pos)) || (rc = store_stage(mem, st, l_size, &a.l_size)) ||
-      (rc = store_stage(mem, st, l_raw, &a.l_raw)) || (rc = store_stage(mem, st, r_list, &a.r_list)) || (rc = store_stage(mem, st, r_cbase, &a.r_cbase)) ||
+  if ((rc = mem.alloc(&d_dl, padded)) || (rc = mem.upload(l_pos, &a.l_pos, st)) || (rc = mem.upload(l_size, &a.l_size, st)) ||
+      (rc = mem.upload(l_raw, &a.l_raw, st)) || (rc = mem.upload(r_list, &a.r_list, st)) || (rc = mem.upload(r_cbase, &a.r_cbase, st)) ||
       (rc = mem.alloc(&a.info, n)) || (rc = mem.alloc(&a.r_status, (size_t)a.n_r)) || (rc = mem.alloc(&d_chunk, n)) || (rc = mem.alloc(&d_dup, n)))
     return rc;
   a.dl = d_dl; a.l_chunk = d_chunk; a.l_dup = d_dup;
@@ -523,7 +521,7 @@ extern "C" {
 int sg_index_load_reference_ex(const char* hd_path, const char* dl_path, const sg_desc* desc, int device, sg_index** out) {
   SG_GUARD_BEGIN
   if (!out || !hd_path || !dl_path) { set_error("null argument"); return SG_E_INVALID; }
-  const auto t0 = std::chrono::steady_clock::now();
+  const auto t0 = clk::now();
   std::unique_ptr<sg_index> ix(new (std::nothrow) sg_index());
   if (!ix) return SG_E_NOMEM;
   std::string err;
@@ -546,7 +544,7 @@ int sg_index_load_reference_ex(const char* hd_path, const char* dl_path, const s
     set_error("wrap strings longer than 8 runes"); return SG_E_UNSUPPORTED;
   }
   for (int i = 0; i < 6; i++) t_load_ms[i] = s[i] * 1e3;
-  t_load_ms[6] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() * 1e3;
+  t_load_ms[6] = since(t0) * 1e3;
   *out = ix.release();
   return SG_OK;
   SG_GUARD_END(SG_RC)

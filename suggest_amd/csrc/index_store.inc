@@ -277,20 +277,9 @@ struct StoreStream {                                      // the call's own stre
   ~StoreStream() { if (s) (void)hipStreamDestroy(s); }
 };
 
-template <class T>
-int store_stage(DeviceBlock& mem, hipStream_t st, const std::vector<T>& src, const T** out) {
-  T* p = nullptr;
-  if (int rc = mem.alloc(&p, src.size())) return rc;
-  if (!src.empty()) HIP_TRY(hipMemcpyAsync(p, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice, st));
-  *out = p;
-  return SG_OK;
-}
-
 // The lists of `h` encoded on `device`: size[] and pos[] per list in header order, the bytes of the .dl in `dl`.
 int store_encode_device(const HostIndex& h, const std::vector<StoreList>& lists, int device, std::vector<uint32_t>& size,
                         std::vector<uint32_t>& pos, uint64_t* total, std::vector<uint8_t>& dl, double seconds[2]) {
-  using clk = std::chrono::steady_clock;
-  auto since = [](clk::time_point t) { return std::chrono::duration<double>(clk::now() - t).count(); };
   const size_t n = lists.size();
   if (n >= (1u << 30)) { set_error("2^30 posting lists or more: beyond the device encoder, store with device < 0"); return SG_E_UNSUPPORTED; }
   DeviceGuard dg;
@@ -327,10 +316,10 @@ int store_encode_device(const HostIndex& h, const std::vector<StoreList>& lists,
   int rc;
   a.n_lists = (uint32_t)n; a.n_items = (uint32_t)items.size(); a.n_r = (uint32_t)r_list.size(); a.n_slots = (uint32_t)n_slots;
   uint32_t* d_pos;
-  if ((rc = store_stage(mem, st, h.postings, &a.post)) || (rc = store_stage(mem, st, l_src, &a.l_src)) || (rc = store_stage(mem, st, l_len, &a.l_len)) ||
-      (rc = store_stage(mem, st, l_raw, &a.l_raw)) || (rc = store_stage(mem, st, l_dbeg, &a.l_dbeg)) || (rc = store_stage(mem, st, l_dn, &a.l_dn)) ||
-      (rc = store_stage(mem, st, d_doc, &a.d_doc)) || (rc = store_stage(mem, st, d_mult, &a.d_mult)) || (rc = store_stage(mem, st, items, &a.items)) ||
-      (rc = store_stage(mem, st, r_list, &a.r_list)) || (rc = store_stage(mem, st, r_cbase, &a.r_cbase)) ||
+  if ((rc = mem.upload(h.postings, &a.post, st)) || (rc = mem.upload(l_src, &a.l_src, st)) || (rc = mem.upload(l_len, &a.l_len, st)) ||
+      (rc = mem.upload(l_raw, &a.l_raw, st)) || (rc = mem.upload(l_dbeg, &a.l_dbeg, st)) || (rc = mem.upload(l_dn, &a.l_dn, st)) ||
+      (rc = mem.upload(d_doc, &a.d_doc, st)) || (rc = mem.upload(d_mult, &a.d_mult, st)) || (rc = mem.upload(items, &a.items, st)) ||
+      (rc = mem.upload(r_list, &a.r_list, st)) || (rc = mem.upload(r_cbase, &a.r_cbase, st)) ||
       (rc = mem.alloc(&a.l_size, n)) || (rc = mem.alloc(&d_pos, n)) || (rc = mem.alloc(&a.r_ncont, (size_t)a.n_r)) || (rc = mem.alloc(&a.r_anyrun, (size_t)a.n_r)))
     return rc;
   a.l_pos = d_pos;
@@ -384,7 +373,7 @@ extern "C" {
 int sg_index_store_reference(sg_index* ix, const char* hd_path, const char* dl_path, int device) {
   SG_GUARD_BEGIN
   if (!ix || !hd_path || !dl_path) { set_error("null argument"); return SG_E_INVALID; }
-  const auto t0 = std::chrono::steady_clock::now();
+  const auto t0 = clk::now();
   const HostIndex& h = ix->host;
   std::string err;
   std::vector<StoreList> lists;
@@ -398,13 +387,13 @@ int sg_index_store_reference(sg_index* ix, const char* hd_path, const char* dl_p
   if (device >= 0 && !lists.empty()) {
     if ((rc = store_encode_device(h, lists, device, size, pos, &total, dl, t))) return rc;
   } else {
-    const auto t_enc = std::chrono::steady_clock::now();   // (behind the list table, like the device path's clock)
+    const auto t_enc = clk::now();                         // (behind the list table, like the device path's clock)
     store_encode_host(h, lists, size, dl);
     if ((rc = store_positions(size, pos, &total, err))) { set_error(err); return rc; }
-    t[0] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_enc).count();
+    t[0] = since(t_enc);
   }
   if ((rc = store_write_files(h, lists, size, pos, dl.data(), total, hd_path, dl_path, &t[2], err))) { set_error(err); return rc; }
-  t[3] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  t[3] = since(t0);
   return SG_OK;
   SG_GUARD_END(SG_RC)
 }

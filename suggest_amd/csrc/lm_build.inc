@@ -1,5 +1,5 @@
-// lm_build.inc — the language model built from a corpus on the device (sg_lm_build_device), included by capi.inc behind
-// index_build.inc (DeviceBlock, hipcub) and the word tokeniser's helpers of engine.hip (d_next_rune, d_lm_lower, d_lm_alpha_has), which it reuses.
+// lm_build.inc — the language model built from a corpus on the device (sg_lm_build_device), included by capi.inc, whose
+// DeviceBlock, device_exclusive_sum and device_total it uses, behind the word tokeniser's helpers of engine.hip (d_next_rune, d_lm_lower, d_lm_alpha_has), which it reuses.
 //
 // What it restates: NGramBuilder.Build over NewSentenceRetriever (pkg/lm/ngram_builder.go:19-64, sentence_retriever.go:54-81),
 // lm.NewTokenizer, buildDictionary's numbering (binary.go:140-198) and the vector builder as lm_load_google restates it — the
@@ -275,23 +275,6 @@ void lm_build_empty(HostLM& h, uint32_t order) {
 #define LMB_GRID(n) dim3((unsigned)(((size_t)(n) + 255) / 256)), dim3(256), 0, 0
 #define LMB_LAUNCHED() HIP_TRY(hipGetLastError())
 
-template <class T> int lmb_scan(DeviceBlock& mem, const T* in, T* out, size_t n) {
-  size_t tb = 0;
-  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, in, out, (int)n));
-  uint8_t* tmp;
-  if (int rc = mem.alloc(&tmp, tb)) return rc;
-  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(tmp, tb, in, out, (int)n));
-  return SG_OK;
-}
-// last exclusive prefix + last value: the sum
-int lmb_total(const uint32_t* val, const uint32_t* pre, size_t n, uint32_t* out) {
-  uint32_t a = 0, b = 0;
-  HIP_TRY(hipMemcpy(&a, val + n - 1, 4, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(&b, pre + n - 1, 4, hipMemcpyDeviceToHost));
-  *out = a + b;
-  return SG_OK;
-}
-
 int lm_build_on_device(const uint8_t* text, uint64_t len, uint32_t order, const std::string& start_symbol, const std::string& end_symbol,
                        const std::vector<std::string>& separators, int id_order, int device, HostLM& h) {
   DeviceGuard dg;
@@ -302,22 +285,16 @@ int lm_build_on_device(const uint8_t* text, uint64_t len, uint32_t order, const 
   // ---- the tables of the walk
   {
     std::vector<uint2> ranges;
-    uint2* d;
     lm_alphabet_tables(h.alphabet, a.alpha.alpha_ascii, ranges);
-    if ((rc = mem.alloc(&d, ranges.size()))) return rc;
-    if (!ranges.empty()) HIP_TRY(hipMemcpy(d, ranges.data(), ranges.size() * 8, hipMemcpyHostToDevice));
-    a.alpha.alpha_ranges = d; a.alpha.n_alpha_ranges = (uint32_t)ranges.size();
+    if ((rc = mem.upload(ranges, &a.alpha.alpha_ranges))) return rc;
+    a.alpha.n_alpha_ranges = (uint32_t)ranges.size();
     lm_alphabet_tables(separators, a.sep.alpha_ascii, ranges);
-    if ((rc = mem.alloc(&d, ranges.size()))) return rc;
-    if (!ranges.empty()) HIP_TRY(hipMemcpy(d, ranges.data(), ranges.size() * 8, hipMemcpyHostToDevice));
-    a.sep.alpha_ranges = d; a.sep.n_alpha_ranges = (uint32_t)ranges.size();
+    if ((rc = mem.upload(ranges, &a.sep.alpha_ranges))) return rc;
+    a.sep.n_alpha_ranges = (uint32_t)ranges.size();
     std::vector<uint32_t> lf, lt;
     for (const auto& pr : kLowerPairs) { lf.push_back(pr.from); lt.push_back(pr.to); }
-    uint32_t *dlf, *dlt;
-    if ((rc = mem.alloc(&dlf, lf.size())) || (rc = mem.alloc(&dlt, lt.size()))) return rc;
-    HIP_TRY(hipMemcpy(dlf, lf.data(), lf.size() * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(dlt, lt.data(), lt.size() * 4, hipMemcpyHostToDevice));
-    a.lower.lower_from = dlf; a.lower.lower_to = dlt; a.lower.n_lower = (uint32_t)lf.size();
+    if ((rc = mem.upload(lf, &a.lower.lower_from)) || (rc = mem.upload(lt, &a.lower.lower_to))) return rc;
+    a.lower.n_lower = (uint32_t)lf.size();
   }
   // ---- the text, with 16 readable bytes before it and the last workgroup's 4 KiB + 16 behind it
   const size_t n_blocks = (size_t)((len + SG_LMB_BLOCK_BYTES - 1) / SG_LMB_BLOCK_BYTES), n_slices = n_blocks * 256;
@@ -335,10 +312,10 @@ int lm_build_on_device(const uint8_t* text, uint64_t len, uint32_t order, const 
   a.o_bytes = c_bytes; a.o_toks = c_toks; a.o_seps = c_seps;
   hipLaunchKernelGGL(lm_build_walk<false>, dim3((unsigned)n_blocks), dim3(256), 0, 0, a);
   LMB_LAUNCHED();
-  if ((rc = lmb_scan(mem, c_bytes, p_bytes, n_slices)) || (rc = lmb_scan(mem, c_toks, p_toks, n_slices)) || (rc = lmb_scan(mem, c_seps, p_seps, n_slices)))
+  if ((rc = device_exclusive_sum(mem, c_bytes, p_bytes, n_slices)) || (rc = device_exclusive_sum(mem, c_toks, p_toks, n_slices)) || (rc = device_exclusive_sum(mem, c_seps, p_seps, n_slices)))
     return rc;
   uint32_t blob_bytes = 0, n_tok = 0;                            // (a GiB of text holds 3 GiB of token bytes at most: invalid bytes
-  if ((rc = lmb_total(c_bytes, p_bytes, n_slices, &blob_bytes)) || (rc = lmb_total(c_toks, p_toks, n_slices, &n_tok))) return rc;   //  as U+FFFD)
+  if ((rc = device_total(c_bytes, p_bytes, n_slices, &blob_bytes)) || (rc = device_total(c_toks, p_toks, n_slices, &n_tok))) return rc;   //  as U+FFFD)
   if (n_tok == 0) { lm_build_empty(h, order); return SG_OK; }
   if ((uint64_t)blob_bytes + start_symbol.size() + end_symbol.size() >= 0xFFFFFFF0ull) { set_error("corpus too large for the device builder: its tokens pass 4 GiB"); return SG_E_UNSUPPORTED; }
 
@@ -373,9 +350,9 @@ int lm_build_on_device(const uint8_t* text, uint64_t len, uint32_t order, const 
   hipLaunchKernelGGL(lm_build_intern, LMB_GRID(n_all), d_blob, tok_end, tok_sent, n_tok, table, (uint32_t)(n_slots - 1),
                      g_lm_build_hash_bits.load(std::memory_order_relaxed), tok_slot, first_flag, d_counters);
   LMB_LAUNCHED();
-  if ((rc = lmb_scan(mem, first_flag, first_pre, n_tok))) return rc;
+  if ((rc = device_exclusive_sum(mem, first_flag, first_pre, n_tok))) return rc;
   uint32_t n_sent = 0, n_words = 0;
-  if ((rc = lmb_total(first_flag, first_pre, n_tok, &n_sent))) return rc;
+  if ((rc = device_total(first_flag, first_pre, n_tok, &n_sent))) return rc;
   HIP_TRY(hipMemcpy(&n_words, d_counters, 4, hipMemcpyDeviceToHost));
   const uint64_t n_seq64 = (uint64_t)n_tok + 2ull * n_sent;
   if (n_seq64 >= 0x7FFFFFF0ull) { set_error("corpus too large for the device builder: tokens and markers pass 2^31"); return SG_E_UNSUPPORTED; }
@@ -472,7 +449,7 @@ int lm_build_on_device(const uint8_t* text, uint64_t len, uint32_t order, const 
         hipLaunchKernelGGL(lm_build_heads, LMB_GRID(n_seq), key_b, n_seq, n_valid, head);
         LMB_LAUNCHED();
         HIP_TRY(hipcub::DeviceScan::ExclusiveSum(sort_tmp, scan_bytes, head, head_pre, (int)n_seq));
-        if ((rc = lmb_total(head, head_pre, n_seq, &n_entries))) return rc;
+        if ((rc = device_total(head, head_pre, n_seq, &n_entries))) return rc;
         hipLaunchKernelGGL(lm_build_entries, LMB_GRID(n_seq), key_b, pos_b, head, head_pre, n_seq, n_valid, ctx_cur, e_start, e_key);
         LMB_LAUNCHED();
         if (n_entries) {

@@ -1,5 +1,5 @@
 // lm_store.inc — the device writer behind sg_lm_store_google, included by engine.hip after index_store.inc (it uses HIP_TRY,
-// DeviceGuard, DeviceBlock, StoreStream and store_stage).  Replaces the walk of googleNGramFormatWriter.Write
+// DeviceGuard, DeviceBlock and StoreStream).  Replaces the walk of googleNGramFormatWriter.Write
 // (pkg/lm/ngram_writer.go:32-76) over a trie of Go maps with the finished levels of a model spelled as lines
 // "w1 .. wk\tcount\n"; the host writer the kernels are read against is lm_store_google_host (lm_store.cpp), and both write
 // identical files.
@@ -105,8 +105,6 @@ namespace {
 thread_local double t_lm_store_seconds[4];                // the calling thread's last sg_lm_store_google: staging, kernels, copy-back, file writes
 
 int lm_store_google_device(const HostLM& lm, const char* out_dir, int device, double seconds[4]) {
-  using clk = std::chrono::steady_clock;
-  auto since = [](clk::time_point t) { return std::chrono::duration<double>(clk::now() - t).count(); };
   std::string err;
   int rc;
   if ((rc = lm_gm_check(lm, err))) { set_error(err); return rc; }
@@ -126,14 +124,14 @@ int lm_store_google_device(const HostLM& lm, const char* out_dir, int device, do
   wbytes.reserve(woff.back());
   for (const auto& w : lm.words) wbytes.insert(wbytes.end(), w.begin(), w.end());
   a.n_words = (uint32_t)lm.words.size();
-  if ((rc = store_stage(mem, st, wbytes, &a.wbytes)) || (rc = store_stage(mem, st, woff, &a.woff))) return rc;
+  if ((rc = mem.upload(wbytes, &a.wbytes, st)) || (rc = mem.upload(woff, &a.woff, st))) return rc;
   size_t n_max = 0;
   for (size_t k = 0; k < order; k++) {
     const LmLevel& lv = lm.level[k];
     a.n[k] = (uint32_t)lv.word.size();
     n_max = std::max(n_max, lv.word.size());
-    if ((rc = store_stage(mem, st, lv.word, &a.word[k])) || (rc = store_stage(mem, st, lv.count, &a.count[k])) ||
-        (rc = store_stage(mem, st, lv.child_begin, &a.cbeg[k])) || (rc = mem.alloc(&a.parent[k], lv.word.size())))
+    if ((rc = mem.upload(lv.word, &a.word[k], st)) || (rc = mem.upload(lv.count, &a.count[k], st)) ||
+        (rc = mem.upload(lv.child_begin, &a.cbeg[k], st)) || (rc = mem.alloc(&a.parent[k], lv.word.size())))
       return rc;
   }
   if ((rc = mem.alloc(&a.len, n_max + 1)) || (rc = mem.alloc(&a.off, n_max + 1))) return rc;

@@ -192,19 +192,6 @@ __global__ void pk_flag_rows(uint32_t* new_off, uint32_t n_terms, uint32_t S, co
 
 namespace {
 
-// releases one device allocation of the replica (dev_alloc's counterpart)
-void dev_release(Replica* r, const void* p) {
-  if (!p) return;
-  for (size_t i = 0; i < r->allocs.size(); i++)
-    if (r->allocs[i] == p) {
-      (void)hipFree(r->allocs[i]);
-      r->device_bytes -= r->alloc_bytes[i];
-      r->allocs.erase(r->allocs.begin() + (long)i);
-      r->alloc_bytes.erase(r->alloc_bytes.begin() + (long)i);
-      return;
-    }
-}
-
 // u32 CSR + forward index (both already on the device, in r->dix) -> the packed store.  On success r->dix.postings /
 // seg_off / fwd_rec / cut_sample are the packed store's, orig_of / seg_base are set and the u32 arrays are freed.
 // g8_mode (knob SG_G8): 0 16-bit gaps only, 1 8-bit gaps for the terms they save chunks on, 2 for every term (tests)
@@ -213,34 +200,27 @@ int pack_store(const HostIndex& h, Replica* r, int g8_mode) {
   const uint32_t n_docs = (uint32_t)h.n_docs, S = h.n_segments, nT = (uint32_t)h.term_key.size();
   int rc;
   if ((uint64_t)h.n_docs + SG_PPC * SG_PAD_GAP > (uint64_t)SG_X_MASK) { set_error("the packed posting store numbers documents below 2^29"); return SG_E_UNSUPPORTED; }
-  struct Free { std::vector<void*> p; ~Free() { for (void* x : p) (void)hipFree(x); } } scratch;
-  auto salloc = [&](void** p, size_t bytes) { hipError_t e = hipMalloc(p, std::max<size_t>(bytes, 16)); if (e == hipSuccess) scratch.p.push_back(*p); return e; };
+  DeviceBlock& mem = r->mem;
+  DeviceBlock scratch;                                          // freed on return: not part of the replica
   uint32_t *orig_of = nullptr, *x_of = nullptr, *seg_base = nullptr;
-  if ((rc = dev_alloc(r, (size_t)n_docs, &orig_of))) return rc;
-  if ((rc = dev_alloc(r, (size_t)n_docs, &x_of))) return rc;
-  if ((rc = dev_alloc(r, (size_t)S + 2, &seg_base))) return rc;
+  if ((rc = mem.alloc(&orig_of, (size_t)n_docs)) || (rc = mem.alloc(&x_of, (size_t)n_docs)) || (rc = mem.alloc(&seg_base, (size_t)S + 2))) return rc;
   const unsigned gd = (n_docs + 255u) / 256u;
   if (n_docs) {
     uint32_t *key_in = nullptr, *key_out = nullptr, *val_in = nullptr;
-    HIP_TRY(salloc((void**)&key_in, (size_t)n_docs * 4)); HIP_TRY(salloc((void**)&key_out, (size_t)n_docs * 4));
-    HIP_TRY(salloc((void**)&val_in, (size_t)n_docs * 4));
+    if ((rc = scratch.alloc(&key_in, (size_t)n_docs)) || (rc = scratch.alloc(&key_out, (size_t)n_docs)) || (rc = scratch.alloc(&val_in, (size_t)n_docs))) return rc;
     hipLaunchKernelGGL(pk_keys, dim3(gd), dim3(256), 0, 0, d.fwd_rec, n_docs, key_in, val_in);
     HIP_TRY(hipGetLastError());
-    size_t tb = 0;
-    void* tmp = nullptr;
-    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, key_in, key_out, val_in, orig_of, (int)n_docs, 0, 16));   // stable
-    HIP_TRY(salloc(&tmp, tb));
-    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, tb, key_in, key_out, val_in, orig_of, (int)n_docs, 0, 16));
+    if ((rc = device_sort_pairs(scratch, key_in, key_out, val_in, orig_of, n_docs, 0, 16))) return rc;   // stable
     hipLaunchKernelGGL(pk_inverse, dim3(gd), dim3(256), 0, 0, orig_of, n_docs, x_of);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(pk_seg_base, dim3((S + 1 + 255) / 256), dim3(256), 0, 0, key_out, n_docs, S, seg_base);
     HIP_TRY(hipGetLastError());
     uint2* rec_x = nullptr;
-    if ((rc = dev_alloc(r, (size_t)n_docs, &rec_x))) return rc;
+    if ((rc = mem.alloc(&rec_x, (size_t)n_docs))) return rc;
     hipLaunchKernelGGL(pk_permute_rec, dim3(gd), dim3(256), 0, 0, d.fwd_rec, orig_of, n_docs, rec_x);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
-    dev_release(r, d.fwd_rec);
+    mem.release(d.fwd_rec);
     d.fwd_rec = rec_x;
     // [r6] the term lists themselves in x order, a segment's documents a fixed stride apart (pk_fwd_strided): where the dictionary
     // has at most 63 segments a verifier's lanes find a document's segment in a table they hold, and its term list with it
@@ -255,14 +235,13 @@ int pack_store(const HostIndex& h, Replica* r, int g8_mode) {
       fb[S] = (uint32_t)tot;
       if (ok) {
         uint32_t *fx_base = nullptr, *terms_x = nullptr;
-        if ((rc = dev_alloc(r, (size_t)S + 2, &fx_base))) return rc;
-        if ((rc = dev_alloc(r, (size_t)std::max<uint64_t>(tot, 1) * 4, &terms_x))) return rc;
+        if ((rc = mem.alloc(&fx_base, (size_t)S + 2)) || (rc = mem.alloc(&terms_x, (size_t)std::max<uint64_t>(tot, 1) * 4))) return rc;
         HIP_TRY(hipMemcpy(fx_base, fb.data(), ((size_t)S + 1) * 4, hipMemcpyHostToDevice));
         HIP_TRY(hipMemset(terms_x, 0xFF, (size_t)std::max<uint64_t>(tot, 1) * 16));
         hipLaunchKernelGGL(pk_fwd_strided, dim3(gd), dim3(256), 0, 0, rec_x, d.fwd_terms, (const uint32_t*)seg_base, (const uint32_t*)fx_base, n_docs, terms_x);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipDeviceSynchronize());
-        dev_release(r, d.fwd_terms);
+        mem.release(d.fwd_terms);
         d.fwd_terms = terms_x;
         d.fx_base = fx_base;
       }
@@ -274,7 +253,7 @@ int pack_store(const HostIndex& h, Replica* r, int g8_mode) {
 
   const uint64_t n_lists = (uint64_t)nT * S, n_rows = (uint64_t)nT * (S + 1);
   uint32_t* new_off = nullptr;
-  if ((rc = dev_alloc(r, (size_t)std::max<uint64_t>(n_rows, 1), &new_off))) return rc;
+  if ((rc = mem.alloc(&new_off, (size_t)std::max<uint64_t>(n_rows, 1)))) return rc;
   uint64_t total_chunks = 0;
   uint8_t* term_fmt = nullptr;                                  // [nT] 1: the term's lists have 8-bit gaps (null: none has)
   const unsigned pk_grid = (unsigned)std::min<uint64_t>(std::max<uint64_t>(n_lists, 1), 1u << 22);
@@ -283,7 +262,7 @@ int pack_store(const HostIndex& h, Replica* r, int g8_mode) {
   if (n_lists) {
     if (n_rows >= 0x7FFFFFFFull) { set_error("terms x segments exceeds a launch grid"); return SG_E_UNSUPPORTED; }
     uint32_t *counts = nullptr, *c8 = nullptr;
-    HIP_TRY(salloc((void**)&counts, (size_t)n_rows * 4));
+    if ((rc = scratch.alloc(&counts, (size_t)n_rows))) return rc;
     HIP_TRY(hipMemset(counts, 0, (size_t)n_rows * 4));
     hipLaunchKernelGGL(pk_pack<false>, dim3(pk_grid), dim3(64), 0, 0, d.postings, d.seg_off, S, n_lists, (const uint32_t*)x_of, counts,
                        (const uint32_t*)nullptr, (uint32_t*)nullptr, false, (const uint8_t*)nullptr);
@@ -291,12 +270,11 @@ int pack_store(const HostIndex& h, Replica* r, int g8_mode) {
     if (g8_possible) {
       uint32_t* c16 = counts;
       unsigned long long* totals = nullptr;
-      HIP_TRY(salloc((void**)&c8, (size_t)n_rows * 4));
+      if ((rc = scratch.alloc(&c8, (size_t)n_rows))) return rc;
       HIP_TRY(hipMemset(c8, 0, (size_t)n_rows * 4));
-      HIP_TRY(salloc((void**)&counts, (size_t)n_rows * 4));
-      HIP_TRY(salloc((void**)&totals, 16));
+      if ((rc = scratch.alloc(&counts, (size_t)n_rows)) || (rc = scratch.alloc(&totals, 2))) return rc;
       HIP_TRY(hipMemset(totals, 0, 16));
-      HIP_TRY(salloc((void**)&term_fmt, (size_t)nT));
+      if ((rc = scratch.alloc(&term_fmt, (size_t)nT))) return rc;
       hipLaunchKernelGGL(pk_pack<false>, dim3(pk_grid), dim3(64), 0, 0, d.postings, d.seg_off, S, n_lists, (const uint32_t*)x_of, c8,
                          (const uint32_t*)nullptr, (uint32_t*)nullptr, true, (const uint8_t*)nullptr);
       hipLaunchKernelGGL(pk_choose, dim3((nT + 255) / 256), dim3(256), 0, 0, (const uint32_t*)c16, (const uint32_t*)c8, nT, S, g8_mode, term_fmt, counts, totals);
@@ -309,11 +287,7 @@ int pack_store(const HostIndex& h, Replica* r, int g8_mode) {
       if (env_int("SG_VERBOSE", 0, 1, 0)) fprintf(stderr, "[suggest_hip] packed store: %llu chunks with 16-bit gaps, %llu with 8-bit gaps for the dense terms%s\n", tot[0], tot[1],
                                         term_fmt ? "" : " (not taken)");
     }
-    size_t tb = 0;
-    void* tmp = nullptr;
-    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, counts, new_off, (int)n_rows));
-    HIP_TRY(salloc(&tmp, tb));
-    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(tmp, tb, counts, new_off, (int)n_rows));
+    if ((rc = device_exclusive_sum(scratch, counts, new_off, (size_t)n_rows))) return rc;
     uint32_t last = 0;                                          // (the last row of a term counts 0: its offset is the total)
     HIP_TRY(hipMemcpy(&last, new_off + (n_rows - 1), 4, hipMemcpyDeviceToHost));
     total_chunks = last;
@@ -321,12 +295,12 @@ int pack_store(const HostIndex& h, Replica* r, int g8_mode) {
     HIP_TRY(hipMemset(new_off, 0, 4));
   }
   uint32_t* packed = nullptr;
-  if ((rc = dev_alloc(r, (size_t)total_chunks * 4 + 64 * 4, &packed))) return rc;      // (+ a row of slack behind the last chunk)
+  if ((rc = mem.alloc(&packed, (size_t)total_chunks * 4 + 64 * 4))) return rc;      // (+ a row of slack behind the last chunk)
   HIP_TRY(hipMemset(packed, 0, ((size_t)total_chunks * 4 + 64 * 4) * 4));
   // one sample per 16 chunks of the store: lets a docID-range pass cut its lists without probing them (written by pk_finish)
   const uint64_t n_cs = total_chunks / 16 + 2;
   uint32_t* cs = nullptr;
-  if ((rc = dev_alloc(r, (size_t)n_cs, &cs))) return rc;
+  if ((rc = mem.alloc(&cs, (size_t)n_cs))) return rc;
   HIP_TRY(hipMemset(cs, 0xFF, std::max<size_t>((size_t)n_cs * 4, 16)));      // (all of the allocation: sg_debug_index_array reads it back whole)
   if (n_lists) {
     hipLaunchKernelGGL(pk_pack<true>, dim3(pk_grid), dim3(64), 0, 0, d.postings, d.seg_off, S, n_lists, (const uint32_t*)x_of, (uint32_t*)nullptr,
@@ -343,8 +317,8 @@ int pack_store(const HostIndex& h, Replica* r, int g8_mode) {
   }
   HIP_TRY(hipDeviceSynchronize());
   r->packed_chunks = total_chunks;
-  dev_release(r, d.postings);
-  dev_release(r, d.seg_off);
+  mem.release(d.postings);
+  mem.release(d.seg_off);
   d.postings = packed;
   d.seg_off = new_off;
   d.cut_sample = cs;

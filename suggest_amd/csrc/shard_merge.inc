@@ -544,11 +544,10 @@ int sg_debug_shard_merge(int device, const uint32_t* ids, const double* scores, 
   const size_t o_ids = sc ? (size_t)n_q * k * 8 : 0, o_cnt = o_ids + (size_t)n_q * k * 4, o_bytes = o_cnt + (size_t)n_q * 4;
   DeviceGuard dg;
   HIP_TRY(dg.set(device));
-  GrowBlock in, out;
-  struct Free { GrowBlock &a, &b; ~Free() { a.release(); b.release(); } } free_{in, out};
-  if (int rc = in.grow(B.bytes)) return rc;
-  if (int rc = out.grow(o_bytes)) return rc;
-  char *di = (char*)in.p, *d_o = (char*)out.p;
+  DeviceBlock mem;
+  char *di = nullptr, *d_o = nullptr;
+  int rc;
+  if ((rc = mem.alloc(&di, block_capacity(B.bytes))) || (rc = mem.alloc(&d_o, block_capacity(o_bytes)))) return rc;   // (a search's GrowBlock sizes)
   if (sc) HIP_TRY(hipMemcpy(di, scores, B.ids, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(di + B.ids, ids, B.cnt - B.ids, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(di + B.cnt, counts, B.bytes - B.cnt, hipMemcpyHostToDevice));
