@@ -215,6 +215,30 @@ struct BatchArgs {
 __device__ __forceinline__ uint64_t ballot(bool p) { return __builtin_amdgcn_ballot_w64(p); }
 __device__ __forceinline__ uint32_t popc64(uint64_t m) { return (uint32_t)__builtin_popcountll(m); }
 __device__ __forceinline__ uint32_t readlane(uint32_t v, int l) { return (uint32_t)__builtin_amdgcn_readlane((int)v, l); }
+// a lane's rank among the lanes of a ballot: the set bits below its own (v_mbcnt_lo / _hi: no shift by the lane number)
+__device__ __forceinline__ uint32_t lane_rank(uint64_t m) { return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u)); }
+// maximum / sum over the wave, in every lane (butterfly)
+__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, off, 64));
+  return v;
+}
+__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) v += (uint32_t)__shfl_xor((int)v, off, 64);
+  return v;
+}
+// minimum over the wave (DPP network, as wave_scan_incl)
+__device__ __forceinline__ int wave_min_i32(int v) {
+  const int I = 0x7FFFFFFF;
+  v = min(v, __builtin_amdgcn_update_dpp(I, v, 0x111, 0xf, 0xf, false));   // row_shr:1 (lanes without a source keep I)
+  v = min(v, __builtin_amdgcn_update_dpp(I, v, 0x112, 0xf, 0xf, false));
+  v = min(v, __builtin_amdgcn_update_dpp(I, v, 0x114, 0xf, 0xf, false));
+  v = min(v, __builtin_amdgcn_update_dpp(I, v, 0x118, 0xf, 0xf, false));
+  v = min(v, __builtin_amdgcn_update_dpp(I, v, 0x142, 0xa, 0xf, false));   // row_bcast:15 -> rows 1, 3
+  v = min(v, __builtin_amdgcn_update_dpp(I, v, 0x143, 0xc, 0xf, false));   // row_bcast:31 -> rows 2, 3
+  return (int)readlane((uint32_t)v, 63);
+}
 
 // pkg/metric — IEEE binary64, Go's evaluation order; built with -ffp-contract=off
 __device__ double d_floor_div_clamp(double x, double hi) { double f = floor(x); return f > hi ? hi : f; }
@@ -262,6 +286,9 @@ __device__ __forceinline__ double d_score(int m, int inter, int a, int b, const 
   }
   return 1 - dist;
 }
+// A segment B is searched with threshold T unless T == 0, T > B or T > |A| (suggester.go:76); the callers add the searcher's own
+// test where they count the present terms: fewer than T of the query's terms with a posting list there (searcher.go:32)
+__device__ __forceinline__ bool segment_admissible(int T, int B, int A) { return !(T == 0 || T > B || T > A); }
 // order-preserving map double -> u64 (bigger = better score)
 __device__ __forceinline__ uint64_t score_bits(double x);
 // Threshold tightening (suggester.go:67-68,101-103, restated exactly): once the top-k is full, a document of segment b can
@@ -291,16 +318,24 @@ __device__ __forceinline__ bool better(uint64_t s1, uint32_t i1, uint64_t s2, ui
   return s1 > s2 || (s1 == s2 && i1 < i2);  // Candidate.Less inverted, collector.go:20-26
 }
 
-__device__ uint32_t d_lower(const DeviceIndex& ix, uint32_t r) {
-  if (r < 0x80) return (r - 'A' < 26u) ? r + 32 : r;
-  uint32_t lo = 0, hi = ix.n_lower;
-  while (lo < hi) {
-    uint32_t mid = (lo + hi) >> 1;
-    if (ix.lower_from[mid] < r) lo = mid + 1; else hi = mid;
-  }
-  return (lo < ix.n_lower && ix.lower_from[lo] == r) ? ix.lower_to[lo] : r;
+// simple lower case of a rune by binary search in the pair table (P: DeviceIndex, SpellArgs, lm_build.inc's LmLowerTable: lower_from / lower_to / n_lower)
+template <class P> __device__ __forceinline__ uint32_t d_lower_pairs(const P& p, uint32_t r) {
+  if (r < 0x80u) return (r - 'A' < 26u) ? r + 32u : r;
+  uint32_t lo = 0, hi = p.n_lower;
+  while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (p.lower_from[mid] < r) lo = mid + 1; else hi = mid; }
+  return (lo < p.n_lower && p.lower_from[lo] == r) ? p.lower_to[lo] : r;
 }
+__device__ uint32_t d_lower(const DeviceIndex& ix, uint32_t r) { return d_lower_pairs(ix, r); }   // (the index's table; inlining left to the compiler)
 __device__ __forceinline__ uint32_t d_width(uint32_t r) { return r < 0x80 ? 1 : r < 0x800 ? 2 : r < 0x10000 ? 3 : 4; }
+// UTF-8 encoding of a rune into out[0 .. width); returns the width
+__device__ __forceinline__ uint32_t d_put_rune(uint8_t* out, uint32_t r) {
+  const uint32_t w = d_width(r);
+  if (w == 1u) out[0] = (uint8_t)r;
+  else if (w == 2u) { out[0] = (uint8_t)(0xC0u | (r >> 6)); out[1] = (uint8_t)(0x80u | (r & 0x3Fu)); }
+  else if (w == 3u) { out[0] = (uint8_t)(0xE0u | (r >> 12)); out[1] = (uint8_t)(0x80u | ((r >> 6) & 0x3Fu)); out[2] = (uint8_t)(0x80u | (r & 0x3Fu)); }
+  else { out[0] = (uint8_t)(0xF0u | (r >> 18)); out[1] = (uint8_t)(0x80u | ((r >> 12) & 0x3Fu)); out[2] = (uint8_t)(0x80u | ((r >> 6) & 0x3Fu)); out[3] = (uint8_t)(0x80u | (r & 0x3Fu)); }
+  return w;
+}
 
 // Go `range` decoding of one rune (invalid byte -> U+FFFD, width 1)
 __device__ uint32_t d_next_rune(const uint8_t* s, uint32_t n, uint32_t* adv) {
@@ -327,6 +362,14 @@ __device__ uint32_t d_next_rune(const uint8_t* s, uint32_t n, uint32_t* adv) {
   return ((c0 & 0x07) << 18) | ((s[1] & 0x3F) << 12) | ((s[2] & 0x3F) << 6) | (s[3] & 0x3F);
 }
 
+// is r a rune of the language model's alphabet (P: SpellArgs, or the builder's own small tables of lm_build.inc — any struct with
+// alpha_ascii / alpha_ranges / n_alpha_ranges)
+template <class P> __device__ __forceinline__ bool d_lm_alpha_has(const P& p, uint32_t r) {
+  if (r < 128u) return (p.alpha_ascii[r >> 6] >> (r & 63u)) & 1ull;
+  uint32_t lo = 0, hi = p.n_alpha_ranges;
+  while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (p.alpha_ranges[mid].y < r) lo = mid + 1; else hi = mid; }
+  return lo < p.n_alpha_ranges && p.alpha_ranges[lo].x <= r;
+}
 // normalizeFilter (normalizer.go:21-37) fused with key packing; n <= 8 runes
 __device__ uint64_t d_pack_key(const DeviceIndex& ix, const uint32_t* runes, uint32_t n) {
   uint64_t k = 0;
@@ -393,7 +436,9 @@ __device__ uint64_t d_mix64(uint64_t k) {
   k ^= k >> 31;
   return k;
 }
-template <uint32_t kQH> __device__ __forceinline__ uint32_t d_qhash(uint32_t term) { return (((term * 0x9E3779B1u) >> 24) * kQH) >> 8; }   // 8 hash bits onto kQH slots
+// The query's terms as an LDS hash of kQH slots (Lds::qh / SG_PIPE_QH), what a candidate's own term list (forward index) is matched
+// against: linear probing from 8 hash bits spread over the slots; an occurrence = an entry, so a repeated term sits in consecutive slots.
+template <uint32_t kQH> __device__ __forceinline__ uint32_t d_qhash(uint32_t term) { return (((term * 0x9E3779B1u) >> 24) * kQH) >> 8; }
 template <uint32_t kQH> __device__ __forceinline__ uint32_t d_qnext(uint32_t h) { return h + 1u == kQH ? 0u : h + 1u; }
 __device__ uint32_t d_term_lookup(const DeviceIndex& ix, uint64_t key) {
   uint32_t h = (uint32_t)d_mix64(key) & ix.slot_mask;
@@ -718,6 +763,11 @@ struct TopK {  // wave-uniform state; arrays live in LDS (k <= SG_K_LDS) or in t
   uint64_t worst_s;
   uint32_t worst_id, worst_pos;
 };
+// an empty queue of k rows over the caller's arrays (LDS, or the query's working rows in HBM)
+__device__ __forceinline__ void topk_begin(TopK& tk, uint64_t* s, uint32_t* id, uint32_t k) {
+  tk.s = s; tk.id = id;
+  tk.n = 0; tk.k = k; tk.worst_s = 0; tk.worst_id = 0; tk.worst_pos = 0;
+}
 
 __device__ __forceinline__ void topk_recompute_worst(TopK& tk, int lane) {
   uint64_t ws = ~0ull; uint32_t wi = 0, wp = 0xFFFFFFFFu;
@@ -769,13 +819,26 @@ __device__ const uint8_t kBucketsPer16Postings[8][33] = {
 // the critical path of every group's setup (group sizes, list skipping, counter geometry: two dependent lookups per group)
 // and a load from the table in memory is a VMEM round trip under a saturated memory system: ~1 us each, a fifth of a
 // headline query's time.  Uniform T: v_readlane; T per lane: ds_bpermute.
+__device__ __forceinline__ uint32_t m16_by_lane(int T, uint32_t m16_lane) {                             // (every lane takes part in the permute)
+  return (uint32_t)__builtin_amdgcn_ds_bpermute((T < 0 ? 0 : (T > 32 ? 32 : T)) << 2, (int)m16_lane);
+}
 __device__ __forceinline__ uint32_t buckets_needed(uint32_t postings, int T, uint32_t m16_lane) {       // T uniform
   const uint32_t m16 = readlane(m16_lane, T < 0 ? 0 : (T > 32 ? 32 : T));
   return (postings * m16) >> 4;
 }
-__device__ __forceinline__ uint32_t buckets_needed_lane(uint32_t postings, int T, uint32_t m16_lane) {  // T differs by lane
-  const uint32_t m16 = (uint32_t)__builtin_amdgcn_ds_bpermute((T < 0 ? 0 : (T > 32 ? 32 : T)) << 2, (int)m16_lane);
-  return (postings * m16) >> 4;
+__device__ __forceinline__ uint32_t buckets_needed_lane(uint32_t postings, int T, uint32_t m16_lane) { return (postings * m16_by_lane(T, m16_lane)) >> 4; }   // T differs by lane
+// Buckets a segment (lane) of `tot` chunks and threshold T would need on its own in the plan launches, 0 for one that is not searched:
+// the equal-length estimate of what list skipping leaves — ks of the A lists unread, T lower by as many.  Every lane calls it (m16_by_lane).
+__device__ __forceinline__ uint32_t segment_need(bool valid, int T, uint32_t tot, int A, int t_floor, uint32_t m16_lane) {
+  uint32_t need_p = 0;
+  int need_T = 0;
+  if (valid) {
+    const int ks = T > t_floor ? min(T - t_floor, A - 1) : 0;
+    const uint32_t rem = tot - (uint32_t)((float)tot * (float)ks * (1.0f / (float)A));
+    need_T = T - ks; need_p = min(rem, 1u << 21) * SG_PPC;     // (capped: 2^21 chunks are far beyond any counter array, and postings x a table entry stay below 2^32)
+  }
+  const uint32_t bn = __umul24(need_p, m16_by_lane(need_T, m16_lane)) >> 4;   // (need_p < 2^24)
+  return valid ? max(1u, bn) : 0u;
 }
 
 typedef uint32_t u32x16 __attribute__((ext_vector_type(16)));
@@ -924,18 +987,6 @@ __device__ __forceinline__ uint64_t count_row8(const uint4& v, uint32_t live, ui
 #define PH_FLUSH
 #endif
 
-// minimum over the wave (DPP network, as wave_scan_incl)
-__device__ __forceinline__ int wave_min_i32(int v) {
-  const int I = 0x7FFFFFFF;
-  v = min(v, __builtin_amdgcn_update_dpp(I, v, 0x111, 0xf, 0xf, false));   // row_shr:1 (lanes without a source keep I)
-  v = min(v, __builtin_amdgcn_update_dpp(I, v, 0x112, 0xf, 0xf, false));
-  v = min(v, __builtin_amdgcn_update_dpp(I, v, 0x114, 0xf, 0xf, false));
-  v = min(v, __builtin_amdgcn_update_dpp(I, v, 0x118, 0xf, 0xf, false));
-  v = min(v, __builtin_amdgcn_update_dpp(I, v, 0x142, 0xa, 0xf, false));   // row_bcast:15 -> rows 1, 3
-  v = min(v, __builtin_amdgcn_update_dpp(I, v, 0x143, 0xc, 0xf, false));   // row_bcast:31 -> rows 2, 3
-  return (int)readlane((uint32_t)v, 63);
-}
-
 // ------------------------------------------------------------------------------------------
 // The fused search kernel.  grid = n_q workgroups of one wavefront; dynamic LDS per wave:
 //   cnt[1<<log2_cnt] u32 (tokeniser scratch aliases it) | term | rows | cand, candw | topk
@@ -984,9 +1035,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kG8 ? 2 : 3,
   uint8_t* rowlist = (uint8_t*)(rowtab + 2 * (L::rowtab_cap + 2 * SG_UNROLL));   // ... and the list (query position) of each row
   uint32_t* dummy_w = rowtab + 2 * (L::rowtab_cap + 2 * SG_UNROLL) + (L::rowtab_cap + 2 * SG_UNROLL + 7) / 8 * 2;   // then one
   const uint32_t dummy_lane = (uint32_t)(uintptr_t)(lds_u32*)(dummy_w + lane);   // private dummy counter word per lane
-  // the query's terms as an LDS hash (linear probing; an occurrence = an entry, so a repeated term sits in consecutive
-  // probe slots): what a candidate's own term list (forward index) is matched against
-  uint32_t* qh_key = dummy_w + 64;
+  uint32_t* qh_key = dummy_w + 64;                  // the query-term hash (d_qhash)
   uint8_t* qh_pos = (uint8_t*)(qh_key + L::qh);     // query position of the entry
   // the repeated-term path (documents that repeat a term: rare) borrows row table + dummies + hash — all idle while
   // candidates are emitted — and rebuilds the hash afterwards
@@ -1201,7 +1250,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kG8 ? 2 : 3,
       if (a.autocomplete == 1) { seg_T = A; seg_valid = true; }
       else {
         seg_T = d_threshold(a.metric, a.alpha, A, B, a.mt);
-        seg_valid = !(seg_T == 0 || seg_T > B || seg_T > A);       // suggester.go:76
+        seg_valid = segment_admissible(seg_T, B, A);
         if (kTight && seg_valid && tk.n == k) {                      // the top-k is full (the docID-ordered modes never get here: seg_T is set above / the host takes the plain instantiation)
           // (a query that repeats a term counts it per occurrence: overlaps reach A even where B is smaller)
           seg_T = d_tighten(a.metric, seg_T, A, A, B, tk.worst_s, a.mt);
@@ -1380,9 +1429,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kG8 ? 2 : 3,
       uint2 rec = make_uint2(0u, 0u);
       uint32_t my_orig = 0u;                                    // (one load per candidate, side by side: the serial emit loop has it at hand)
       if ((uint32_t)lane < n) { rec = ix.fwd_rec[my_doc]; my_orig = ix.orig_of[my_doc]; }
-      uint32_t nd_max = rec.y >> 16;
-#pragma unroll
-      for (int off = 32; off >= 1; off >>= 1) nd_max = max(nd_max, (uint32_t)__shfl_xor((int)nd_max, off, 64));
+      const uint32_t nd_max = wave_max_u32(rec.y >> 16);
       const int gsz = nd_max <= 8u ? 8 : nd_max <= 16u ? 16 : nd_max <= 32u ? 32 : 64, ngrp = 64 / gsz;
       const int gi = lane / gsz, ti = lane - gi * gsz;
       const uint64_t gmask = gsz == 64 ? ~0ull : ((1ull << gsz) - 1ull) << (gi * gsz);
@@ -2280,24 +2327,21 @@ __device__ void long_query(const BatchArgs& a, uint32_t qi, uint8_t* slot, int l
   }
   b_min = max(b_min, 0);
   TopK tk;
-  tk.s = k <= SG_K_LDS ? (uint64_t*)(slot + LongSlot::o_tks) : a.scratch_s + (uint64_t)qi * k;
-  tk.id = k <= SG_K_LDS ? (uint32_t*)(slot + LongSlot::o_tkid) : a.scratch_id + (uint64_t)qi * k;
-  tk.n = 0; tk.k = k; tk.worst_s = 0; tk.worst_id = 0; tk.worst_pos = 0;
+  topk_begin(tk, k <= SG_K_LDS ? (uint64_t*)(slot + LongSlot::o_tks) : a.scratch_s + (uint64_t)qi * k,
+             k <= SG_K_LDS ? (uint32_t*)(slot + LongSlot::o_tkid) : a.scratch_id + (uint64_t)qi * k, k);
   const uint32_t lm_from = a.lm_values ? a.lm_from[qi] : 0u, lm_to = a.lm_values ? a.lm_to[qi] : 0u;
   const uint32_t S1 = (uint32_t)S + 1u;
   for (int B = b_min; B <= b_max; B++) {
     int T = (int)A;
     if (a.autocomplete != 1) {
       T = d_threshold(a.metric, a.alpha, (int)A, B, a.mt);
-      if (T == 0 || T > B || T > (int)A) continue;               // suggester.go:76
+      if (!segment_admissible(T, B, (int)A)) continue;
     }
     const uint32_t x0 = ix.seg_base[B], n_seg = ix.seg_base[B + 1] - x0;
     if (n_seg == 0u || n_seg > a.long_max_seg) continue;
-    uint32_t ne = 0;                                            // searcher.go:32: fewer present terms than T
+    uint32_t ne = 0;                                            // the query's terms with a list in the segment
     for (uint32_t i = lane; i < A; i += 64) { const uint32_t t = term[i]; if (t != kNoTerm) ne += ix.seg_off[(uint64_t)t * S1 + (uint32_t)B + 1u] != ix.seg_off[(uint64_t)t * S1 + (uint32_t)B]; }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) ne += (uint32_t)__shfl_xor((int)ne, off, 64);
-    if ((int)ne < T) continue;
+    if ((int)wave_sum_u32(ne) < T) continue;                     // searcher.go:32
     for (uint32_t j = lane; j < n_seg; j += 64) cnt[j] = 0u;
     __threadfence();
     __syncthreads();
@@ -2501,19 +2545,6 @@ struct SpellArgs {
   uint32_t slot_mul;                                           // bytes of a query's slot in w_blob per byte of the query (2; 3 when U+FFFD is in the alphabet)
 };
 
-// (P: SpellArgs, or the builder's own small tables of lm_build.inc — any struct with these fields)
-template <class P> __device__ __forceinline__ bool d_lm_alpha_has(const P& p, uint32_t r) {
-  if (r < 128u) return (p.alpha_ascii[r >> 6] >> (r & 63u)) & 1ull;
-  uint32_t lo = 0, hi = p.n_alpha_ranges;
-  while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (p.alpha_ranges[mid].y < r) lo = mid + 1; else hi = mid; }
-  return lo < p.n_alpha_ranges && p.alpha_ranges[lo].x <= r;
-}
-template <class P> __device__ __forceinline__ uint32_t d_lm_lower(const P& p, uint32_t r) {
-  if (r < 0x80u) return (r - 'A' < 26u) ? r + 32u : r;
-  uint32_t lo = 0, hi = p.n_lower;
-  while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (p.lower_from[mid] < r) lo = mid + 1; else hi = mid; }
-  return (lo < p.n_lower && p.lower_from[lo] == r) ? p.lower_to[lo] : r;
-}
 __device__ __forceinline__ uint64_t d_word_hash_step(uint64_t h, uint32_t byte) { return (h ^ (uint64_t)byte) * 0x100000001B3ull; }   // FNV-1a
 #define SG_WORD_HASH_SEED 0xCBF29CE484222325ull
 __device__ uint32_t d_word_id(const SpellArgs& p, uint64_t h, const uint8_t* w, uint32_t n) {
@@ -2579,16 +2610,12 @@ __device__ __forceinline__ void spell_tokenize_one(const SpellArgs& p, uint32_t 
   };
   for (uint32_t pos = a; pos < b;) {
     uint32_t adv;
-    const uint32_t r = d_lm_lower(p, d_next_rune(q + pos, b - pos, &adv));
+    const uint32_t r = d_lower_pairs(p, d_next_rune(q + pos, b - pos, &adv));
     pos += adv;
     if (!d_lm_alpha_has(p, r)) { end_token(); continue; }
     if (out == start) h = SG_WORD_HASH_SEED;                   // a new token
     uint8_t enc[4];
-    const uint32_t w = d_width(r);
-    if (w == 1u) enc[0] = (uint8_t)r;
-    else if (w == 2u) { enc[0] = (uint8_t)(0xC0u | (r >> 6)); enc[1] = (uint8_t)(0x80u | (r & 0x3Fu)); }
-    else if (w == 3u) { enc[0] = (uint8_t)(0xE0u | (r >> 12)); enc[1] = (uint8_t)(0x80u | ((r >> 6) & 0x3Fu)); enc[2] = (uint8_t)(0x80u | (r & 0x3Fu)); }
-    else { enc[0] = (uint8_t)(0xF0u | (r >> 18)); enc[1] = (uint8_t)(0x80u | ((r >> 12) & 0x3Fu)); enc[2] = (uint8_t)(0x80u | ((r >> 6) & 0x3Fu)); enc[3] = (uint8_t)(0x80u | (r & 0x3Fu)); }
+    const uint32_t w = d_put_rune(enc, r);
     for (uint32_t j = 0; j < w; j++) { slot[out + j] = enc[j]; h = d_word_hash_step(h, enc[j]); }
     out += w;
   }

@@ -1,5 +1,5 @@
 // lm_build.inc — the language model built from a corpus on the device (sg_lm_build_device), included by capi.inc, whose
-// DeviceBlock, device_exclusive_sum and device_total it uses, behind the word tokeniser's helpers of engine.hip (d_next_rune, d_lm_lower, d_lm_alpha_has), which it reuses.
+// DeviceBlock, device_exclusive_sum and device_total it uses, behind the word tokeniser's helpers of engine.hip (d_next_rune, d_lower_pairs, d_lm_alpha_has, d_put_rune), which it reuses.
 //
 // What it restates: NGramBuilder.Build over NewSentenceRetriever (pkg/lm/ngram_builder.go:19-64, sentence_retriever.go:54-81),
 // lm.NewTokenizer, buildDictionary's numbering (binary.go:140-198) and the vector builder as lm_load_google restates it — the
@@ -38,7 +38,7 @@ struct LmRuneSet {                // alphabet.Has as d_lm_alpha_has reads it
   const uint2* alpha_ranges; uint32_t n_alpha_ranges;   // runes >= 128 as inclusive ranges, ascending
   uint64_t alpha_ascii[2];                              // ... and below 128 as a bitmap
 };
-struct LmLowerTable { const uint32_t* lower_from; const uint32_t* lower_to; uint32_t n_lower; };   // d_lm_lower's pairs
+struct LmLowerTable { const uint32_t* lower_from; const uint32_t* lower_to; uint32_t n_lower; };   // as d_lower_pairs reads it
 
 struct LmBuildArgs {
   LmRuneSet alpha, sep;           // the model's alphabet; the sentence separators
@@ -56,7 +56,7 @@ enum { LMB_OTHER = 0, LMB_ALPHA = 1, LMB_SEP = 2, LMB_END = 3 };
 __device__ __forceinline__ uint32_t lm_build_classify(const LmBuildArgs& a, const uint8_t* s, uint32_t n, uint32_t* adv, uint32_t* low) {
   const uint32_t r = d_next_rune(s, n, adv);
   if (d_lm_alpha_has(a.sep, r)) return LMB_SEP;                  // (the raw rune: sentence_retriever.go:60-70)
-  *low = d_lm_lower(a.lower, r);
+  *low = d_lower_pairs(a.lower, r);
   return d_lm_alpha_has(a.alpha, *low) ? LMB_ALPHA : LMB_OTHER;
 }
 
@@ -101,13 +101,7 @@ __global__ __launch_bounds__(256) void lm_build_walk(const LmBuildArgs a) {
       if (nxt < rel_len) n_cls = lm_build_classify(a, s + nxt, n_at(nxt), &n_adv, &n_low);
       if (cls == LMB_ALPHA) {
         const uint32_t w = d_width(low);
-        if (kEmit) {
-          uint8_t* o = a.blob + bytes;
-          if (w == 1u) o[0] = (uint8_t)low;
-          else if (w == 2u) { o[0] = (uint8_t)(0xC0u | (low >> 6)); o[1] = (uint8_t)(0x80u | (low & 0x3Fu)); }
-          else if (w == 3u) { o[0] = (uint8_t)(0xE0u | (low >> 12)); o[1] = (uint8_t)(0x80u | ((low >> 6) & 0x3Fu)); o[2] = (uint8_t)(0x80u | (low & 0x3Fu)); }
-          else { o[0] = (uint8_t)(0xF0u | (low >> 18)); o[1] = (uint8_t)(0x80u | ((low >> 12) & 0x3Fu)); o[2] = (uint8_t)(0x80u | ((low >> 6) & 0x3Fu)); o[3] = (uint8_t)(0x80u | (low & 0x3Fu)); }
-        }
+        if (kEmit) d_put_rune(a.blob + bytes, low);
         bytes += w;
         if (n_cls != LMB_ALPHA) {                                // the token ends with this rune
           if (kEmit) { a.tok_end[toks] = bytes; a.tok_sent[toks] = seps; }

@@ -57,7 +57,7 @@ __global__ __launch_bounds__(256) void lm_text_tokenize_kernel(const LmScoreArgs
   uint32_t out = 0, start = 0, nt = 0;
   while (pos < b) {
     uint32_t adv;
-    const uint32_t r = d_lm_lower(p, d_next_rune(q + pos, b - pos, &adv));
+    const uint32_t r = d_lower_pairs(p, d_next_rune(q + pos, b - pos, &adv));
     pos += adv;
     if (!d_lm_alpha_has(p, r)) {
       if (out != start) { tk[nt++] = start; start = out; }

@@ -99,7 +99,8 @@ struct PipeArgs {
 };
 
 // (SG_PHASE_TIMING builds only — tools/gpu_job.sh plan_stages: the plan / verify launch cut short behind stage n, SG_DEBUG_SKIP = n << 20 /
-//  n << 24; rows are wrong when set)
+//  n << 24; rows are wrong when set.  PLAN_STAGE stands in plan_one_query alone and closes the slot with that function's `done`; sg_plan2_kernel's
+//  own path has no stages, so such a run sets SG_PLAN2=0)
 #ifdef SG_PHASE_TIMING
 #define PLAN_STAGE(n) if (((a.dbg_skip >> 20) & 15u) == (n)) { done(0u); return; }
 #define VERIFY_STAGE(n) if (((a.dbg_skip >> 24) & 15u) == (n)) return;
@@ -108,14 +109,22 @@ struct PipeArgs {
 #define VERIFY_STAGE(n)
 #endif
 __device__ __forceinline__ uint32_t rfl(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
-__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, off, 64));
-  return v;
-}
 // ------------------------------------------------------------------------------------------
 // plan: one wavefront per query slot (slot s of the piece = position b0 + s of the batch / the ordered list)
 // ------------------------------------------------------------------------------------------
+// ---- how both plan launches close a slot without a plan (`writer`: lane 0 in plan_one_query, the first lane of a half in sg_plan2_kernel) ----
+// nothing to stream, nothing to verify: empty records, the candidate count says so
+__device__ __forceinline__ void plan_skip_slot(const PipeArgs& p, uint32_t s, uint32_t qi, uint32_t* rec, uint32_t* vrec) {
+  p.cand_n[s] = SG_PIPE_SKIP; *(uint4*)vrec = make_uint4(0u, qi, 0u, 0u); *(uint4*)rec = make_uint4(0u, 0u, SG_PIPE_NO_OVF, 0u);
+}
+// the query's row is final: its count, or the flag of its window or of its length
+__device__ __forceinline__ void plan_close(const BatchArgs& a, const PipeArgs& p, uint32_t s, uint32_t qi, uint32_t* rec, uint32_t* vrec, bool writer, uint32_t status) {
+  if (writer) { a.out_counts[qi] = status; plan_skip_slot(p, s, qi, rec, vrec); }
+}
+// the fused kernel answers this query
+__device__ __forceinline__ void plan_hand_back(const PipeArgs& p, uint32_t s, uint32_t qi, uint32_t* rec, uint32_t* vrec, bool writer) {
+  if (writer) { p.fb_list[atomicAdd(p.fb_n, 1u)] = qi; plan_skip_slot(p, s, qi, rec, vrec); atomicAdd(p.stat + SG_STAT_UNPLANNED, 1u); }
+}
 // One query planned by one wavefront: slot s of the piece (rows: SG_PIPE_ROWS_WORDS words of LDS; m16_lane: the launch's row of
 // kBucketsPer16Postings, lane t holds entry min(t, 32)).  sg_plan_kernel is this and nothing else; sg_plan2_kernel (plan2.inc) calls
 // it for the queries its two-per-wavefront path does not take.
@@ -135,12 +144,8 @@ __device__ __forceinline__ void plan_one_query(const BatchArgs& a, const PipeArg
     if (lane < A) t_mine = term[lane];                          // (A > 64: left to the fused kernel below)
     __syncthreads();
   }
-  auto done = [&](uint32_t status) {                        // the row is final: nothing to stream, nothing to verify
-    if (lane == 0) { a.out_counts[qi] = status; p.cand_n[s] = SG_PIPE_SKIP; *(uint4*)vrec = make_uint4(0u, qi, 0u, 0u); *(uint4*)rec = make_uint4(0u, 0u, SG_PIPE_NO_OVF, 0u); }
-  };
-  auto fallback = [&]() {                                   // the fused kernel answers this query
-    if (lane == 0) { p.fb_list[atomicAdd(p.fb_n, 1u)] = qi; p.cand_n[s] = SG_PIPE_SKIP; *(uint4*)vrec = make_uint4(0u, qi, 0u, 0u); *(uint4*)rec = make_uint4(0u, 0u, SG_PIPE_NO_OVF, 0u); atomicAdd(p.stat + SG_STAT_UNPLANNED, 1u); }
-  };
+  auto done = [&](uint32_t status) { plan_close(a, p, s, qi, rec, vrec, lane == 0, status); };
+  auto fallback = [&]() { plan_hand_back(p, s, qi, rec, vrec, lane == 0); };
   PLAN_STAGE(1u)
   if (A < 0) {                                               // beyond the wavefront kernels' tables: sg_long_kernel
     if (lane == 0 && a.long_list) a.long_list[1u + atomicAdd(a.long_list, 1u)] = qi;
@@ -215,21 +220,10 @@ __device__ __forceinline__ void plan_one_query(const BatchArgs& a, const PipeArg
   if (lane < W) {
     const int B = b_min + lane;
     seg_T = d_threshold(a.metric, a.alpha, A, B, a.mt);
-    seg_valid = !(seg_T == 0 || seg_T > B || seg_T > A) && (int)seg_ne >= seg_T;   // suggester.go:76, searcher.go:32
+    seg_valid = segment_admissible(seg_T, B, A) && (int)seg_ne >= seg_T;   // searcher.go:32
   }
   const uint64_t vmask = ballot(seg_valid);
-  uint32_t seg_need = 0, need_p = 0;
-  int need_T = 0;
-  if (seg_valid) {
-    const int ks = seg_T > a.t_floor ? min(seg_T - a.t_floor, A - 1) : 0;
-    const uint32_t rem = seg_tot - (uint32_t)((float)seg_tot * (float)ks * (1.0f / (float)A));
-    need_T = seg_T - ks; need_p = min(rem, 1u << 21) * SG_PPC;     // (capped: 2^21 chunks are far beyond any counter array, and postings x a table entry stay below 2^32)
-  }
-  {
-    const uint32_t m16 = (uint32_t)__builtin_amdgcn_ds_bpermute((need_T < 0 ? 0 : (need_T > 32 ? 32 : need_T)) << 2, (int)m16_lane);   // (buckets_needed_lane; every lane takes part in the permute)
-    const uint32_t bn = __umul24(need_p, m16) >> 4;                       // (need_p < 2^24)
-    if (seg_valid) seg_need = max(1u, bn);
-  }
+  const uint32_t seg_need = segment_need(seg_valid, seg_T, seg_tot, A, a.t_floor, m16_lane);
   const uint32_t P_need = wave_scan_incl(min(seg_need, 1u << 24), lane), P_tot = wave_scan_incl(seg_valid ? seg_tot : 0u, lane);
   PLAN_STAGE(4u)
 
@@ -272,7 +266,7 @@ __device__ __forceinline__ void plan_one_query(const BatchArgs& a, const PipeArg
       for (int f = 0; f < 4; f++) {
         if (budget > 0) {
           const uint64_t m = ballot(x0 > th[f]) & ~pick;
-          const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+          const uint32_t rank = lane_rank(m);
           const uint64_t keep = m & ballot((int)rank < budget);        // (mask arithmetic is scalar: no per-lane test of m's bit)
           pick |= keep;
           budget -= (int)popc64(keep);
@@ -296,7 +290,7 @@ __device__ __forceinline__ void plan_one_query(const BatchArgs& a, const PipeArg
     // ---- the group's streamed lists, one behind the other in query order (the stream workgroup cuts them into sub-rows of
     //      2^sub chunks — rows of 64 lanes, a group starts a new row — and keeps the sub-rows of ALL the query's groups in LDS) ----
     const uint64_t rm = ballot(streamed);
-    const uint32_t pos = __builtin_amdgcn_mbcnt_hi((uint32_t)(rm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)rm, 0u)), n_l = popc64(rm);
+    const uint32_t pos = lane_rank(rm), n_l = popc64(rm);
     const uint32_t nd = streamed ? (ln + G - 1u) >> sub : 0u;
     const uint32_t n_sub = readlane(wave_scan_incl(nd, lane), 63), n_rows = (n_sub + dpr - 1u) / dpr;
     if (doff + n_l > SG_PIPE_MAX_LISTS || n_rows > p.dt_rows) { bail = true; break; }     // (a group's sub-rows fit the stream workgroup's table; a query's need not: windows)
@@ -605,8 +599,7 @@ __device__ __forceinline__ void verify_one_query(const BatchArgs& a, const PipeA
   VERIFY_STAGE(1u)
   const int A = (int)readlane(f.h, 2);                         // 1 .. 64 (the plan let it through)
   const uint32_t t_mine = lane < A ? f.t : kNoTerm;
-  // the query's terms as an LDS hash (an occurrence = an entry: a repeated term sits in consecutive probe slots)
-  for (uint32_t i = lane; i < SG_PIPE_QH; i += 64) qh_key[i] = kNoTerm;
+  for (uint32_t i = lane; i < SG_PIPE_QH; i += 64) qh_key[i] = kNoTerm;                           // the query-term hash (d_qhash)
   if (strided) { sb_lds[lane] = lane <= S ? sb_load : 0xFFFFFFFFu; fb_lds[lane] = fb_load; }      // (S <= 63: entries 0 .. S, then sentinels)
   __syncthreads();
   if (t_mine != kNoTerm)
@@ -617,9 +610,8 @@ __device__ __forceinline__ void verify_one_query(const BatchArgs& a, const PipeA
   //  segments only — MinY <= B <= MaxY, 0 < T(B) <= min(A, B), suggester.go:53-59,76 — so its document's segment is one of them.)
   VERIFY_STAGE(2u)
   TopK tk;
-  if (kBigK) { tk.s = a.scratch_s + (uint64_t)qi * k; tk.id = a.scratch_id + (uint64_t)qi * k; }
-  else { tk.s = tk_s_lds; tk.id = tk_id_lds; }
-  tk.n = 0; tk.k = k; tk.worst_s = 0; tk.worst_id = 0; tk.worst_pos = 0;
+  if (kBigK) topk_begin(tk, a.scratch_s + (uint64_t)qi * k, a.scratch_id + (uint64_t)qi * k, k);
+  else topk_begin(tk, tk_s_lds, tk_id_lds, k);
   bool give_up = false;
   for (uint32_t base = 0; base < n_c && !give_up; base += 64) {
     const uint32_t n_raw = min(64u, n_c - base);
@@ -631,7 +623,7 @@ __device__ __forceinline__ void verify_one_query(const BatchArgs& a, const PipeA
       bool dup = false;
       for (uint32_t i = 0; i + 1u < n_raw; i++) dup |= readlane(my_doc, (int)i) == my_doc && i < (uint32_t)lane;
       const uint64_t keep = ballot((uint32_t)lane < n_raw && !dup);
-      const uint32_t to = __builtin_amdgcn_mbcnt_hi((uint32_t)(keep >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)keep, 0u));
+      const uint32_t to = lane_rank(keep);
       const bool mine = (keep >> lane) & 1ull;
       my_doc = (uint32_t)__builtin_amdgcn_ds_permute((int)((mine ? to : 63u) << 2), (int)my_doc);   // (lanes that send nothing aim at lane 63: it holds a first occurrence only if all 64 are distinct, and then sends to itself)
       n = popc64(keep);

@@ -65,12 +65,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8), amdgp
   uint32_t* rec = p.rec + (uint64_t)s * SG_PIPE_REC_STRIDE;
   uint32_t* vrec = p.vrec + (uint64_t)s * p.vrec_words;
   const bool first = hl == 0u;                                 // the lane that writes a half's scalars
-  auto finish = [&](bool which, uint32_t status) {           // rows final: nothing to stream, nothing to verify
-    if (which && first) { a.out_counts[qi] = status; p.cand_n[s] = SG_PIPE_SKIP; *(uint4*)vrec = make_uint4(0u, qi, 0u, 0u); *(uint4*)rec = make_uint4(0u, 0u, SG_PIPE_NO_OVF, 0u); }
-  };
-  auto to_fused = [&](bool which) {                          // the fused kernel answers
-    if (which && first) { p.fb_list[atomicAdd(p.fb_n, 1u)] = qi; p.cand_n[s] = SG_PIPE_SKIP; *(uint4*)vrec = make_uint4(0u, qi, 0u, 0u); *(uint4*)rec = make_uint4(0u, 0u, SG_PIPE_NO_OVF, 0u); atomicAdd(p.stat + SG_STAT_UNPLANNED, 1u); }
-  };
+  auto finish = [&](bool which, uint32_t status) { plan_close(a, p, s, qi, rec, vrec, which && first, status); };
 
   // ---- tokenise (pkg/suggest/tokenizer.go:9-34), the ASCII path of d_tokenize for two queries side by side ----
   const uint32_t n_w0 = ix.n_wrap0, n_w1 = ix.n_wrap1, q_n = ix.q;
@@ -211,21 +206,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8), amdgp
   if (act && hl < (uint32_t)W) {
     const int B = b_min + (int)hl;
     seg_T = d_threshold(a.metric, a.alpha, A, B, a.mt);
-    seg_valid = !(seg_T == 0 || seg_T > B || seg_T > A) && (int)seg_ne >= seg_T;   // suggester.go:76, searcher.go:32
+    seg_valid = segment_admissible(seg_T, B, A) && (int)seg_ne >= seg_T;   // searcher.go:32
   }
   const uint32_t vmask = h_ballot(seg_valid, hb);
-  uint32_t seg_need = 0, need_p = 0;
-  int need_T = 0;
-  if (seg_valid) {
-    const int ks = seg_T > a.t_floor ? min(seg_T - a.t_floor, A - 1) : 0;
-    const uint32_t rem = seg_tot - (uint32_t)((float)seg_tot * (float)ks * (1.0f / (float)A));
-    need_T = seg_T - ks; need_p = min(rem, 1u << 21) * SG_PPC;
-  }
-  {
-    const uint32_t m16 = (uint32_t)__builtin_amdgcn_ds_bpermute((need_T < 0 ? 0 : (need_T > 32 ? 32 : need_T)) << 2, (int)m16_lane);
-    const uint32_t bn = __umul24(need_p, m16) >> 4;
-    if (seg_valid) seg_need = max(1u, bn);
-  }
+  const uint32_t seg_need = segment_need(seg_valid, seg_T, seg_tot, A, a.t_floor, m16_lane);
   const uint32_t P_need = h_scan_incl(min(seg_need, 1u << 24)), P_tot = h_scan_incl(seg_valid ? seg_tot : 0u);
 
   // ---- the groups: both halves step through their own, side by side, until both are done ----
@@ -305,7 +289,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8), amdgp
     if (wr) { n_items++; doff += n_l; rows_total += n_rows; q_chunks += Leff; }
     bail = bail || stop;
   }
-  to_fused(act && bail);
+  plan_hand_back(p, s, qi, rec, vrec, act && bail && first);
   if (act && !bail && first) {
     *(uint4*)rec = make_uint4(n_items, doff, ovf_blk, rows_total);
     *(uint4*)vrec = make_uint4(0u, qi, (uint32_t)A, 0u);
