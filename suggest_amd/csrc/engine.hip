@@ -217,16 +217,25 @@ __device__ __forceinline__ uint32_t popc64(uint64_t m) { return (uint32_t)__buil
 __device__ __forceinline__ uint32_t readlane(uint32_t v, int l) { return (uint32_t)__builtin_amdgcn_readlane((int)v, l); }
 // a lane's rank among the lanes of a ballot: the set bits below its own (v_mbcnt_lo / _hi: no shift by the lane number)
 __device__ __forceinline__ uint32_t lane_rank(uint64_t m) { return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u)); }
-// maximum / sum over the wave, in every lane (butterfly)
+// maximum / sum over the wave (all 64 lanes on), wavefront-uniform: a scalar, read from lane 63 of a DPP reduction (row_shr
+// 1, 2, 4, 8 inside rows of 16 lanes, then row_bcast:15 / row_bcast:31 carry the rows' results) — no LDS operation
 __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, off, 64));
-  return v;
+  v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, true));    // row_shr:1 (lanes without a source take 0)
+  v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, true));
+  v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, true));
+  v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, true));
+  v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false));   // row_bcast:15 -> rows 1, 3
+  v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false));   // row_bcast:31 -> rows 2, 3
+  return readlane(v, 63);
 }
 __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += (uint32_t)__shfl_xor((int)v, off, 64);
-  return v;
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, true);
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, true);
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, true);
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, true);
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false);
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false);
+  return readlane(v, 63);
 }
 // minimum over the wave (DPP network, as wave_scan_incl)
 __device__ __forceinline__ int wave_min_i32(int v) {
@@ -844,6 +853,7 @@ __device__ __forceinline__ uint32_t segment_need(bool valid, int T, uint32_t tot
 typedef uint32_t u32x16 __attribute__((ext_vector_type(16)));
 typedef uint32_t u32x8v __attribute__((ext_vector_type(8)));
 typedef uint32_t u32x4v __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x2v __attribute__((ext_vector_type(2)));
 static_assert(SG_UNROLL == 4 && SG_SUB == 2 && SG_SUB * SG_PPC <= 16, "u32x16 below holds SG_SUB rows x SG_PPC postings");
 
 // The SG_PPC slots of one packed chunk: first x, then six 16-bit gaps.  Returns how many of them are postings (the top
@@ -879,6 +889,8 @@ __device__ __forceinline__ uint32_t decode_chunk8(const uint4& v, V& p, int at) 
 // chunk and add 0).  Returns the ballot of lanes holding a posting whose bucket reached T; `pp` receives the decoded
 // postings, `was` the counts seen.
 typedef __attribute__((address_space(3))) uint32_t lds_u32;
+typedef __attribute__((address_space(3))) u32x2v lds_u32x2;      // (typed by address space: a load through one is a ds_read / global_load
+typedef __attribute__((address_space(1))) u32x2v glb_u32x2;      //  whatever the compiler makes of the code around it, never a flat one)
 
 // LDS byte address of the counter word of doc d.  amask selects the bucket bits of the docID and is
 // already a byte mask, cbase is the LDS address of the counter array, so the address is ONE v_and_or_b32:

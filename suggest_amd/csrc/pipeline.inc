@@ -354,7 +354,7 @@ __device__ __forceinline__ uint64_t pipe_count_row(const uint4& v, uint32_t live
                                                    uint32_t (&pp)[SG_PPC], uint32_t (&old)[SG_PPC]) {
   const uint32_t g[SG_PPC] = {0u, v.y & 0xFFFFu, v.y >> 16, v.z & 0xFFFFu, v.z >> 16, v.w & 0xFFFFu, v.w >> 16};
   const uint32_t am = live ? amask : 0u;
-  const uint32_t cb = live ? cbase : cbase + lane4;
+  const uint32_t cb = cbase | (live ? 0u : lane4);                  // (the counters are aligned to their size, as counter_word has it: | is +, and folds where cbase is 0)
   uint32_t d = v.x & SG_X_MASK;
 #pragma unroll
   for (int e = 0; e < SG_PPC; e++) {
@@ -454,17 +454,27 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_num_sgpr(80))) void 
     for (uint32_t it = win_lo + wave; it < win_hi; it += NW) {
       const uint32_t w1 = readlane(w1_mine, (int)it), w2 = readlane(w2_mine, (int)it);
       const uint32_t n_l = w1 >> 12, loff = w2 & 0xFFFFu, D0 = readlane(r0_mine, (int)it) * dpr, n_d = (w2 >> 16) * dpr;
-      uint32_t ls = 0, ln = 0;
-      if (lane < n_l) {
-        const uint32_t li = loff + lane;
-        const uint2 e = li < SG_PIPE_REC_LISTS ? *(const uint2*)(S + SG_PIPE_REC_HDR + 2u * li) : *(const uint2*)(ovf + SG_PIPE_OVF_HDR + 2u * (li - SG_PIPE_REC_LISTS));
-        ls = e.x; ln = e.y;
+      // the list's entry {first chunk, chunks}: an LDS read where the whole group lies in the staged record (every group of a
+      // query without an overflow block), else the record's entries from LDS and the block's from memory — never a flat load
+      u32x2v e = {0u, 0u};
+      const uint32_t li = loff + lane;
+      const lds_u32x2* e_rec = (const lds_u32x2*)(lds_u32*)(S + SG_PIPE_REC_HDR) + li;
+      if (__builtin_expect(loff + n_l <= SG_PIPE_REC_LISTS, 1)) {
+        if (lane < n_l) e = *e_rec;
+      } else {
+        const glb_u32x2* e_ovf = (const glb_u32x2*)(ovf + SG_PIPE_OVF_HDR) + (li - SG_PIPE_REC_LISTS);
+        if (lane < n_l && li < SG_PIPE_REC_LISTS) e = *e_rec;
+        if (lane < n_l && li >= SG_PIPE_REC_LISTS) e = *e_ovf;
+        asm volatile("" : "+v"(e));                                        // (the block's entries waited for here: the record's path waits for its LDS read alone)
       }
+      uint32_t ls = e.x, ln = e.y;
       const uint32_t nd = (ln + G - 1u) >> sub;
-      const uint32_t incl = wave_scan_incl(nd, (int)lane), pre = incl - nd, total = readlane(incl, 63);
-      const uint32_t nd_max = wave_max_u32(nd);
-      for (uint32_t o = 0; o < nd_max; o++)
-        if (o < nd) D[D0 + pre + o] = PD::make(ls + o * G, min(G, ln - o * G));
+      const uint32_t incl = wave_scan_incl(nd, (int)lane), total = readlane(incl, 63);
+      for (uint32_t d = D0 + incl - nd; ln; d++) {                        // (the lanes with sub-rows left to write: no bound over the wavefront)
+        const uint32_t n = min(G, ln);
+        D[d] = PD::make(ls, n);
+        ls += G; ln -= n;
+      }
       if (total + lane < n_d) D[D0 + total + lane] = PD::make(0u, 0u);   // what is left of the group's last row
     }
     __syncthreads();
