@@ -177,8 +177,13 @@ int sg_autocomplete_batch_multi(sg_index* index, const uint8_t* q_utf8, const ui
  * documents the primary entries are the same, but the reference's SECONDARY duplicate rows depend on the relative
  * lengths of posting lists, which differ inside a shard: those rows can differ from the unsharded index's (they always equal the
  * merge of the shards' own rows).
- * Concurrency: the host-buffer calls of one handle share its streams and staging and take turns behind a mutex in the handle;
- * the device-resident call writes nothing of the handle and may run from any number of threads and streams at once. */
+ * Concurrency: any number of threads may call one handle at once.  A host-buffer call stages, copies and waits on the calling
+ * thread's own stream and buffers, as sg_suggest_batch does; on a handle with several lanes it holds a mutex in the handle while
+ * it enqueues on the lanes' streams, no longer.  A handle with one lane takes no lock, and neither does the device-resident call,
+ * which writes nothing of the handle.
+ * A host-buffer call goes the way of every other one, so a batch whose inputs or merged rows pass 64 MiB is copied straight from
+ * and to the caller's memory instead of through pinned staging, and a batch whose offsets do not start at zero AND whose inputs
+ * pass 64 MiB is refused: SG_E_INVALID, "batch slice too large to stage". */
 typedef struct sg_sharded sg_sharded;
 #define SG_MAX_SHARDS 64u        /* a design limit: 8 GPUs with 8 shards each */
 
@@ -204,9 +209,11 @@ void sg_sharded_release(sg_sharded* sharded);
 /* The shards that stand, in docID order: fills up to cap entries of out_doc_lo / out_devices (either may be NULL), returns their number. */
 uint32_t sg_sharded_shards(const sg_sharded* sharded, uint64_t* out_doc_lo, int* out_devices, uint32_t cap);
 
-/* sg_suggest_batch over every shard, merged: host buffers, synchronous.  The queries are uploaded once per device; the batch
- * goes through in slices of queries whose [shard][query][k] block of ids, scores and counts stays within 256 MiB; rows of a
- * device other than shard 0's are copied there asynchronously behind their searches and ordered by events. */
+/* sg_suggest_batch over every shard, merged: host buffers, synchronous.  The queries are uploaded once, to shard 0's device,
+ * and copied from there once to every other device that holds a lane; the batch goes through in slices of queries whose
+ * [shard][query][k] block of ids, scores and counts stays within 256 MiB, and the merged rows of the whole batch come back in
+ * one copy; rows of a lane other than shard 0's are copied to its block asynchronously behind their searches and ordered by
+ * events. */
 int sg_sharded_suggest_batch(sg_sharded* sharded, const uint8_t* q_utf8, const uint64_t* q_offs, uint32_t n_q, int metric,
                              double similarity, uint32_t k, uint32_t* out_ids, double* out_scores, uint32_t* out_counts);
 /* The same on buffers resident in HBM, asynchronous on `stream` — searches and merge are enqueued there, the shards' rows stay

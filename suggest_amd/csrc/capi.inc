@@ -417,9 +417,9 @@ struct GrowBlock {
 // dropping a buffer never pulls it from under a running kernel.
 // A block per tag: one launch holds SCRATCH_ROWS, SCRATCH_LONG_LIST and one of SCRATCH_PRETOK / SCRATCH_PIPE of its stream at
 // once, and Predict's block besides when Predict is the caller — four at most.  Sentence scoring (lm_score.inc) holds its own
-// block alone.  A device-resident sharded search (shard_merge.inc) holds SCRATCH_SHARD, the shards' rows, around its launches.
+// block alone.  A sharded search (shard_merge.inc) holds SCRATCH_SHARD, the shards' rows, around its launches.
 enum ScratchTag { SCRATCH_ROWS = 0, SCRATCH_PREDICT = 1, SCRATCH_LONG_LIST = 2, SCRATCH_PRETOK = 3, SCRATCH_PIPE = 4, SCRATCH_LM_SCORE = 5, SCRATCH_SHARD = 6 };
-struct ScratchSlot { int device; hipStream_t stream; int tag; GrowBlock blk; };
+struct ScratchSlot { int device; hipStream_t stream; int tag; GrowBlock blk; bool held = false; };
 inline bool on_main_thread() { return (long)getpid() == (long)syscall(SYS_gettid); }
 // (a thread that ends hands its buffers back; the main thread's are left to process exit, when the HIP runtime may already
 //  be going down)
@@ -441,7 +441,7 @@ int stream_scratch(int device, hipStream_t stream, size_t bytes, void** out, Scr
     // for the device, so nothing running loses its memory)
     if (t_scratch.size() >= 16) {
       for (size_t i = 0; i < t_scratch.size(); i++) {
-        if (t_scratch[i].device == device && t_scratch[i].stream == stream) continue;
+        if ((t_scratch[i].device == device && t_scratch[i].stream == stream) || t_scratch[i].held) continue;
         if (t_scratch[i].blk.p) { (void)hipSetDevice(t_scratch[i].device); t_scratch[i].blk.release(); (void)hipSetDevice(device); }
         t_scratch.erase(t_scratch.begin() + (long)i);
         break;
@@ -453,6 +453,12 @@ int stream_scratch(int device, hipStream_t stream, size_t bytes, void** out, Scr
   if (int rc = sl->blk.grow(bytes)) return rc;
   *out = sl->blk.p;
   return SG_OK;
+}
+
+// A block its holder keeps across this thread's launches on OTHER streams (a sharded call with lanes, shard_merge.inc): not
+// recycled while held
+void scratch_hold(int device, hipStream_t stream, ScratchTag tag, bool on) {
+  for (auto& x : t_scratch) if (x.device == device && x.stream == stream && x.tag == tag) x.held = on;
 }
 
 // A block cut into regions, in order: take() places the next one at the first multiple of `align` bytes behind the last;
@@ -1651,15 +1657,20 @@ static LaunchReq search_req(int metric, double sim, uint32_t k, int autocomplete
   return r;
 }
 
+// LaunchReq::no_long_queries of a caller with host buffers, who knows its longest query: at most 112 bytes + the wrap runes stay
+// within the wavefront kernel's 144 runes / 128 n-grams, and the long-query launch — a few microseconds of a single query's
+// latency — is left out
+static bool no_long_queries(const uint64_t* offs, uint32_t n_q) {
+  uint64_t max_len = 0;
+  for (uint32_t i = 0; i < n_q; i++) max_len = std::max<uint64_t>(max_len, offs[i + 1] - offs[i]);
+  return max_len <= 112;
+}
+
 // the enqueue step of a search: launch() on the device block, with what the caller's buffers say
 static Enqueue search_enqueue(sg_index* index, Replica* rep, const LaunchReq& req, const HostBufs& b) {
   return [=](char* dev, const IoLayout& io, hipStream_t st) {
-    // (a caller with host buffers knows its longest query: at most 112 bytes + the wrap runes stay within the wavefront
-    //  kernel's 144 runes / 128 n-grams, and the long-query launch — a few microseconds of a single query's latency — is left out)
-    uint64_t max_len = 0;
-    for (uint32_t i = 0; i < b.n_q; i++) max_len = std::max<uint64_t>(max_len, b.offs[i + 1] - b.offs[i]);
     LaunchReq r = req;
-    r.q = dev + io.q; r.offs = dev + io.offs; r.n_q = b.n_q; r.stream = st; r.no_long_queries = max_len <= 112;
+    r.q = dev + io.q; r.offs = dev + io.offs; r.n_q = b.n_q; r.stream = st; r.no_long_queries = no_long_queries(b.offs, b.n_q);
     r.ids = dev + io.ids; r.scores = r.autocomplete ? nullptr : dev; r.counts = dev + io.cnt;
     r.out_aux = b.aux ? (uint32_t*)(dev + io.aux) : nullptr;
     return launch(index, rep, r);

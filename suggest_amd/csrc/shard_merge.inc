@@ -1,5 +1,7 @@
 // shard_merge.inc — a dictionary sharded by docID range behind one handle (sg_sharded, include/suggest_hip.h), included by
-// engine.hip after capi.inc (it uses launch(), build_any(), add_replica(), stream_scratch, GrowBlock, DeviceGuard, HIP_TRY).
+// engine.hip after capi.inc (it uses launch(), build_any(), add_replica(), stream_scratch, run_host_call, io_layout, GrowBlock,
+// DeviceGuard, HIP_TRY).  A sharded search is one enqueue step, sharded_enqueue: the device-resident call is that step on the
+// caller's stream, a host-buffer call is capi.inc's run_host_call around it, as every other host-buffer call is around its own.
 // SURVEY.md §8(e) / DESIGN.md §5: every shard indexes the documents [doc_lo, doc_lo + n) under local docIDs, built with the
 // dictionary-wide number of cardinality segments; a call searches the whole batch on every shard and sg_shard_merge_kernel
 // merges the per-shard top-k rows on the device under the reference's total order (score desc, docID asc; collector.go:20-26).
@@ -149,28 +151,29 @@ static inline uint32_t shard_slice_queries(uint32_t W, uint32_t k, bool scores, 
 
 }  // namespace sg
 
-// The shards of one entry of the device list (sg_sharded_build) or of one device (sg_sharded_adopt): a stream of their own, and
-// for host-buffer calls the queries and this lane's shard rows on that device.  Lane 0 holds shard 0: its device merges.
+// The shards of one entry of the device list (sg_sharded_build) or of one device (sg_sharded_adopt).  Lane 0 holds shard 0: its
+// device merges, and its shards run on the call's own stream into the call's own block — it keeps nothing.  Every other lane
+// has, for the host-buffer calls of a handle with several lanes, a stream of its own and its shards' rows on its device, and
+// on a device other than the merge device the queries.
 struct ShardLane {
   int device = -1;
-  uint32_t q_owner = 0;              // the first lane on the same device: the queries are uploaded once, into its block
+  uint32_t q_owner = 0;              // the first lane on the same device: the queries are copied there once, into its block
   std::vector<uint32_t> shards;      // ascending
   hipStream_t stream = nullptr;
   hipEvent_t ev_q = nullptr, ev_rows = nullptr;
-  GrowBlock q;                       // [offsets | queries] (the owner's)
-  GrowBlock rows;                    // lane 0: the merge's [W][m][k] block; others: [their shards][m][k], copied there
+  GrowBlock q;                       // [offsets | queries] (the owner's, on a device other than the merge device)
+  GrowBlock rows;                    // [this lane's shards][m][k], copied from here into the call's [W][m][k] block
 };
 
 struct sg_sharded {
   std::atomic<int> refs{1};
-  std::mutex mu;                     // host-buffer calls on one handle take turns: they share the lanes' streams and blocks
+  std::mutex mu;                     // held while a host-buffer call enqueues on lanes 1 ..: their streams, blocks and events
   std::vector<sg_index*> shard;      // retained
   std::vector<uint64_t> doc_lo;
   std::vector<int> device;           // of each shard's primary replica
   std::vector<ShardLane> lanes;
   bool one_device = true;            // every shard on the merge device: the device-resident call can run
-  GrowBlock out;                     // host-buffer calls: the merged rows of a slice on the merge device ...
-  GrowBlock pin_in{true}, pin_out{true};   // ... and the pinned staging both ways
+  hipEvent_t ev_st = nullptr;        // recorded on a call's stream for lanes 1 .. to wait for (sharded_enqueue)
   ~sg_sharded() {
     int prev = -1;
     (void)hipGetDevice(&prev);
@@ -182,9 +185,7 @@ struct sg_sharded {
       if (l.ev_rows) (void)hipEventDestroy(l.ev_rows);
       l.q.release(); l.rows.release();
     }
-    if ((out.p || pin_in.p || pin_out.p) && !lanes.empty() && hipSetDevice(lanes[0].device) == hipSuccess) {
-      out.release(); pin_in.release(); pin_out.release();
-    }
+    if (ev_st && hipSetDevice(lanes[0].device) == hipSuccess) (void)hipEventDestroy(ev_st);
     if (prev >= 0) (void)hipSetDevice(prev);
     (void)hipGetLastError();
     for (sg_index* ix : shard) sg_index_release(ix);
@@ -264,11 +265,11 @@ int sharded_search(sg_index* ix, const void* d_q, const uint64_t* d_offs, uint32
   return launch(ix, find_replica(ix, -1), r);
 }
 
-ShardMergeArgs sharded_merge_args(const sg_sharded* h, const char* blk, const ShardBlock& B, uint32_t m, uint32_t k, bool scores) {
+ShardMergeArgs sharded_merge_args(uint32_t W, const uint64_t* doc_lo, const char* blk, const ShardBlock& B, uint32_t m, uint32_t k, bool scores) {
   ShardMergeArgs a{};
   a.ids = (const uint32_t*)(blk + B.ids); a.scores = scores ? (const uint64_t*)blk : nullptr; a.counts = (const uint32_t*)(blk + B.cnt);
-  a.W = (uint32_t)h->shard.size(); a.n_q = m; a.k = k;
-  for (size_t s = 0; s < h->shard.size(); s++) a.doc_lo[s] = h->doc_lo[s];
+  a.W = W; a.n_q = m; a.k = k;
+  for (uint32_t s = 0; s < W; s++) a.doc_lo[s] = doc_lo[s];
   return a;
 }
 
@@ -277,139 +278,117 @@ int sharded_check_call(sg_sharded* h, uint32_t k, bool fuzzy, double similarity,
   return check_search_args(h->shard[0], k, fuzzy, similarity, metric);
 }
 
-// Device-resident: every shard searched on the caller's stream into the calling thread's block for (device, stream), merged
-// into the caller's rows.  Nothing of the handle is written: no lock.
-int sharded_run_device(sg_sharded* h, const void* d_q, const void* d_offs, uint32_t n_q, const LaunchReq& base, void* d_ids, void* d_scores,
-                       void* d_counts, hipStream_t st) {
-  if (n_q == 0) return SG_OK;
-  if (!d_offs || !d_ids || !d_counts || (!base.autocomplete && !d_scores)) { set_error("null argument"); return SG_E_INVALID; }
+// The enqueue step of a sharded search: n_q > 0 queries, their offsets and the three arrays of merged rows on shard 0's device,
+// everything enqueued slice by slice, nothing waited for; the device that was current is current again on return (a host-buffer
+// call: shard 0's).
+// with_lanes == false: every shard is searched on `st` into the calling thread's SCRATCH_SHARD block of (device, st) and merged
+// on `st` into the caller's rows at the slice's offset.  Nothing of the handle is written: no lock.
+// with_lanes == true (a host-buffer call on a handle with several lanes; d_q lies q_bytes long right behind the offsets, as in
+// IoLayout): lane 0's shards as above; every other lane searches its shards on its own stream into its own rows, copies them
+// into the SCRATCH_SHARD block behind each search and records ev_rows, which `st` waits for before the merge.  A lane on
+// another device gets one peer copy of [offsets | queries], on its own stream.  h->mu is held while this enqueues, no longer:
+// the lanes' streams order the calls of several threads, and each thread merges from a block of its own.
+int sharded_enqueue(sg_sharded* h, const char* d_q, const uint64_t* d_offs, uint32_t n_q, size_t q_bytes, const LaunchReq& base, uint32_t* d_ids,
+                    uint64_t* d_scores, uint32_t* d_counts, hipStream_t st, bool with_lanes) {
   const int dev = h->device[0];
-  hipPointerAttribute_t at;
-  bool there = h->one_device && hipPointerGetAttributes(&at, d_offs) == hipSuccess && at.type == hipMemoryTypeDevice && at.device == dev;
-  if (!there) {
-    (void)hipGetLastError();
-    set_error("sg_sharded_*_device: every shard has to be resident on the device that owns the buffers");
-    return SG_E_UNSUPPORTED;
-  }
-  DeviceGuard dg;
-  HIP_TRY(dg.set(dev));
-  const uint32_t W = (uint32_t)h->shard.size(), k = base.k;
-  const bool scores = !base.autocomplete;
-  const uint32_t slice = shard_slice_queries(W, k, scores, n_q);
-  void* blk = nullptr;
-  if (int rc = stream_scratch(dev, st, ShardBlock(W, slice, k, scores).bytes, &blk, SCRATCH_SHARD)) return rc;
-  for (uint32_t lo = 0; lo < n_q; lo += slice) {
-    const uint32_t m = std::min(slice, n_q - lo);
-    const ShardBlock B(W, m, k, scores);
-    for (uint32_t s = 0; s < W; s++)
-      if (int rc = sharded_search(h->shard[s], d_q, (const uint64_t*)d_offs + lo, m, base, (char*)blk, B, s, st)) return rc;
-    ShardMergeArgs a = sharded_merge_args(h, (const char*)blk, B, m, k, scores);
-    a.out_ids = (uint32_t*)d_ids + (size_t)lo * k;
-    a.out_scores = scores ? (uint64_t*)d_scores + (size_t)lo * k : nullptr;
-    a.out_counts = (uint32_t*)d_counts + lo;
-    if (int rc = enqueue_shard_merge(a, st)) return rc;
-  }
-  return SG_OK;
-}
-
-// Host buffers.  The queries go to every device once; per slice every lane searches its shards on its own stream, lanes other
-// than 0 copy their rows into lane 0's block behind their searches and record an event lane 0's stream waits for; the merge and
-// the copy back run there.  A slice ends with a wait for lane 0's stream alone — behind it every lane's work of the slice is done.
-int sharded_run_host(sg_sharded* h, const uint8_t* q, const uint64_t* offs, uint32_t n_q, LaunchReq base, uint32_t* ids, double* scores,
-                     uint32_t* counts) {
-  if (!offs || !ids || !counts || (!base.autocomplete && !scores)) { set_error("null argument"); return SG_E_INVALID; }
-  if (n_q == 0) return SG_OK;
-  const uint64_t q0 = offs[0], q_bytes = offs[n_q] - q0;
-  if (!q && q_bytes) { set_error("null query buffer"); return SG_E_INVALID; }
-  std::lock_guard<std::mutex> lock(h->mu);
   const uint32_t W = (uint32_t)h->shard.size(), k = base.k;
   const bool sc = !base.autocomplete;
-  const size_t off_bytes = ((size_t)n_q + 1) * 8, in_bytes = off_bytes + (size_t)q_bytes;
-  uint64_t max_len = 0;
-  for (uint32_t i = 0; i < n_q; i++) max_len = std::max<uint64_t>(max_len, offs[i + 1] - offs[i]);
-  base.no_long_queries = max_len <= 112;       // (as search_enqueue)
-  DeviceGuard dg;
-  ShardLane& L0 = h->lanes[0];
-  HIP_TRY(dg.set(L0.device));
-  // ---- the queries: staged once (offsets rebased to zero), copied to every device once ----
-  if (int rc = h->pin_in.grow(in_bytes)) return rc;
-  uint64_t* po = (uint64_t*)h->pin_in.p;
-  for (uint32_t i = 0; i <= n_q; i++) po[i] = offs[i] - q0;
-  if (q_bytes) memcpy((char*)h->pin_in.p + off_bytes, q + q0, (size_t)q_bytes);
-  struct Drain {       // a call that fails half way waits for what it enqueued: the blocks are the next call's
-    sg_sharded* h; bool armed = true;
-    ~Drain() { if (armed) for (auto& l : h->lanes) if (l.stream) (void)hipStreamSynchronize(l.stream); }
-  } drain{h};
-  for (auto& l : h->lanes) {
-    HIP_TRY(dg.set(l.device));
-    if (int rc = sharded_lane_init(l)) return rc;
-  }
-  for (size_t j = 0; j < h->lanes.size(); j++) {
-    ShardLane& l = h->lanes[j];
-    HIP_TRY(dg.set(l.device));
-    if (l.q_owner == j) {
-      if (int rc = l.q.grow(in_bytes)) return rc;
-      HIP_TRY(hipMemcpyAsync(l.q.p, h->pin_in.p, in_bytes, hipMemcpyHostToDevice, l.stream));
-      HIP_TRY(hipEventRecord(l.ev_q, l.stream));
-    } else HIP_TRY(hipStreamWaitEvent(l.stream, h->lanes[l.q_owner].ev_q, 0));
-  }
   const uint32_t slice = shard_slice_queries(W, k, sc, n_q);
-  const ShardBlock Bmax(W, slice, k, sc);
-  const size_t out_ids = sc ? (size_t)slice * k * 8 : 0, out_cnt = out_ids + (size_t)slice * k * 4, out_bytes = out_cnt + (size_t)slice * 4;
-  HIP_TRY(dg.set(L0.device));
-  if (int rc = L0.rows.grow(Bmax.bytes)) return rc;
-  if (int rc = h->out.grow(out_bytes)) return rc;
-  if (int rc = h->pin_out.grow(out_bytes)) return rc;
-  for (size_t j = 1; j < h->lanes.size(); j++) {
-    ShardLane& l = h->lanes[j];
-    HIP_TRY(dg.set(l.device));
-    if (int rc = l.rows.grow(ShardBlock((uint32_t)l.shards.size(), slice, k, sc).bytes)) return rc;
+  const size_t off_bytes = ((size_t)n_q + 1) * 8;
+  DeviceGuard dg;
+  HIP_TRY(dg.set(dev));
+  void* blk = nullptr;
+  if (int rc = stream_scratch(dev, st, ShardBlock(W, slice, k, sc).bytes, &blk, SCRATCH_SHARD)) return rc;
+  char* dst = (char*)blk;
+  std::unique_lock<std::mutex> lock(h->mu, std::defer_lock);
+  struct Drain {       // a call that fails half way waits for what it enqueued on the lanes: their blocks are the next call's
+    sg_sharded* h; bool armed;
+    ~Drain() { if (armed) for (auto& l : h->lanes) if (l.stream) (void)hipStreamSynchronize(l.stream); }
+  } drain{h, with_lanes};
+  struct Hold {        // the lanes' launches ask for scratch of their own streams: they must not recycle the block they copy into
+    int dev; hipStream_t st; bool on;
+    ~Hold() { if (on) scratch_hold(dev, st, SCRATCH_SHARD, false); }
+  } hold{dev, st, with_lanes};
+  if (with_lanes) {
+    scratch_hold(dev, st, SCRATCH_SHARD, true);
+    lock.lock();
+    if (!h->ev_st) HIP_TRY(hipEventCreateWithFlags(&h->ev_st, hipEventDisableTiming));
+    for (size_t j = 1; j < h->lanes.size(); j++) {
+      ShardLane& l = h->lanes[j];
+      HIP_TRY(dg.set(l.device));
+      if (int rc = sharded_lane_init(l)) return rc;
+      if (int rc = l.rows.grow(ShardBlock((uint32_t)l.shards.size(), slice, k, sc).bytes)) return rc;
+      // (the owner's block is the next call's: the lanes that read it have to be through with this one's queries)
+      if (l.device != dev && l.q_owner != j) HIP_TRY(hipStreamWaitEvent(h->lanes[l.q_owner].stream, l.ev_rows, 0));
+    }
   }
   for (uint32_t lo = 0; lo < n_q; lo += slice) {
     const uint32_t m = std::min(slice, n_q - lo);
     const ShardBlock B(W, m, k, sc);
-    char* dst = (char*)L0.rows.p;
+    // Two orders the lanes' streams do not give by themselves: no lane touches the inputs before `st` has copied them in, and no
+    // lane copies rows of this slice into the block before the merge of the last slice has read it.
+    if (with_lanes) { HIP_TRY(dg.set(dev)); HIP_TRY(hipEventRecord(h->ev_st, st)); }
     for (size_t j = 0; j < h->lanes.size(); j++) {
       ShardLane& l = h->lanes[j];
+      const bool own = with_lanes && j > 0;         // on the lane's stream, else on `st`
       HIP_TRY(dg.set(l.device));
-      const char* dq = (const char*)h->lanes[l.q_owner].q.p;
-      const uint64_t* d_offs = (const uint64_t*)dq + lo;
+      const char* lq = d_q;
+      const uint64_t* loffs = d_offs;
+      if (own) {
+        HIP_TRY(hipStreamWaitEvent(l.stream, h->ev_st, 0));
+        if (l.device != dev) {
+          ShardLane& owner = h->lanes[l.q_owner];
+          if (lo == 0 && l.q_owner == j) {
+            if (int rc = l.q.grow(off_bytes + q_bytes)) return rc;
+            HIP_TRY(hipMemcpyPeerAsync(l.q.p, l.device, d_offs, dev, off_bytes + q_bytes, l.stream));
+            HIP_TRY(hipEventRecord(l.ev_q, l.stream));
+          } else if (lo == 0) HIP_TRY(hipStreamWaitEvent(l.stream, owner.ev_q, 0));
+          loffs = (const uint64_t*)owner.q.p;
+          lq = (const char*)owner.q.p + off_bytes;
+        }
+      }
       const ShardBlock Bj((uint32_t)l.shards.size(), m, k, sc);
       for (size_t i = 0; i < l.shards.size(); i++) {
         const uint32_t s = l.shards[i];
-        if (j == 0) { if (int rc = sharded_search(h->shard[s], dq + off_bytes, d_offs, m, base, dst, B, s, l.stream)) return rc; continue; }
+        if (!own) { if (int rc = sharded_search(h->shard[s], lq, loffs + lo, m, base, dst, B, s, st)) return rc; continue; }
         char* src = (char*)l.rows.p;
-        if (int rc = sharded_search(h->shard[s], dq + off_bytes, d_offs, m, base, src, Bj, (uint32_t)i, l.stream)) return rc;
-        // this shard's rows to their place in lane 0's block, behind the search on this lane's stream
+        if (int rc = sharded_search(h->shard[s], lq, loffs + lo, m, base, src, Bj, (uint32_t)i, l.stream)) return rc;
+        // this shard's rows to their place in the call's block, behind the search on this lane's stream
         const size_t from = i * (size_t)m, to = (size_t)s * m;
         auto copy = [&](size_t d_off, size_t s_off, size_t bytes) -> hipError_t {
-          if (l.device == L0.device) return hipMemcpyAsync(dst + d_off, src + s_off, bytes, hipMemcpyDeviceToDevice, l.stream);
-          return hipMemcpyPeerAsync(dst + d_off, L0.device, src + s_off, l.device, bytes, l.stream);
+          if (l.device == dev) return hipMemcpyAsync(dst + d_off, src + s_off, bytes, hipMemcpyDeviceToDevice, l.stream);
+          return hipMemcpyPeerAsync(dst + d_off, dev, src + s_off, l.device, bytes, l.stream);
         };
         if (sc) HIP_TRY(copy(to * k * 8, from * k * 8, (size_t)m * k * 8));
         HIP_TRY(copy(B.ids + to * k * 4, Bj.ids + from * k * 4, (size_t)m * k * 4));
         HIP_TRY(copy(B.cnt + to * 4, Bj.cnt + from * 4, (size_t)m * 4));
       }
-      if (j) { HIP_TRY(hipEventRecord(l.ev_rows, l.stream)); }
+      if (own) HIP_TRY(hipEventRecord(l.ev_rows, l.stream));
     }
-    HIP_TRY(dg.set(L0.device));
-    for (size_t j = 1; j < h->lanes.size(); j++) HIP_TRY(hipStreamWaitEvent(L0.stream, h->lanes[j].ev_rows, 0));
-    char* o = (char*)h->out.p;
-    ShardMergeArgs a = sharded_merge_args(h, dst, B, m, k, sc);
-    a.out_ids = (uint32_t*)(o + out_ids); a.out_scores = sc ? (uint64_t*)o : nullptr; a.out_counts = (uint32_t*)(o + out_cnt);
-    if (int rc = enqueue_shard_merge(a, L0.stream)) return rc;
-    // (the slice's rows sit at the front of each region; the regions are laid out for `slice` queries)
-    const char* pin = (const char*)h->pin_out.p;
-    if (sc) HIP_TRY(hipMemcpyAsync(h->pin_out.p, o, (size_t)m * k * 8, hipMemcpyDeviceToHost, L0.stream));
-    HIP_TRY(hipMemcpyAsync((char*)h->pin_out.p + out_ids, o + out_ids, (size_t)m * k * 4, hipMemcpyDeviceToHost, L0.stream));
-    HIP_TRY(hipMemcpyAsync((char*)h->pin_out.p + out_cnt, o + out_cnt, (size_t)m * 4, hipMemcpyDeviceToHost, L0.stream));
-    HIP_TRY(hipStreamSynchronize(L0.stream));
-    if (sc) memcpy(scores + (size_t)lo * k, pin, (size_t)m * k * 8);
-    memcpy(ids + (size_t)lo * k, pin + out_ids, (size_t)m * k * 4);
-    memcpy(counts + lo, pin + out_cnt, (size_t)m * 4);
+    HIP_TRY(dg.set(dev));
+    if (with_lanes) for (size_t j = 1; j < h->lanes.size(); j++) HIP_TRY(hipStreamWaitEvent(st, h->lanes[j].ev_rows, 0));
+    ShardMergeArgs a = sharded_merge_args(W, h->doc_lo.data(), dst, B, m, k, sc);
+    a.out_ids = d_ids + (size_t)lo * k;
+    a.out_scores = sc ? d_scores + (size_t)lo * k : nullptr;
+    a.out_counts = d_counts + lo;
+    if (int rc = enqueue_shard_merge(a, st)) return rc;
   }
   drain.armed = false;
   return SG_OK;
+}
+
+// Host buffers: a synchronous host-buffer call (run_host_call) on the merge device around the enqueue step.
+int sharded_host_call(sg_sharded* h, const uint8_t* q, const uint64_t* offs, uint32_t n_q, const LaunchReq& base, uint32_t* ids, double* scores,
+                      uint32_t* counts) {
+  if (!offs || !ids || !counts || (!base.autocomplete && !scores)) { set_error("null argument"); return SG_E_INVALID; }
+  const HostBufs b = search_bufs(q, offs, n_q, base, ids, scores, counts, nullptr);
+  // (clear_rows is false: the merge kernel writes every slot of every row, flags included)
+  return run_host_call(h->device[0], b, false, [&](char* dev, const IoLayout& io, hipStream_t st) {
+    LaunchReq r = base;
+    r.no_long_queries = no_long_queries(offs, n_q);
+    return sharded_enqueue(h, dev + io.q, (const uint64_t*)(dev + io.offs), n_q, io.q_bytes, r, (uint32_t*)(dev + io.ids),
+                           b.scores ? (uint64_t*)dev : nullptr, (uint32_t*)(dev + io.cnt), st, h->lanes.size() > 1);
+  });
 }
 
 }  // namespace
@@ -505,7 +484,7 @@ int sg_sharded_suggest_batch(sg_sharded* h, const uint8_t* q, const uint64_t* of
                              uint32_t* ids, double* scores, uint32_t* counts) {
   SG_GUARD_BEGIN
   if (int rc = sharded_check_call(h, k, true, similarity, metric)) return rc;
-  return sharded_run_host(h, q, offs, n_q, search_req(metric, similarity, k, 0), ids, scores, counts);
+  return sharded_host_call(h, q, offs, n_q, search_req(metric, similarity, k, 0), ids, scores, counts);
   SG_GUARD_END(SG_RC)
 }
 
@@ -513,7 +492,7 @@ int sg_sharded_autocomplete_batch(sg_sharded* h, const uint8_t* q, const uint64_
                                   uint32_t* counts) {
   SG_GUARD_BEGIN
   if (int rc = sharded_check_call(h, limit, false, 0, 0)) return rc;
-  return sharded_run_host(h, q, offs, n_q, search_req(0, 0, limit, 1), ids, nullptr, counts);
+  return sharded_host_call(h, q, offs, n_q, search_req(0, 0, limit, 1), ids, nullptr, counts);
   SG_GUARD_END(SG_RC)
 }
 
@@ -521,7 +500,17 @@ int sg_sharded_suggest_batch_device(sg_sharded* h, const void* d_q, const void* 
                                     void* d_ids, void* d_scores, void* d_counts, void* stream) {
   SG_GUARD_BEGIN
   if (int rc = sharded_check_call(h, k, true, similarity, metric)) return rc;
-  return sharded_run_device(h, d_q, d_offs, n_q, search_req(metric, similarity, k, 0), d_ids, d_scores, d_counts, (hipStream_t)stream);
+  if (n_q == 0) return SG_OK;
+  if (!d_offs || !d_ids || !d_counts || !d_scores) { set_error("null argument"); return SG_E_INVALID; }
+  hipPointerAttribute_t at;
+  const bool there = h->one_device && hipPointerGetAttributes(&at, d_offs) == hipSuccess && at.type == hipMemoryTypeDevice && at.device == h->device[0];
+  if (!there) {
+    (void)hipGetLastError();
+    set_error("sg_sharded_*_device: every shard has to be resident on the device that owns the buffers");
+    return SG_E_UNSUPPORTED;
+  }
+  return sharded_enqueue(h, (const char*)d_q, (const uint64_t*)d_offs, n_q, 0, search_req(metric, similarity, k, 0), (uint32_t*)d_ids,
+                         (uint64_t*)d_scores, (uint32_t*)d_counts, (hipStream_t)stream, false);
   SG_GUARD_END(SG_RC)
 }
 
@@ -541,22 +530,19 @@ int sg_debug_shard_merge(int device, const uint32_t* ids, const double* scores, 
   if (n_shards == 0 || n_shards > SG_MAX_SHARDS || k == 0 || k > SG_MAX_TOPK || device < 0) { set_error("sg_debug_shard_merge: bad argument"); return SG_E_INVALID; }
   if (n_q == 0) return SG_OK;
   const ShardBlock B(n_shards, n_q, k, sc);
-  const size_t o_ids = sc ? (size_t)n_q * k * 8 : 0, o_cnt = o_ids + (size_t)n_q * k * 4, o_bytes = o_cnt + (size_t)n_q * 4;
+  const IoLayout io = io_layout(n_q, k, sc, false, 0);
   DeviceGuard dg;
   HIP_TRY(dg.set(device));
   DeviceBlock mem;
   char *di = nullptr, *d_o = nullptr;
   int rc;
-  if ((rc = mem.alloc(&di, block_capacity(B.bytes))) || (rc = mem.alloc(&d_o, block_capacity(o_bytes)))) return rc;   // (a search's GrowBlock sizes)
+  if ((rc = mem.alloc(&di, block_capacity(B.bytes))) || (rc = mem.alloc(&d_o, block_capacity(io.out_bytes)))) return rc;   // (a search's GrowBlock sizes)
   if (sc) HIP_TRY(hipMemcpy(di, scores, B.ids, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(di + B.ids, ids, B.cnt - B.ids, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(di + B.cnt, counts, B.bytes - B.cnt, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemset(d_o, 0xA5, o_bytes));          // (the kernel writes every slot of every row)
-  ShardMergeArgs a{};
-  a.ids = (const uint32_t*)(di + B.ids); a.scores = sc ? (const uint64_t*)di : nullptr; a.counts = (const uint32_t*)(di + B.cnt);
-  a.out_ids = (uint32_t*)(d_o + o_ids); a.out_scores = sc ? (uint64_t*)d_o : nullptr; a.out_counts = (uint32_t*)(d_o + o_cnt);
-  a.W = n_shards; a.n_q = n_q; a.k = k;
-  for (uint32_t s = 0; s < n_shards; s++) a.doc_lo[s] = doc_lo[s];
+  HIP_TRY(hipMemset(d_o, 0xA5, io.out_bytes));          // (the kernel writes every slot of every row)
+  ShardMergeArgs a = sharded_merge_args(n_shards, doc_lo, di, B, n_q, k, sc);
+  a.out_ids = (uint32_t*)(d_o + io.ids); a.out_scores = sc ? (uint64_t*)d_o : nullptr; a.out_counts = (uint32_t*)(d_o + io.cnt);
   hipEvent_t ev[2] = {nullptr, nullptr};
   struct Events { hipEvent_t* e; ~Events() { for (int i = 0; i < 2; i++) if (e[i]) (void)hipEventDestroy(e[i]); } } events_{ev};
   HIP_TRY(hipEventCreate(&ev[0])); HIP_TRY(hipEventCreate(&ev[1]));
@@ -567,9 +553,9 @@ int sg_debug_shard_merge(int device, const uint32_t* ids, const double* scores, 
   float ms = 0;
   HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
   t_shard_merge_ms = ms;
-  if (sc) HIP_TRY(hipMemcpy(out_scores, d_o, o_ids, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(out_ids, d_o + o_ids, o_cnt - o_ids, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(out_counts, d_o + o_cnt, o_bytes - o_cnt, hipMemcpyDeviceToHost));
+  if (sc) HIP_TRY(hipMemcpy(out_scores, d_o, io.sc_bytes, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(out_ids, d_o + io.ids, io.id_bytes, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(out_counts, d_o + io.cnt, io.cnt_bytes, hipMemcpyDeviceToHost));
   return SG_OK;
   SG_GUARD_END(SG_RC)
 }

@@ -121,28 +121,31 @@ def test_sharded_index_equals_the_unsharded(uneven, W, build):
 
 
 def test_slices_give_the_unsliced_rows(uneven):
-    """257 queries in slices of 128, 128 and 1: the budget holds 128 queries' rows of three shards"""
+    """257 queries in slices of 128, 128 and 1: the budget holds 128 queries' rows of every shard.  Three shards in one lane;
+    four in two lanes, where a lane's copy of slice i + 1 into the merge's block has to wait for the merge of slice i"""
     from suggest_amd import ShardedIndex, _lib
     u = uneven
     qo = u["qo"][:258]
     qb = u["qb"][:int(qo[-1])]
-    sh = ShardedIndex(blob=u["blob"], offs=u["offs"], description=u["desc"], n_shards=3)
     k = 10
-    whole = sh.suggest_batch(blob=qb, offs=qo, metric="cosine", similarity=0.4, k=k)
-    whole_ac = sh.autocomplete_batch(blob=qb, offs=qo, limit=k)
-    try:
-        _lib.check(_lib.lib().sg_debug_shard_slice_bytes(128 * 3 * (k * 12 + 4)))
-        sliced = sh.suggest_batch(blob=qb, offs=qo, metric="cosine", similarity=0.4, k=k)
-        sliced_dev = _device_call(sh, qb, qo, "cosine", 0.4, k)
-        _lib.check(_lib.lib().sg_debug_shard_slice_bytes(128 * 3 * (k * 4 + 4)))
-        sliced_ac = sh.autocomplete_batch(blob=qb, offs=qo, limit=k)
-    finally:
-        _lib.check(_lib.lib().sg_debug_shard_slice_bytes(0))
-    _same_rows(sliced, whole, "host-buffer")
-    _same_rows(sliced_dev, whole, "device-resident")
-    assert np.array_equal(sliced_ac[0], whole_ac[0]) and np.array_equal(sliced_ac[1], whole_ac[1])
-    assert_same(whole, tuple(x[:257] for x in u["want"][("cosine", 0.4, 10)]))
-    sh.close()
+    for W, devices in ((3, (0,)), (4, (0, 0))):
+        sh = ShardedIndex(blob=u["blob"], offs=u["offs"], description=u["desc"], n_shards=W, devices=devices)
+        whole = sh.suggest_batch(blob=qb, offs=qo, metric="cosine", similarity=0.4, k=k)
+        whole_ac = sh.autocomplete_batch(blob=qb, offs=qo, limit=k)
+        try:
+            _lib.check(_lib.lib().sg_debug_shard_slice_bytes(128 * W * (k * 12 + 4)))
+            sliced = sh.suggest_batch(blob=qb, offs=qo, metric="cosine", similarity=0.4, k=k)
+            sliced_dev = _device_call(sh, qb, qo, "cosine", 0.4, k)
+            _lib.check(_lib.lib().sg_debug_shard_slice_bytes(128 * W * (k * 4 + 4)))
+            sliced_ac = sh.autocomplete_batch(blob=qb, offs=qo, limit=k)
+        finally:
+            _lib.check(_lib.lib().sg_debug_shard_slice_bytes(0))
+        _same_rows(sliced, whole, (W, "host-buffer"))
+        _same_rows(sliced_dev, whole, (W, "device-resident"))
+        assert np.array_equal(sliced_ac[0], whole_ac[0]) and np.array_equal(sliced_ac[1], whole_ac[1]), W
+        assert_same(whole, tuple(x[:257] for x in u["want"][("cosine", 0.4, 10)]))
+        assert np.array_equal(whole_ac[1], u["want_ac"][1][:257]), W
+        sh.close()
 
 
 def test_devices_0_0_takes_the_path_for_rows_from_another_device(uneven):
@@ -156,6 +159,103 @@ def test_devices_0_0_takes_the_path_for_rows_from_another_device(uneven):
     assert np.array_equal(cnt, u["want_ac"][1])
     valid = np.arange(10)[None, :] < np.minimum(cnt, 10)[:, None]
     assert np.array_equal(ids[valid], u["want_ac"][0][valid])
+    sh.close()
+
+
+def _handles(u):
+    """one lane and two lanes over the same dictionary"""
+    from suggest_amd import ShardedIndex
+    return [ShardedIndex(blob=u["blob"], offs=u["offs"], description=u["desc"], n_shards=W, devices=d) for W, d in ((3, (0,)), (4, (0, 0)))]
+
+
+def test_offsets_that_do_not_start_at_zero(uneven):
+    """queries 100 .. 229 as a slice of the whole blob: the offsets are rebased in staging"""
+    u = uneven
+    offs = u["qo"][100:231]
+    assert offs[0] > 0
+    for sh in _handles(u):
+        for (m, a, k), want in u["want"].items():
+            whole = sh.suggest_batch(blob=u["qb"], offs=u["qo"], metric=m, similarity=a, k=k)
+            _same_rows(sh.suggest_batch(blob=u["qb"], offs=offs, metric=m, similarity=a, k=k), tuple(x[100:230] for x in whole), (m, a, k))
+        whole = sh.autocomplete_batch(blob=u["qb"], offs=u["qo"], limit=10)
+        ids, cnt = sh.autocomplete_batch(blob=u["qb"], offs=offs, limit=10)
+        assert np.array_equal(ids, whole[0][100:230]) and np.array_equal(cnt, whole[1][100:230])
+        sh.close()
+
+
+def test_threads_on_one_handle(uneven):
+    """two threads on a handle with two lanes, which share the lanes' streams and rows and nothing else; a thread on a handle
+    with one lane next to a device-resident call on it, which share nothing"""
+    import threading
+    u = uneven
+    one, two = _handles(u)
+    got, errors = {}, []
+
+    def host_calls(sh, name):
+        try:
+            got[name] = [(key, sh.suggest_batch(blob=u["qb"], offs=u["qo"], metric=key[0], similarity=key[1], k=key[2]))
+                         for _ in range(2) for key in u["want"]]
+        except Exception as e:      # (a thread's exception is the test's)
+            errors.append((name, e))
+
+    threads = [threading.Thread(target=host_calls, args=(two, i)) for i in range(2)]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join()
+    t = threading.Thread(target=host_calls, args=(one, "one lane"))
+    t.start()
+    dev = [(key, _device_call(one, u["qb"], u["qo"], *key)) for _ in range(2) for key in u["want"]]
+    t.join()
+    assert not errors, errors
+    assert sorted(got, key=str) == [0, 1, "one lane"] and all(len(v) == 4 for v in got.values())
+    for name, rows in list(got.items()) + [("device-resident", dev)]:
+        for key, r in rows:
+            assert_same(r, u["want"][key], (name, key))
+    one.close()
+    two.close()
+
+
+def test_poisoned_scratch_leaves_the_rows_as_they_are(uneven):
+    """the merge kernel writes every slot of every row, so a host-buffer call does not clear them first: with the scratch and
+    the shards' rows poisoned the merged rows are the same, zero past each count"""
+    from suggest_amd import _lib
+    u = uneven
+    for sh in _handles(u):
+        for (m, a, k), want in u["want"].items():
+            plain = sh.suggest_batch(blob=u["qb"], offs=u["qo"], metric=m, similarity=a, k=k)
+            for family in (1, 2):
+                with _lib.poisoned(family):
+                    ids, sc, cnt = sh.suggest_batch(blob=u["qb"], offs=u["qo"], metric=m, similarity=a, k=k)
+                _same_rows((ids, sc, cnt), plain, (m, a, k, family))
+                past = np.arange(k)[None, :] >= np.minimum(cnt, k)[:, None]
+                assert past.any() and not ids[past].any() and not sc.view(np.uint64)[past].any()
+        plain = sh.autocomplete_batch(blob=u["qb"], offs=u["qo"], limit=10)
+        for family in (1, 2):
+            with _lib.poisoned(family):
+                ids, cnt = sh.autocomplete_batch(blob=u["qb"], offs=u["qo"], limit=10)
+            assert np.array_equal(ids, plain[0]) and np.array_equal(cnt, plain[1])
+            assert not ids[np.arange(10)[None, :] >= np.minimum(cnt, 10)[:, None]].any()
+        sh.close()
+
+
+def test_merged_rows_above_64_mib_are_copied_straight_out(uneven):
+    """6 000 queries at k = 1 000: 72 MB of merged rows, past what a host-buffer call stages, from a [shard][query][k] block of
+    216 MB — one slice.  Cosine >= 0.1: the threshold at which this dictionary gives rows of more than 64 entries (up to 177)"""
+    from suggest_amd import ShardedIndex
+    u = uneven
+    n, k = 6000, 1000
+    reps = -(-n // 512)
+    lens = np.tile(np.diff(u["qo"].astype(np.int64)), reps)[:n]
+    qo = np.concatenate([[0], np.cumsum(lens)]).astype(np.uint64)
+    qb = np.tile(u["qb"][:int(u["qo"][-1])], reps)[:int(qo[-1])]
+    assert n * (12 * k + 4) > 64 << 20 and 3 * n * (12 * k + 4) <= 256 << 20
+    want = u["full"].suggest_batch(blob=qb, offs=qo, metric="cosine", similarity=0.1, k=k)
+    assert (want[2][want[2] < shard_ref.FLAG_MIN] > 64).any()        # rows that long come from the top-k kept in HBM
+    sh = ShardedIndex(blob=u["blob"], offs=u["offs"], description=u["desc"], n_shards=3)
+    got = sh.suggest_batch(blob=qb, offs=qo, metric="cosine", similarity=0.1, k=k)
+    assert_same(got, want)
+    assert not got[0][np.arange(k)[None, :] >= np.minimum(got[2], k)[:, None]].any()
     sh.close()
 
 
@@ -269,7 +369,7 @@ def test_device_call_needs_every_shard_on_the_buffers_device():
     """One GPU visible: the check is exercised by its arguments alone — buffers that are not device memory of the shards' GPU;
     with a second GPU, buffers that live there"""
     import torch
-    from suggest_amd import IndexDescription, ShardedIndex, _lib, synth
+    from suggest_amd import IndexDescription, NGramIndex, ShardedIndex, _lib, synth
     sh = ShardedIndex([b"alpha", b"beta", b"gamma", b"delta"], description=IndexDescription(**synth.DESCRIPTION), n_shards=2)
     UNSUPPORTED, INVALID = -2, -1
     qb, qo = oracle.pack_strings([b"alpha"])
@@ -299,3 +399,6 @@ def test_device_call_needs_every_shard_on_the_buffers_device():
             two.suggest_batch_device(t[0].data_ptr(), t[1].data_ptr(), 1, "jaccard", 0.5, 3, t[2].data_ptr(), t[3].data_ptr(), t[4].data_ptr())
         assert e.value.code == UNSUPPORTED
         assert_same(two.suggest_batch([b"alpha", b"gamm"], metric="jaccard", similarity=0.3, k=3), sh.suggest_batch([b"alpha", b"gamm"], metric="jaccard", similarity=0.3, k=3))
+        full = NGramIndex([b"alpha", b"beta", b"gamma", b"delta"], IndexDescription(**synth.DESCRIPTION))
+        assert_same(two.suggest_batch([b"alpha", b"gamm", b"delt"], metric="jaccard", similarity=0.3, k=3),
+                    full.suggest_batch([b"alpha", b"gamm", b"delt"], metric="jaccard", similarity=0.3, k=3))      # against the unsharded index

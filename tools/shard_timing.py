@@ -9,9 +9,16 @@ W = 1, 2, 4, 8 shards, at k = 10 and 100.  Per (W, k), device-resident buffers, 
   - unsharded_ms      sg_suggest_batch_device on the unsharded index
   - torch_merge_ms    the existing route on the same rows on the GPU: distributed.merge_topk (two torch.sort over [n, W * k])
 and the ratios merge_kernel / searches_sum, torch_merge / merge_kernel, sharded / unsharded.  The merged rows of the kernel, of
-merge_topk and of the sharded call are compared.  Writes profiles/shard_merge_timing.json and prints it.  GPU box only."""
+merge_topk and of the sharded call are compared.
+  - host_ms           sg_sharded_suggest_batch, host buffers: a host clock around the call, which returns synchronised; one
+                      warm-up, the median of `--reps` runs (host_runs_ms: each of them), on a handle with one lane (devices
+                      (0,), key "1") and on one with two (devices (0, 0), key "2").  host_rows: a SHA-256 of the rows, to hold
+                      two builds of the library against each other; host_rows_equal_sharded_call: against the device-resident call's.
+--host-only measures the host-buffer call alone (an A/B of two builds under SG_LIB_NAME, a process each).
+Writes profiles/shard_merge_timing.json and prints it.  GPU box only."""
 import argparse
 import ctypes as C
+import hashlib
 import json
 import os
 import statistics
@@ -26,6 +33,7 @@ import torch
 
 from suggest_amd import IndexDescription, NGramIndex, ShardedIndex, _lib, synth
 from suggest_amd.distributed import merge_topk, shard_bounds
+from suggest_amd.metric import resolve
 from suggest_amd.sharded import shard_merge
 
 ap = argparse.ArgumentParser()
@@ -37,6 +45,7 @@ ap.add_argument("--metric", default="jaccard")
 ap.add_argument("--similarity", type=float, default=0.5)
 ap.add_argument("--reps", type=int, default=5)
 ap.add_argument("--device", type=int, default=0)
+ap.add_argument("--host-only", action="store_true")
 ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "shard_merge_timing.json"))
 args = ap.parse_args()
 
@@ -62,6 +71,51 @@ def timed(fn, reps=args.reps):
     return statistics.median(out)
 
 
+def timed_host(fn, reps=args.reps):
+    """milliseconds of a host clock around fn(), which returns synchronised, after one warm-up: (median, every run)"""
+    fn()
+    out = []
+    for _ in range(reps):
+        t = time.perf_counter()
+        fn()
+        out.append((time.perf_counter() - t) * 1e3)
+    return statistics.median(out), out
+
+
+def host_handles(W):
+    """W shards built on the GPU behind a handle with one lane and behind one with two"""
+    return {str(n): ShardedIndex(blob=blob, offs=offs, description=desc, n_shards=W, devices=(args.device,) * n, build="device") for n in (1, 2)}
+
+
+def host_call(sh, k):
+    """-> (median ms, runs, rows) of sg_sharded_suggest_batch"""
+    ids, sc, cnt = np.empty((n_q, k), dtype=np.uint32), np.empty((n_q, k), dtype=np.float64), np.empty(n_q, dtype=np.uint32)
+    for x in (ids, sc, cnt):
+        x.fill(0)           # (the pages are there before the first call)
+    code = resolve(args.metric).code
+    with sh._use() as h:
+        ms, runs = timed_host(lambda: _lib.check(_lib.lib().sg_sharded_suggest_batch(h, qb.ctypes.data, qo.ctypes.data, n_q, code, args.similarity, k,
+                                                                                     ids.ctypes.data, sc.ctypes.data, cnt.ctypes.data)))
+    return ms, runs, (ids, sc, cnt)
+
+
+def write_record():
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(record, f, indent=1)
+        f.write("\n")
+
+
+def host_cells(handles, k):
+    row, rows = {"host_ms": {}, "host_runs_ms": {}, "host_rows": {}}, None
+    for key, sh in handles.items():
+        ms, runs, rows = host_call(sh, k)
+        row["host_ms"][key] = round(ms, 4)
+        row["host_runs_ms"][key] = [round(x, 4) for x in runs]
+        row["host_rows"][key] = hashlib.sha256(b"".join(x.tobytes() for x in rows)).hexdigest()
+    return row, rows
+
+
 desc = IndexDescription(**synth.DESCRIPTION)
 t0 = time.perf_counter()
 blob, offs = synth.make_dict(args.dict_size, seed=1)
@@ -83,6 +137,18 @@ def search(ix, out, k):
                             out[2].data_ptr(), stream.cuda_stream)
 
 
+if args.host_only:
+    for W in args.shards:
+        handles = host_handles(W)
+        for k in args.topk:
+            row = dict({"shards": W, "k": k}, **host_cells(handles, k)[0])
+            record["rows"].append(row)
+            print(json.dumps(row), flush=True)
+        for x in handles.values():
+            x.close()
+    write_record()
+    sys.exit(0)
+
 full = NGramIndex(blob=blob, offs=offs, description=desc, device=args.device, build="device")
 S = full.stats()["n_segments"]
 unsharded = {}
@@ -98,6 +164,7 @@ for W in args.shards:
                                  device=args.device, build="device", min_segments=S))
         los.append(lo)
     sh = ShardedIndex.adopt(shards, los)
+    handles = host_handles(W)
     for k in args.topk:
         un_ms, un_rows = unsharded[k]
         per = [rows_for(k) for _ in range(W)]
@@ -136,15 +203,16 @@ for W in args.shards:
                                                     and np.array_equal(t_sc.view(np.uint64)[valid], s_sc.view(np.uint64)[valid])),
                "sharded_rows_equal_unsharded": bool(np.array_equal(u_cnt, s_cnt) and np.array_equal(u_ids[valid], s_ids[valid])
                                                     and np.array_equal(u_sc.view(np.uint64)[valid], s_sc.view(np.uint64)[valid]))}
+        host, h_rows = host_cells(handles, k)
+        row.update(host)
+        row["host_rows_equal_sharded_call"] = bool(np.array_equal(h_rows[0], s_ids) and np.array_equal(h_rows[1].view(np.uint64), s_sc.view(np.uint64))
+                                                   and np.array_equal(h_rows[2], s_cnt))
         record["rows"].append(row)
         print(json.dumps(row), flush=True)
         del ids, sc, cnt, g_ids, g_cnt, t_rows, per, out
         torch.cuda.empty_cache()
     sh.close()
-    for x in shards:
+    for x in shards + list(handles.values()):
         x.close()
 
-os.makedirs(os.path.dirname(args.out), exist_ok=True)
-with open(args.out, "w") as f:
-    json.dump(record, f, indent=1)
-    f.write("\n")
+write_record()
