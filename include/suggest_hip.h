@@ -79,6 +79,15 @@ int sg_index_build_device(const uint8_t* utf8, const uint64_t* offs, uint32_t n_
  * sg_sharded_build builds, uploads and searches all of them behind one handle; sg_sharded_adopt takes shards built here. */
 int sg_index_build_ex(const uint8_t* utf8, const uint64_t* offs, uint32_t n_docs, const sg_desc* desc, uint32_t min_segments,
                       int device, sg_index** out);
+/* Test hooks like the other sg_debug_* entries (bindings need not mirror them).  sg_debug_index_build_table_bits, process-wide
+ * (like sg_debug_lm_build_hash_bits): the device builder starts its term table at exactly 2^bits slots — bits 4 .. 20 — instead of
+ * 2^20 or a sixteenth of the dictionary's rune capacity, whichever is larger; 0 restores that default.  Either way the table grows
+ * fourfold, with the tokenise pass repeated, once more than half of it is taken.  sg_debug_index_build_report: the calling thread's last
+ * device build (sg_index_build_device, sg_index_build_ex with device >= 0; all zero if it tokenised nothing), failed ones
+ * included — out = {tokenise passes; log2 of the slots of the final table; terms interned by the last pass; documents the long
+ * tokeniser took in the last pass (those above 128 n-grams)}.  No reference counterpart. */
+int sg_debug_index_build_table_bits(uint32_t bits);
+int sg_debug_index_build_report(uint32_t out[4]);
 
 /* NewFSBuilder + Reader.Read (pkg/suggest/ngram_index_builder.go:44-83, pkg/index/index_reader.go:29-120): loads an
  * index the reference itself built — <name>.hd (gob header) and <name>.dl (VB / skip-VB / roaring posting lists,

@@ -34,6 +34,7 @@ EXPORTS = [
     "sg_lm_store_binary_ex", "sg_lm_store_google", "sg_debug_lm_store_slice_bytes", "sg_debug_lm_store_times",
     "sg_sharded_build", "sg_sharded_adopt", "sg_sharded_retain", "sg_sharded_release", "sg_sharded_shards", "sg_sharded_suggest_batch",
     "sg_sharded_suggest_batch_device", "sg_sharded_autocomplete_batch", "sg_debug_shard_slice_bytes", "sg_debug_shard_merge", "sg_debug_shard_merge_time",
+    "sg_debug_index_build_table_bits", "sg_debug_index_build_report",
 ]
 SG_MAX_SHARDS = 64
 SG_LM_STORE_MPH = 1
@@ -71,6 +72,8 @@ def lib():
     if hasattr(L, "sg_index_build"): L.sg_index_build.argtypes = [vp, vp, u32, C.POINTER(SgDesc), C.POINTER(vp)]
     if hasattr(L, "sg_index_build_device"): L.sg_index_build_device.argtypes = [vp, vp, u32, C.POINTER(SgDesc), i32, C.POINTER(vp)]
     if hasattr(L, "sg_index_build_ex"): L.sg_index_build_ex.argtypes = [vp, vp, u32, C.POINTER(SgDesc), u32, i32, C.POINTER(vp)]
+    if hasattr(L, "sg_debug_index_build_table_bits"): L.sg_debug_index_build_table_bits.argtypes = [u32]
+    if hasattr(L, "sg_debug_index_build_report"): L.sg_debug_index_build_report.argtypes = [vp]
     if hasattr(L, "sg_index_digest"): L.sg_index_digest.argtypes = [vp, vp]
     if hasattr(L, "sg_index_load_reference"): L.sg_index_load_reference.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(SgDesc), C.POINTER(vp)]
     if hasattr(L, "sg_index_load_reference_ex"): L.sg_index_load_reference_ex.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(SgDesc), i32, C.POINTER(vp)]

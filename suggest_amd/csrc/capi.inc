@@ -1135,6 +1135,18 @@ int sg_index_build_ex(const uint8_t* utf8, const uint64_t* offs, uint32_t n_docs
   SG_GUARD_END(SG_RC)
 }
 
+int sg_debug_index_build_table_bits(uint32_t bits) {
+  if (bits && (bits < 4u || bits > 20u)) { set_error("table bits: 0 (the default, 20) or 4 .. 20"); return SG_E_INVALID; }
+  g_index_build_table_bits.store(bits, std::memory_order_relaxed);
+  return SG_OK;
+}
+
+int sg_debug_index_build_report(uint32_t out[4]) {
+  if (!out) { set_error("null argument"); return SG_E_INVALID; }
+  for (int i = 0; i < 4; i++) out[i] = t_index_build_report[i];
+  return SG_OK;
+}
+
 int sg_index_digest(const sg_index* ix, uint64_t out[4]) {
   if (!ix || !out) { set_error("null argument"); return SG_E_INVALID; }
   const HostIndex& h = ix->host;

@@ -7,7 +7,7 @@
 // host's), so everything downstream (upload, search, introspection) is unchanged.
 //
 //   K1 build_tokenize    one wavefront per document: d_tokenize -> keys to HBM, keys interned (CAS on the 64-bit key),
-//                        first appearance (doc << 8 | position) kept with atomicMin, cardinality -> doc_cnt
+//                        first appearance (doc << 20 | min(position, 0xFFFFF)) kept with atomicMin, cardinality -> doc_cnt
 //   K2 build_collect     occupied slots -> (stamp, key) pairs; hipcub radix sort by stamp = term numbering;
 //      build_assign      term id written back into the slot
 //   K3 build_emit        one wavefront per document: keys -> term ids, repeated terms of a document folded (side list
@@ -216,8 +216,14 @@ __global__ void build_seg_off(const uint32_t* chunk_off, uint32_t n_terms, uint3
 
 namespace {
 
+std::atomic<uint32_t> g_index_build_table_bits{0};      // sg_debug_index_build_table_bits (0: 20)
+thread_local uint32_t t_index_build_report[4];          // the calling thread's last device build: tokenise passes, log2 of the final
+                                                        // table, terms interned, documents the long tokeniser took (sg_debug_index_build_report)
+
 int build_on_device(sg_index* ix, const uint8_t* utf8, const uint64_t* offs, uint32_t n_docs, int device) {
   HostIndex& h = ix->host;
+  uint32_t* const report = t_index_build_report;
+  report[0] = report[1] = report[2] = report[3] = 0;
   DeviceGuard dg;
   HIP_TRY(dg.set(device));
   h.n_docs = n_docs;
@@ -260,9 +266,13 @@ int build_on_device(sg_index* ix, const uint8_t* utf8, const uint64_t* offs, uin
   // K1 (the table is grown and the pass repeated if the dictionary has more distinct terms than guessed)
   uint32_t stats[8];
   uint32_t log2_table = 20;
-  while ((1ull << log2_table) < cap_total / 16 && log2_table < 26) log2_table++;
+  // (the test hook names the first table outright: under the capacity rule no dictionary could make it grow more than three times)
+  if (const uint32_t bits = g_index_build_table_bits.load(std::memory_order_relaxed)) log2_table = bits;
+  else while ((1ull << log2_table) < cap_total / 16 && log2_table < 26) log2_table++;
   for (;; log2_table += 2) {
     if (log2_table > 28) { set_error("too many distinct terms for the device builder"); return SG_E_UNSUPPORTED; }
+    report[0]++;
+    report[1] = log2_table;
     const size_t n_slots = (size_t)1 << log2_table;
     if ((rc = mem.alloc(&b.table, n_slots))) return rc;
     b.table_mask = (uint32_t)(n_slots - 1);
@@ -279,6 +289,8 @@ int build_on_device(sg_index* ix, const uint8_t* utf8, const uint64_t* offs, uin
       HIP_TRY(hipGetLastError());
       HIP_TRY(hipMemcpy(stats, d_stats, 32, hipMemcpyDeviceToHost));
     }
+    report[2] = stats[2];
+    report[3] = stats[3] ? 0u : stats[1];
     if (!stats[3]) break;
   }
   if (stats[6]) { set_error("a document exceeds 65536 bytes: beyond the device builder, use sg_index_build"); return SG_E_UNSUPPORTED; }

@@ -138,6 +138,26 @@ def knobs(index=None):
     return rows
 
 
+@contextlib.contextmanager
+def build_table_bits(bits):
+    """Test hook (sg_debug_index_build_table_bits): `with build_table_bits(4):` device builds start their term table at 2^bits
+    slots (4 .. 20) instead of 2^20, so that small dictionaries grow it and repeat the tokenise pass.  Process-wide: the default
+    again on leaving."""
+    _lib.check(_lib.lib().sg_debug_index_build_table_bits(int(bits)))
+    try:
+        yield
+    finally:
+        _lib.check(_lib.lib().sg_debug_index_build_table_bits(0))
+
+
+def build_report():
+    """Test hook (sg_debug_index_build_report): the calling thread's last device build -> {passes, log2_table, terms, long_docs}:
+    tokenise passes, log2 of the final term table's slots, terms interned, documents the long tokeniser took."""
+    out = (C.c_uint32 * 4)()
+    _lib.check(_lib.lib().sg_debug_index_build_report(out))
+    return dict(zip(("passes", "log2_table", "terms", "long_docs"), (int(x) for x in out)))
+
+
 class NGramIndex:
     def __init__(self, docs=None, description=None, blob=None, offs=None, device=0, upload=True, _handle=None, build="host", min_segments=0):
         """build="host": sg_index_build (CPU tokenise + CSR); build="device": sg_index_build_device (same arrays, built on the

@@ -24,6 +24,21 @@ def test_library_exports_every_declared_symbol():
     assert declared == set(_lib.EXPORTS), declared ^ set(_lib.EXPORTS)
     for name in declared:
         assert hasattr(L, name), name
+    assert {"sg_debug_index_build_table_bits", "sg_debug_index_build_report"} <= declared
+    # the builder's table hook takes 0 (the default) and 4 .. 20
+    import ctypes as C
+    try:
+        assert [L.sg_debug_index_build_table_bits(b) for b in (3, 4, 20, 21, 0)] == [-1, 0, 0, -1, 0]
+    finally:
+        L.sg_debug_index_build_table_bits(0)
+    assert L.sg_debug_index_build_report((C.c_uint32 * 4)()) == 0 and L.sg_debug_index_build_report(None) == -1
+    from suggest_amd.index import build_report, build_table_bits
+    with build_table_bits(4):
+        pass
+    with pytest.raises(_lib.SuggestHipError):
+        with build_table_bits(21):
+            pass
+    assert list(build_report()) == ["passes", "log2_table", "terms", "long_docs"]
 
 
 def test_product_does_not_touch_the_oracle():
