@@ -867,6 +867,93 @@ func (i *Index) SuggestBatch(queries []string, similarity float64, m metric.Metr
 	return
 }
 
+// ManyConfig is one request of SuggestMany: what suggest.SearchConfig carries per call (pkg/suggest/search.go:18-35), with a
+// metric of pkg/metric (a Metric implementation of the caller's has no device twin: use SuggestBatch).
+type ManyConfig struct {
+	Query      string
+	Similarity float64
+	Metric     metric.Metric
+	TopK       int
+}
+
+// SuggestMany answers requests that differ in metric, similarity and topK with ONE mixed call (sg_suggest_batch_mixed): equal
+// (metric, similarity, topK) share an entry of the config table, the device groups the queries by entry and runs every group as
+// its ordinary launch.  cands[q] and status[q] are SuggestBatch's.  More than C.SG_MAX_MIXED_CONFIGS distinct configs: an error.
+func (i *Index) SuggestMany(reqs []ManyConfig) ([][]suggest.Candidate, []uint32, error) {
+	n := len(reqs)
+	if n == 0 {
+		return nil, nil, nil
+	}
+	type key struct {
+		code C.int
+		sim  float64
+		k    int
+	}
+	number := map[key]uint32{}
+	var table []C.sg_search_config
+	configOf := make([]C.uint32_t, n)
+	var blob []byte
+	offs := []C.uint64_t{0}
+	rows := 0
+	for q, r := range reqs {
+		code, known := metricCode(r.Metric)
+		if !known {
+			return nil, nil, errors.New("SuggestMany: a metric without a device twin (use SuggestBatch)")
+		}
+		kk := key{code, r.Similarity, r.TopK}
+		g, ok := number[kk]
+		if !ok {
+			if len(table) == int(C.SG_MAX_MIXED_CONFIGS) {
+				return nil, nil, errors.New("SuggestMany: more distinct configs than one call takes")
+			}
+			g = uint32(len(table))
+			number[kk] = g
+			table = append(table, C.sg_search_config{metric: C.int32_t(code), autocomplete: 0, similarity: C.double(r.Similarity), k: C.uint32_t(r.TopK), first_doc: 0})
+		}
+		configOf[q] = C.uint32_t(g)
+		blob = append(blob, r.Query...)
+		offs = append(offs, C.uint64_t(len(blob)))
+		if r.TopK > 0 {
+			rows += r.TopK
+		}
+	}
+	ids := make([]C.uint32_t, rows+1)
+	scores := make([]C.double, rows+1)
+	counts := make([]C.uint32_t, n)
+	rowOffs := make([]C.uint64_t, n+1)
+	var bp *C.uint8_t
+	if len(blob) > 0 {
+		bp = (*C.uint8_t)(unsafe.Pointer(&blob[0]))
+	}
+	e := i.e
+	if err := e.retain(); err != nil {
+		return nil, nil, err
+	}
+	err := ccall(func() C.int {
+		return C.sg_suggest_batch_mixed(e.h, bp, &offs[0], C.uint32_t(n), &table[0], C.uint32_t(len(table)), &configOf[0], C.uint64_t(rows), &ids[0], &scores[0], &counts[0], &rowOffs[0])
+	})
+	e.release()
+	runtime.KeepAlive(i)
+	if err != nil {
+		return nil, nil, err
+	}
+	out := make([][]suggest.Candidate, n)
+	status := make([]uint32, n)
+	for q := 0; q < n; q++ {
+		c := uint32(counts[q])
+		if c >= C.SG_COUNT_LM_ERROR { // an SG_COUNT_* flag: no row
+			status[q] = c
+			continue
+		}
+		at := int(rowOffs[q])
+		out[q] = make([]suggest.Candidate, c)
+		for j := 0; j < int(c); j++ {
+			out[q][j] = suggest.Candidate{Key: uint32(ids[at+j]), Score: float64(scores[at+j])}
+		}
+	}
+	return out, status, nil
+}
+
 // Autocomplete implements suggest.Autocomplete (pkg/suggest/autocomplete.go:14-17) for ANY collector manager: the matching
 // documents, ascending docID, are replayed through the caller's own collector — first-k (collector.go:48-115) stops after
 // its limit, pkg/spellchecker's lmCollectorManager (spellchecker/collector.go:61-79) ranks every one of them with its

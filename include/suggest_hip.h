@@ -538,6 +538,61 @@ int sg_debug_replica_devices(sg_index* index, uint32_t replica, int32_t out[8]);
  * copied (SG_E_INVALID if cap_bytes is smaller).  SG_E_INVALID: not uploaded, no such replica, unknown array.  Reads only. */
 int sg_debug_index_array(sg_index* index, uint32_t replica, uint32_t which, void* out, uint64_t cap_bytes, uint64_t* out_bytes);
 
+/* A batch whose queries differ in metric, similarity and k.  The reference takes a SearchConfig per call
+ * (pkg/suggest/service.go:105) and its HTTP handler reads metric | similarity | topK per request
+ * (internal/suggest/api/suggest_handler.go:79-101); here the caller passes a table of DISTINCT configs and, per query, an index
+ * into it.  The device groups the queries by config (a stable permutation: within a group they keep the caller's order), gathers
+ * each group's queries into one contiguous blob, runs every non-empty group as the ordinary launch of its config and scatters the
+ * groups' rows back in caller order.  A row is bit for bit the row the plain call with that config gives the query.
+ *
+ * Output, ragged: row i starts at out_row_offs[i] = k_0 + ... + k_(i-1) (k_j: the k of query j's config) and has k_i slots of
+ * out_ids and out_scores; out_row_offs has n_q + 1 entries.  Slots past a row's count are zero; an autocomplete row's score slots
+ * are zero.  out_counts[i] is the plain call's, SG_COUNT_* values included.  rows_cap: the slots out_ids and out_scores have room
+ * for; a batch that needs more is refused.
+ *
+ * 1 <= n_configs <= SG_MAX_MIXED_CONFIGS.  Every entry is checked as the plain call checks its arguments; a config no query names
+ * is legal (an empty group, no launch), two equal entries are two groups.  config_of[i] >= n_configs is refused (invalid argument)
+ * on either route with no access outside any array — the device route finds it on the device.  n_q == 0 succeeds.  Not offered:
+ * docID-ordered configs, tabulated metrics, Predict, sharded handles, tickets, several replicas.
+ *
+ * The device route takes device pointers (d_out_row_offs: n_q + 1 u64, computed on the device), `configs` in host memory, and
+ * enqueues on `stream` — but it is the one device call that is NOT asynchronous: the group sizes come back through pinned memory
+ * with ONE wait on `stream` after the counting launch, before the groups are launched.  It returns with the groups' launches and
+ * the scatter enqueued. */
+#define SG_MAX_MIXED_CONFIGS 256u
+typedef struct sg_search_config {      /* 24 bytes */
+  int32_t metric;        /* enum sg_metric; ignored when autocomplete */
+  int32_t autocomplete;  /* 0: Suggest, 1: Autocomplete (k = limit, first_doc as in sg_autocomplete_batch_from) */
+  double similarity;     /* ignored when autocomplete */
+  uint32_t k, first_doc; /* first_doc must be 0 when autocomplete == 0 */
+} sg_search_config;
+int sg_suggest_batch_mixed(sg_index* index, const uint8_t* q_utf8, const uint64_t* q_offs, uint32_t n_q,
+                           const sg_search_config* configs, uint32_t n_configs, const uint32_t* config_of, uint64_t rows_cap,
+                           uint32_t* out_ids, double* out_scores, uint32_t* out_counts, uint64_t* out_row_offs);
+int sg_suggest_batch_mixed_device(sg_index* index, const void* d_q_utf8, const void* d_q_offs, uint32_t n_q,
+                                  const sg_search_config* configs, uint32_t n_configs, const void* d_config_of, uint64_t rows_cap,
+                                  void* d_out_ids, void* d_out_scores, void* d_out_counts, void* d_out_row_offs, void* stream);
+/* The single-query coalescer (sg_suggest_one, sg_autocomplete_one): on != 0 lets a dispatcher whose pending queue holds more than
+ * one key take everything pending — up to its batch limit and SG_MAX_MIXED_CONFIGS distinct keys, the rest waits for the next
+ * take — and answer it with ONE mixed call; a take with a single key goes as before.  Off by default: the dispatcher then takes
+ * only the requests that share the first one's key.  Results do not depend on it. */
+int sg_coalesce_mixed(sg_index* index, int on);
+/* Test hooks like the other sg_debug_* entries (bindings need not mirror them).  sg_debug_mixed_last: the calling thread's last
+ * successful mixed call with n_q > 0 — perm[j] (cap entries at least n_q) = the caller's number of the query at grouped position
+ * j, group_start[g] (n_configs + 1 entries) = the first grouped position of config g.  Fails when there was none, when n_configs is
+ * not that call's or cap is too small.  sg_debug_coalesce_hold: while on, the dispatchers take nothing (requests queue up); off
+ * releases them.  Release before the index goes.  sg_debug_coalesce_stats: out = {requests pending now; batches taken; of them
+ * mixed; launches — a mixed batch counts its configs, a plain one 1}.  No reference counterpart. */
+int sg_debug_mixed_last(uint32_t* perm, uint32_t cap, uint32_t* group_start, uint32_t n_configs);
+int sg_debug_coalesce_hold(sg_index* index, int on);
+int sg_debug_coalesce_stats(sg_index* index, uint64_t out[4]);
+/* Milliseconds of the calling thread's last device-route mixed call, between events on its stream, taken only while on != 0 was
+ * set by the first function (process-wide; it makes the call wait for its own end): out = {count; permute; gather; the groups'
+ * launches; scatter}.  tools/mixed_timing.py reads it.  A measuring hook only: while it is on, EVERY thread's device-route mixed
+ * call blocks until its own work has ended, so it must not stay on in a service. */
+int sg_debug_mixed_timing(int on);
+int sg_debug_mixed_times(double out_ms[5]);
+
 /* Sets a tuning knob of the index, before or after its first upload: SG_LOG2_CNT, SG_T_FLOOR, SG_FILTER_LEVEL, SG_TIGHTEN, SG_ROOMY,
  * SG_ORDER, SG_PRETOK, SG_SPLIT_CHUNKS, SG_PARTS_CNT_BONUS; the pipeline's SG_PIPE, SG_PIPE_SUB, SG_PIPE_CAND_CAP, SG_PIPE_WIDE,
  * SG_PLAN2.  SG_PIPE_NW, SG_PIPE_LOG2_CNT and SG_PIPE_DT_BYTES freeze the stream workgroup's shape for every launch;

@@ -30,6 +30,7 @@
 #include <sstream>
 #include <stdexcept>
 #include <string>
+#include <tuple>
 #include <utility>
 #include <vector>
 
@@ -432,6 +433,51 @@ class NGramIndex {
     return out;
   }
 
+  // Requests that differ in metric, similarity and topK — a SearchConfig each, as Service.Suggest takes one per call
+  // (service.go:105) — as ONE mixed call (sg_suggest_batch_mixed): equal (metric, similarity, topK) share an entry of the config
+  // table (keyed by the similarity's bits: a last bit apart is two entries); row i answers configs[i].  More than
+  // SG_MAX_MIXED_CONFIGS distinct configs: an Error.  Like SuggestBatch, the first query the reference would panic or block on
+  // throws for the whole call (the Python binding's suggest_many returns None for that row instead).
+  std::vector<std::vector<Candidate>> SuggestMany(const std::vector<SearchConfig>& configs) const {
+    const size_t n = configs.size();
+    std::vector<sg_search_config> table;
+    std::map<std::tuple<int32_t, uint64_t, uint32_t>, uint32_t> entry_of;
+    std::vector<uint32_t> config_of(n);
+    std::vector<std::string> queries;
+    uint64_t rows = 0;
+    for (size_t i = 0; i < n; i++) {
+      const SearchConfig& c = configs[i];
+      const sg_search_config e{(int32_t)c.metric.id, 0, c.similarity, (uint32_t)(c.topK > 0 ? c.topK : 0), 0u};
+      uint64_t sim_bits;
+      std::memcpy(&sim_bits, &e.similarity, 8);
+      auto it = entry_of.find(std::make_tuple(e.metric, sim_bits, e.k));
+      if (it == entry_of.end()) {
+        if (table.size() == SG_MAX_MIXED_CONFIGS) throw Error("SuggestMany: more distinct configs than one call takes");
+        it = entry_of.emplace(std::make_tuple(e.metric, sim_bits, e.k), (uint32_t)table.size()).first;
+        table.push_back(e);
+      }
+      config_of[i] = it->second;
+      queries.push_back(c.query);
+      rows += e.k;
+    }
+    std::vector<std::vector<Candidate>> out(n);
+    if (n == 0) return out;
+    std::vector<uint64_t> offs;
+    const std::string blob = Pack(queries, offs);
+    std::vector<uint32_t> ids(rows + 1), counts(n);
+    std::vector<double> scores(rows + 1);
+    std::vector<uint64_t> row_offs(n + 1);
+    Check(sg_suggest_batch_mixed(h_, (const uint8_t*)blob.data(), offs.data(), (uint32_t)n, table.data(), (uint32_t)table.size(), config_of.data(),
+                                 rows, ids.data(), scores.data(), counts.data(), row_offs.data()));
+    for (size_t i = 0; i < n; i++) {
+      if (counts[i] == SG_COUNT_REF_PANIC) throw Error("reference behaviour: panic: makechan: size out of range");
+      if (counts[i] == SG_COUNT_REF_DEADLOCK) throw Error("reference behaviour: deadlock (unbuffered channel, suggester.go:62)");
+      if (counts[i] == SG_COUNT_TOO_LONG) throw Error("query has more than SG_MAX_QUERY_TERMS n-grams");
+      for (uint32_t j = 0; j < counts[i]; j++) out[i].push_back(Candidate{ids[row_offs[i] + j], scores[row_offs[i] + j]});
+    }
+    return out;
+  }
+
   std::vector<std::vector<Candidate>> AutocompleteBatch(const std::vector<std::string>& queries, int limit) const {
     std::vector<uint64_t> offs;
     const std::string blob = Pack(queries, offs);
@@ -729,6 +775,19 @@ class Service {
     Lookup(dictName, ix, dict);
     std::vector<std::vector<ResultItem>> out;
     for (auto& row : ix->SuggestBatch(queries, similarity, m, topK)) {
+      out.emplace_back();
+      for (const Candidate& c : row) out.back().push_back(ResultItem{c.Score, dict->Get(c.Key)});
+    }
+    return out;
+  }
+  // additive: one mixed call for requests of one dictionary that differ in metric, similarity and topK (NGramIndex::SuggestMany)
+  std::vector<std::vector<ResultItem>> SuggestMany(const std::string& dictName, const std::vector<SearchConfig>& configs) const {
+    for (const SearchConfig& c : configs) NewSearchConfig(c.query, c.topK, c.metric, c.similarity);
+    std::shared_ptr<NGramIndex> ix;
+    std::shared_ptr<dictionary::Dictionary> dict;
+    Lookup(dictName, ix, dict);
+    std::vector<std::vector<ResultItem>> out;
+    for (auto& row : ix->SuggestMany(configs)) {
       out.emplace_back();
       for (const Candidate& c : row) out.back().push_back(ResultItem{c.Score, dict->Get(c.Key)});
     }

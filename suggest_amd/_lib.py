@@ -35,7 +35,10 @@ EXPORTS = [
     "sg_sharded_build", "sg_sharded_adopt", "sg_sharded_retain", "sg_sharded_release", "sg_sharded_shards", "sg_sharded_suggest_batch",
     "sg_sharded_suggest_batch_device", "sg_sharded_autocomplete_batch", "sg_debug_shard_slice_bytes", "sg_debug_shard_merge", "sg_debug_shard_merge_time",
     "sg_debug_index_build_table_bits", "sg_debug_index_build_report",
+    "sg_suggest_batch_mixed", "sg_suggest_batch_mixed_device", "sg_coalesce_mixed", "sg_debug_mixed_last", "sg_debug_coalesce_hold",
+    "sg_debug_coalesce_stats", "sg_debug_mixed_timing", "sg_debug_mixed_times",
 ]
+SG_MAX_MIXED_CONFIGS = 256
 SG_MAX_SHARDS = 64
 SG_LM_STORE_MPH = 1
 SG_COUNT_LM_ERROR = 0xFFFFFFFC
@@ -49,6 +52,11 @@ class SgDesc(C.Structure):
 class SgStats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("n_docs", "n_segments", "n_terms", "n_lists", "n_postings", "n_postings_raw",
                                           "posting_bytes", "table_bytes", "device_bytes")]
+
+
+class SgSearchConfig(C.Structure):
+    """sg_search_config: one entry of a mixed batch's table (24 bytes)"""
+    _fields_ = [("metric", C.c_int32), ("autocomplete", C.c_int32), ("similarity", C.c_double), ("k", C.c_uint32), ("first_doc", C.c_uint32)]
 
 
 class SuggestHipError(RuntimeError):
@@ -187,6 +195,14 @@ def lib():
     if hasattr(L, "sg_debug_shard_slice_bytes"): L.sg_debug_shard_slice_bytes.argtypes = [u32]
     if hasattr(L, "sg_debug_shard_merge"): L.sg_debug_shard_merge.argtypes = [i32, vp, vp, vp, vp, u32, u32, u32, i32, vp, vp, vp]
     if hasattr(L, "sg_debug_shard_merge_time"): L.sg_debug_shard_merge_time.argtypes = [C.POINTER(dbl)]
+    if hasattr(L, "sg_suggest_batch_mixed"): L.sg_suggest_batch_mixed.argtypes = [vp, vp, vp, u32, vp, u32, vp, u64, vp, vp, vp, vp]
+    if hasattr(L, "sg_suggest_batch_mixed_device"): L.sg_suggest_batch_mixed_device.argtypes = [vp, vp, vp, u32, vp, u32, vp, u64, vp, vp, vp, vp, vp]
+    if hasattr(L, "sg_coalesce_mixed"): L.sg_coalesce_mixed.argtypes = [vp, i32]
+    if hasattr(L, "sg_debug_mixed_last"): L.sg_debug_mixed_last.argtypes = [vp, u32, vp, u32]
+    if hasattr(L, "sg_debug_coalesce_hold"): L.sg_debug_coalesce_hold.argtypes = [vp, i32]
+    if hasattr(L, "sg_debug_coalesce_stats"): L.sg_debug_coalesce_stats.argtypes = [vp, vp]
+    if hasattr(L, "sg_debug_mixed_timing"): L.sg_debug_mixed_timing.argtypes = [i32]
+    if hasattr(L, "sg_debug_mixed_times"): L.sg_debug_mixed_times.argtypes = [vp]
     _lib = L
     return L
 

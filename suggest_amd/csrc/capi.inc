@@ -352,9 +352,8 @@ Replica* find_replica(sg_index* ix, int device, uint32_t nth = 0) {
   return nullptr;
 }
 
-int check_search_args(sg_index* index, uint32_t k, bool need_alpha, double similarity, int metric) {
-  if (!index) { set_error("null index"); return SG_E_INVALID; }
-  if (!index->uploaded.load(std::memory_order_acquire)) { set_error("index not uploaded: call sg_index_upload first"); return SG_E_NOT_UPLOADED; }
+// the checks of a search's values alone (a mixed call makes them for every entry of its table before it looks at the index)
+int check_search_values(uint32_t k, bool need_alpha, double similarity, int metric) {
   if (k == 0) { set_error("topK should be greater or equal to 1"); return SG_E_INVALID; }       // search.go:20-22
   if (k > SG_MAX_TOPK) { set_error("topK above SG_MAX_TOPK"); return SG_E_INVALID; }
   if (need_alpha) {
@@ -362,6 +361,11 @@ int check_search_args(sg_index* index, uint32_t k, bool need_alpha, double simil
     if (metric < SG_JACCARD || metric > SG_OVERLAP) { set_error("unknown metric"); return SG_E_INVALID; }
   }
   return SG_OK;
+}
+int check_search_args(sg_index* index, uint32_t k, bool need_alpha, double similarity, int metric) {
+  if (!index) { set_error("null index"); return SG_E_INVALID; }
+  if (!index->uploaded.load(std::memory_order_acquire)) { set_error("index not uploaded: call sg_index_upload first"); return SG_E_NOT_UPLOADED; }
+  return check_search_values(k, need_alpha, similarity, metric);
 }
 
 struct LmRanges { const uint64_t* values; const uint32_t *from, *to; };   // device pointers (spellchecker mode)
@@ -418,7 +422,10 @@ struct GrowBlock {
 // A block per tag: one launch holds SCRATCH_ROWS, SCRATCH_LONG_LIST and one of SCRATCH_PRETOK / SCRATCH_PIPE of its stream at
 // once, and Predict's block besides when Predict is the caller — four at most.  Sentence scoring (lm_score.inc) holds its own
 // block alone.  A sharded search (shard_merge.inc) holds SCRATCH_SHARD, the shards' rows, around its launches.
-enum ScratchTag { SCRATCH_ROWS = 0, SCRATCH_PREDICT = 1, SCRATCH_LONG_LIST = 2, SCRATCH_PRETOK = 3, SCRATCH_PIPE = 4, SCRATCH_LM_SCORE = 5, SCRATCH_SHARD = 6 };
+// A mixed call (mixed_batch.inc) holds SCRATCH_MIXED, its lists and offsets, and SCRATCH_MIXED_ROWS, the grouped queries and the
+// groups' rows, around its launches.
+enum ScratchTag { SCRATCH_ROWS = 0, SCRATCH_PREDICT = 1, SCRATCH_LONG_LIST = 2, SCRATCH_PRETOK = 3, SCRATCH_PIPE = 4, SCRATCH_LM_SCORE = 5, SCRATCH_SHARD = 6,
+                  SCRATCH_MIXED = 7, SCRATCH_MIXED_ROWS = 8 };
 struct ScratchSlot { int device; hipStream_t stream; int tag; GrowBlock blk; bool held = false; };
 inline bool on_main_thread() { return (long)getpid() == (long)syscall(SYS_gettid); }
 // (a thread that ends hands its buffers back; the main thread's are left to process exit, when the HIP runtime may already
@@ -1474,19 +1481,24 @@ static void thread_contexts_release() {
 
 // The device block of a host-buffer call: [scores | ids | counts | aux] — the results, one copy back — then, from the next 16
 // bytes on, [offsets | queries] — the inputs, one copy in.  Offsets and sizes in bytes.  Predict: id rows of topK + 1, counts.
+// A mixed call (mixed_batch.inc): ragged rows — `rows` slots in all in place of n_q * k — and, behind the queries, its [n_q] list
+// of config numbers (sel); a fixed-k call has neither and lies exactly as it did.
 struct IoLayout {
-  size_t sc_bytes = 0, id_bytes = 0, cnt_bytes = 0, aux_bytes = 0, off_bytes = 0, q_bytes = 0;
-  size_t ids = 0, cnt = 0, aux = 0, out_bytes = 0, offs = 0, q = 0, in_bytes = 0, total = 0;   // (the scores start the block)
+  size_t sc_bytes = 0, id_bytes = 0, cnt_bytes = 0, aux_bytes = 0, off_bytes = 0, q_bytes = 0, sel_bytes = 0;
+  size_t ids = 0, cnt = 0, aux = 0, out_bytes = 0, offs = 0, q = 0, sel = 0, in_bytes = 0, total = 0;   // (the scores start the block)
 };
-static IoLayout io_layout(uint32_t n_q, uint32_t k, bool scores, bool aux, size_t q_bytes) {
+constexpr uint64_t kRowsFixed = ~0ull;      // HostBufs::rows of a fixed-k call: n_q * row
+static IoLayout io_layout(uint32_t n_q, uint32_t k, bool scores, bool aux, size_t q_bytes, uint64_t rows = kRowsFixed, bool sel = false) {
   IoLayout L;
-  L.sc_bytes = scores ? (size_t)n_q * k * 8 : 0; L.id_bytes = (size_t)n_q * k * 4; L.cnt_bytes = (size_t)n_q * 4;
-  L.aux_bytes = aux ? (size_t)n_q * k * 4 : 0; L.off_bytes = (size_t)(n_q + 1) * 8; L.q_bytes = q_bytes;
+  const size_t slots = rows == kRowsFixed ? (size_t)n_q * k : (size_t)rows;
+  L.sc_bytes = scores ? slots * 8 : 0; L.id_bytes = slots * 4; L.cnt_bytes = (size_t)n_q * 4;
+  L.aux_bytes = aux ? slots * 4 : 0; L.off_bytes = (size_t)(n_q + 1) * 8; L.q_bytes = q_bytes;
   Carve c;
   c.take(L.sc_bytes);
   L.ids = c.take(L.id_bytes, 4); L.cnt = c.take(L.cnt_bytes, 4); L.aux = c.take(L.aux_bytes, 4);
   L.out_bytes = c.off;
   L.offs = c.take(L.off_bytes); L.q = c.take(q_bytes, 8);
+  if (sel) { L.sel_bytes = (size_t)n_q * 4; L.sel = c.take(L.sel_bytes, 4); }
   L.in_bytes = c.off - L.offs; L.total = c.off + 16;
   return L;
 }
@@ -1525,6 +1537,8 @@ static bool is_pinned_host(const void* p, size_t bytes) {
 struct HostBufs {
   const uint8_t* q = nullptr; const uint64_t* offs = nullptr; uint32_t n_q = 0, row = 0;
   uint32_t* ids = nullptr; double* scores = nullptr; uint32_t* counts = nullptr; uint32_t* aux = nullptr;
+  uint64_t rows = kRowsFixed;          // a mixed call: the slots of its ragged ids / scores rows in all (`row` unused)
+  const uint32_t* sel = nullptr;       // ... and its [n_q] config numbers, staged and copied in with the queries
 };
 // What a call runs on.  A synchronous call: the calling thread's HostCtx — one stream for everything, no events, one staging
 // buffer both ways, staging up to kPinnedMax.  A ticket: its AsyncSlot — the copy-in, run and copy-out streams of the replica's
@@ -1552,7 +1566,7 @@ using Enqueue = std::function<int(char* dev, const IoLayout& io, hipStream_t st)
 static int begin_host_call(const HostBufs& b, bool clear_rows, const Enqueue& enqueue, const IoCtx& x, HostCall* c) {
   const uint64_t q0 = b.offs[0];
   if (!b.q && b.offs[b.n_q] != q0) { set_error("null query buffer"); return SG_E_INVALID; }
-  const IoLayout io = io_layout(b.n_q, b.row, b.scores != nullptr, b.aux != nullptr, (size_t)(b.offs[b.n_q] - q0));
+  const IoLayout io = io_layout(b.n_q, b.row, b.scores != nullptr, b.aux != nullptr, (size_t)(b.offs[b.n_q] - q0), b.rows, b.sel != nullptr);
   // the routes.  A ticket: caller memory from sg_host_alloc where it lies, the rest staged.  A synchronous call: staged both ways
   // while it fits kPinnedMax, else straight from / to the caller's memory — but offsets that do not start at zero (a slice of a
   // larger batch) are rebased in the staging buffer.
@@ -1583,10 +1597,12 @@ static int begin_host_call(const HostBufs& b, bool clear_rows, const Enqueue& en
     uint64_t* po = (uint64_t*)pin;
     if (q0) for (uint32_t i = 0; i <= b.n_q; i++) po[i] = b.offs[i] - q0; else memcpy(po, b.offs, io.off_bytes);
     if (io.q_bytes) memcpy(pin + io.off_bytes, b.q + q0, io.q_bytes);
+    if (io.sel_bytes) memcpy(pin + (io.sel - io.offs), b.sel, io.sel_bytes);
     HIP_TRY(hipMemcpyAsync(dev + io.offs, pin, io.in_bytes, hipMemcpyHostToDevice, x.in));
   } else {
     HIP_TRY(hipMemcpyAsync(dev + io.offs, b.offs, io.off_bytes, hipMemcpyHostToDevice, x.in));
     if (io.q_bytes) HIP_TRY(hipMemcpyAsync(dev + io.q, b.q, io.q_bytes, hipMemcpyHostToDevice, x.in));
+    if (io.sel_bytes) HIP_TRY(hipMemcpyAsync(dev + io.sel, b.sel, io.sel_bytes, hipMemcpyHostToDevice, x.in));
   }
   // (rows of queries with fewer than k results stay zero; a ticket clears them on its copy-in stream, beside the previous
   //  ticket's search launch — on the run stream the 8 MB fill was 0.09 ms between two search launches)
@@ -2156,30 +2172,132 @@ struct Coalescer {
   std::vector<std::thread> lanes;
   uint32_t max_batch = 8192;
   std::atomic<uint32_t> batch_ns{100000};   // recent time from taking a batch to answering it (moving average): how long callers spin
+  bool mixed = false;               // sg_coalesce_mixed: a take with several keys is ONE mixed call (mixed_batch.inc); under mu
+  bool hold = false;                // sg_debug_coalesce_hold: the dispatchers take nothing (a stop overrides it); under mu
+  std::atomic<uint64_t> n_batches{0}, n_mixed{0}, n_groups{0};   // sg_debug_coalesce_stats: takes, mixed ones, launches (a plain take is one)
 };
 
+// the mixed call over host buffers (mixed_batch.inc; the arguments of sg_suggest_batch_mixed, checked, on `rep`)
+static int mixed_host_call(sg_index* index, Replica* rep, const uint8_t* q, const uint64_t* offs, uint32_t n_q, const sg_search_config* configs,
+                           uint32_t n_configs, const uint32_t* config_of, uint64_t rows_cap, uint32_t* ids, double* scores, uint32_t* counts,
+                           uint64_t* row_offs);
+
+// The end of every take, plain or mixed: each caller gets its row (row i starts at row_offs[i]; at i * k where row_offs is null, a
+// plain take, whose requests share one k), then the sleeping callers are woken.  ONE statement of the wake-up: OneWaiter::child is
+// the caller thread's and outlives the request, so every take rewrites it for every sleeper.
+static void answer_take(Coalescer* c, const std::vector<OneReq*>& batch, int rc, const std::string& err, const uint32_t* ids, const double* scores,
+                        const uint32_t* counts, const uint64_t* row_offs, std::vector<OneWaiter*>& sleepers,
+                        std::chrono::steady_clock::time_point t_batch) {
+  sleepers.clear();
+  for (size_t i = 0; i < batch.size(); i++) {
+    OneReq* r = batch[i];
+    r->rc = rc;
+    if (rc) r->err = err;
+    else {
+      const uint32_t k = r->k, cnt = counts[i], m = cnt < k ? cnt : (cnt >= SG_COUNT_LM_ERROR ? 0u : k);
+      const size_t at = row_offs ? (size_t)row_offs[i] : i * (size_t)k;
+      *r->count = cnt;
+#ifdef SG_PHASE_TIMING
+      memcpy(r->ids, ids + at, (size_t)(row_offs ? m : k) * 4);   // (debug builds, a plain take: the whole row, it may carry debug words)
+#else
+      memcpy(r->ids, ids + at, (size_t)m * 4);
+#endif
+      if (!r->autocomplete) memcpy(r->scores, scores + at, (size_t)m * 8);
+    }
+    OneWaiter* w = r->waiter;                              // (r is the caller's: gone once it sees state 1)
+    if (r->state.exchange(1, std::memory_order_acq_rel) == 2) sleepers.push_back(w);   // asleep: stays until released
+  }
+  // the sleeping callers are woken one by one; SG_COALESCE_TREE=1 lets them wake each other up as a binary tree instead
+  // (one futex wake on the dispatcher per batch: better with spare cores, worse on a CPU quota)
+  static const bool tree = env_int("SG_COALESCE_TREE", 0, 1, 0) != 0;
+  for (size_t i = 0; i < sleepers.size(); i++) {
+    sleepers[i]->child[0] = tree && 2 * i + 1 < sleepers.size() ? sleepers[2 * i + 1] : nullptr;
+    sleepers[i]->child[1] = tree && 2 * i + 2 < sleepers.size() ? sleepers[2 * i + 2] : nullptr;
+  }
+  if (tree) { if (!sleepers.empty()) release_waiter(sleepers[0]); }
+  else for (OneWaiter* w : sleepers) release_waiter(w);
+  const uint32_t ns = (uint32_t)std::min<long long>(std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t_batch).count(), 5000000);
+  c->batch_ns.store((c->batch_ns.load(std::memory_order_relaxed) * 7u + ns) / 8u, std::memory_order_relaxed);
+}
+
 static void coalescer_lane(Coalescer* c, Replica* rep) {
-  std::vector<OneReq*> batch;
+  std::vector<OneReq*> batch, late;
+  std::map<std::tuple<int, uint64_t, uint32_t, int, uint32_t>, uint32_t> key_no;   // a mixed take: its keys, numbered as they first appear
   std::vector<uint8_t> blob;
   std::vector<uint64_t> offs;
   std::vector<uint32_t> ids, counts;
   std::vector<double> scores;
   std::vector<OneWaiter*> sleepers;
+  std::vector<sg_search_config> cfgs;          // a mixed take: its distinct keys, the key of every request, the rows' starts
+  std::vector<uint32_t> cfg_of;
+  std::vector<uint64_t> row_offs;
   struct AtExit { ~AtExit() { thread_contexts_release(); } } at_exit;
   for (;;) {
-    batch.clear();
-    sleepers.clear();
+    batch.clear(); late.clear();
+    cfgs.clear(); cfg_of.clear(); key_no.clear();
+    bool mixed_take;
     {
       std::unique_lock<std::mutex> lock(c->mu);
-      c->cv.wait(lock, [&] { return c->stop || !c->pending.empty(); });
+      c->cv.wait(lock, [&] { return c->stop || (!c->hold && !c->pending.empty()); });
       if (c->pending.empty()) return;                       // stop, and nothing left to serve
       OneReq* first = c->pending.front();
       c->pending.pop_front();
       batch.push_back(first);
-      for (auto it = c->pending.begin(); it != c->pending.end() && batch.size() < c->max_batch;) {
-        if ((*it)->same_key(*first)) { batch.push_back(*it); it = c->pending.erase(it); } else ++it;
+      mixed_take = c->mixed;
+      if (!mixed_take) {
+        for (auto it = c->pending.begin(); it != c->pending.end() && batch.size() < c->max_batch;) {
+          if ((*it)->same_key(*first)) { batch.push_back(*it); it = c->pending.erase(it); } else ++it;
+        }
+      } else {                                               // the oldest max_batch requests, whatever their keys: sorted out below, off the lock
+        while (!c->pending.empty() && batch.size() < c->max_batch) { batch.push_back(c->pending.front()); c->pending.pop_front(); }
       }
     }
+    if (mixed_take) {
+      // the keys are numbered in order of first appearance, SG_MAX_MIXED_CONFIGS of them at the most: a request with one key more goes
+      // back to the head of the queue, in its order, for the next take.  (The key holds the similarity's bits, -0 as +0: what
+      // same_key calls equal.)
+      size_t kept = 0;
+      for (OneReq* r : batch) {
+        const double sim = r->sim + 0.0;
+        uint64_t sim_bits;
+        memcpy(&sim_bits, &sim, 8);
+        const auto key = std::make_tuple(r->metric, sim_bits, r->k, r->autocomplete, r->ac_first);
+        auto it = key_no.find(key);
+        if (it == key_no.end()) {
+          if (key_no.size() == SG_MAX_MIXED_CONFIGS) { late.push_back(r); continue; }
+          it = key_no.emplace(key, (uint32_t)key_no.size()).first;
+          cfgs.push_back(sg_search_config{r->metric, r->autocomplete, r->sim, r->k, r->ac_first});
+        }
+        cfg_of.push_back(it->second);
+        batch[kept++] = r;
+      }
+      batch.resize(kept);
+      if (!late.empty()) {
+        { std::lock_guard<std::mutex> lock(c->mu); c->pending.insert(c->pending.begin(), late.begin(), late.end()); }
+        c->cv.notify_one();
+      }
+      if (cfgs.size() == 1) cfgs.clear();                    // a take with a single key goes exactly the old way
+    }
+    if (!cfgs.empty()) {       // several keys: one mixed call, every caller's row cut out of the ragged rows
+      const uint32_t n = (uint32_t)batch.size();
+      const auto t_batch = std::chrono::steady_clock::now();
+      int rc = SG_OK;
+      std::string err;
+      try {
+        blob.clear(); offs.assign(1, 0);
+        uint64_t rows = 0;
+        for (OneReq* r : batch) { blob.insert(blob.end(), r->q, r->q + r->len); offs.push_back(blob.size()); rows += r->k; }
+        ids.resize(rows); scores.resize(rows); counts.resize(n); row_offs.resize((size_t)n + 1);
+        rc = mixed_host_call(c->index, rep, blob.data(), offs.data(), n, cfgs.data(), (uint32_t)cfgs.size(), cfg_of.data(), rows, ids.data(),
+                             scores.data(), counts.data(), row_offs.data());
+        if (rc) err = g_err;
+      } catch (const std::exception& e) { rc = SG_E_NOMEM; err = e.what(); }
+      c->n_batches.fetch_add(1, std::memory_order_relaxed); c->n_mixed.fetch_add(1, std::memory_order_relaxed);
+      c->n_groups.fetch_add(cfgs.size(), std::memory_order_relaxed);
+      answer_take(c, batch, rc, err, ids.data(), scores.data(), counts.data(), row_offs.data(), sleepers, t_batch);
+      continue;
+    }
+    c->n_batches.fetch_add(1, std::memory_order_relaxed); c->n_groups.fetch_add(1, std::memory_order_relaxed);
     // (copies: batch[0] lives on its caller's stack and is gone once that caller is answered)
     const struct { int metric; double sim; uint32_t k; int autocomplete; uint32_t ac_first; } f = {batch[0]->metric, batch[0]->sim, batch[0]->k, batch[0]->autocomplete, batch[0]->ac_first};
     const uint32_t n = (uint32_t)batch.size(), k = f.k;
@@ -2195,34 +2313,7 @@ static void coalescer_lane(Coalescer* c, Replica* rep) {
                     f.autocomplete ? nullptr : scores.data(), counts.data());
       if (rc) err = g_err;
     } catch (const std::exception& e) { rc = SG_E_NOMEM; err = e.what(); }
-    for (uint32_t i = 0; i < n; i++) {
-      OneReq* r = batch[i];
-      r->rc = rc;
-      if (rc) r->err = err;
-      else {
-        const uint32_t cnt = counts[i], m = cnt < k ? cnt : (cnt >= SG_COUNT_LM_ERROR ? 0u : k);
-        *r->count = cnt;
-#ifdef SG_PHASE_TIMING
-        memcpy(r->ids, ids.data() + (size_t)i * k, (size_t)k * 4);   // (debug builds: the whole row, it may carry debug words)
-#else
-        memcpy(r->ids, ids.data() + (size_t)i * k, (size_t)m * 4);
-#endif
-        if (!f.autocomplete) memcpy(r->scores, scores.data() + (size_t)i * k, (size_t)m * 8);
-      }
-      OneWaiter* w = r->waiter;                              // (r is the caller's: gone once it sees state 1)
-      if (r->state.exchange(1, std::memory_order_acq_rel) == 2) sleepers.push_back(w);   // asleep: stays until released
-    }
-    // the sleeping callers are woken one by one; SG_COALESCE_TREE=1 lets them wake each other up as a binary tree instead
-    // (one futex wake on the dispatcher per batch: better with spare cores, worse on a CPU quota)
-    static const bool tree = env_int("SG_COALESCE_TREE", 0, 1, 0) != 0;
-    for (size_t i = 0; i < sleepers.size(); i++) {
-      sleepers[i]->child[0] = tree && 2 * i + 1 < sleepers.size() ? sleepers[2 * i + 1] : nullptr;
-      sleepers[i]->child[1] = tree && 2 * i + 2 < sleepers.size() ? sleepers[2 * i + 2] : nullptr;
-    }
-    if (tree) { if (!sleepers.empty()) release_waiter(sleepers[0]); }
-    else for (OneWaiter* w : sleepers) release_waiter(w);
-    const uint32_t ns = (uint32_t)std::min<long long>(std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t_batch).count(), 5000000);
-    c->batch_ns.store((c->batch_ns.load(std::memory_order_relaxed) * 7u + ns) / 8u, std::memory_order_relaxed);
+    answer_take(c, batch, rc, err, ids.data(), scores.data(), counts.data(), nullptr, sleepers, t_batch);
   }
 }
 

@@ -25,6 +25,7 @@
 #include <memory>
 #include <mutex>
 #include <thread>
+#include <tuple>
 #include <functional>
 #include <string>
 #include <sys/syscall.h>
@@ -2960,3 +2961,4 @@ __global__ __launch_bounds__(64) void pairsort_test_kernel(const uint32_t* keys,
 #include "index_load.inc"
 #include "lm_store.inc"
 #include "shard_merge.inc"
+#include "mixed_batch.inc"

@@ -158,6 +158,34 @@ def build_report():
     return dict(zip(("passes", "log2_table", "terms", "long_docs"), (int(x) for x in out)))
 
 
+def mixed_table(configs):
+    """The sg_search_config array of a mixed batch from a sequence of (metric, similarity, k) tuples, dicts (metric, similarity, k,
+    autocomplete, first_doc) or _lib.SgSearchConfig entries.  Values are passed on as they are: the library checks them."""
+    table = (_lib.SgSearchConfig * len(configs))()
+    for i, c in enumerate(configs):
+        if isinstance(c, _lib.SgSearchConfig):
+            table[i] = c
+            continue
+        if not isinstance(c, dict):
+            c = dict(zip(("metric", "similarity", "k"), c))
+        ac = 1 if c.get("autocomplete") else 0
+        metric = c.get("metric", 0)
+        code = metric if isinstance(metric, int) else resolve(metric).code
+        if code is None:
+            raise ValueError("a mixed batch takes the metrics with a device twin (jaccard, cosine, dice, exact, overlap)")
+        table[i] = _lib.SgSearchConfig(int(code), ac, float(c.get("similarity", 0.0)), int(c["k"]), int(c.get("first_doc", 0)))
+    return table
+
+
+def mixed_last(n_q, n_configs):
+    """Test hook (sg_debug_mixed_last): the calling thread's last mixed call -> (perm[n_q], group_start[n_configs + 1]): the
+    caller's number of the query at every grouped position, the first grouped position of every config."""
+    perm = np.zeros(n_q, dtype=np.uint32)
+    start = np.zeros(n_configs + 1, dtype=np.uint32)
+    _lib.check(_lib.lib().sg_debug_mixed_last(perm.ctypes.data, n_q, start.ctypes.data, n_configs))
+    return perm, start
+
+
 class NGramIndex:
     def __init__(self, docs=None, description=None, blob=None, offs=None, device=0, upload=True, _handle=None, build="host", min_segments=0):
         """build="host": sg_index_build (CPU tokenise + CSR); build="device": sg_index_build_device (same arrays, built on the
@@ -484,6 +512,48 @@ class NGramIndex:
     def autocomplete_batch_device(self, d_blob, d_offs, n_q, limit, d_ids, d_counts, stream=0):
         with self._use() as h:
             _lib.check(_lib.lib().sg_autocomplete_batch_device(h, d_blob, d_offs, int(n_q), int(limit), d_ids, d_counts, stream))
+
+    # ---- search: one batch, a config per query (sg_suggest_batch_mixed) ------
+    def suggest_batch_mixed(self, queries=None, configs=(), config_of=(), blob=None, offs=None):
+        """One batch whose queries differ in metric, similarity and k.  configs: the table of DISTINCT configs (at most 256) —
+        each a (metric, similarity, k) tuple, a dict with the keys metric / similarity / k / autocomplete / first_doc, or a
+        _lib.SgSearchConfig; config_of[i]: the table entry query i is answered with.
+        -> (ids, scores, counts, row_offs), ragged: row i is ids[row_offs[i]:row_offs[i + 1]] (k of its config slots, best first,
+        zero past counts[i]), scores alike (zero for an autocomplete config).  Every row is bit for bit the plain call's."""
+        if blob is None:
+            blob, offs = pack_strings(queries)
+        blob = np.ascontiguousarray(blob, dtype=np.uint8)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        n_q = len(offs) - 1
+        table = mixed_table(configs)
+        cfg_of = np.ascontiguousarray(config_of, dtype=np.uint32)
+        if cfg_of.shape != (n_q,):
+            raise ValueError("config_of needs one entry per query")
+        ks = np.array([c.k for c in table], dtype=np.uint64)
+        rows = int(ks[cfg_of[cfg_of < len(table)]].sum()) if len(table) else 0    # (a number outside the table: the library refuses it)
+        ids = np.zeros(rows, dtype=np.uint32)
+        sc = np.zeros(rows, dtype=np.float64)
+        cnt = np.zeros(n_q, dtype=np.uint32)
+        row_offs = np.zeros(n_q + 1, dtype=np.uint64)
+        with self._use() as h:
+            _lib.check(_lib.lib().sg_suggest_batch_mixed(h, blob.ctypes.data if blob.size else None, offs.ctypes.data, n_q, table, len(table),
+                                                         cfg_of.ctypes.data, rows, ids.ctypes.data, sc.ctypes.data, cnt.ctypes.data, row_offs.ctypes.data))
+        return ids, sc, cnt, row_offs
+
+    def suggest_batch_mixed_device(self, d_blob, d_offs, n_q, configs, d_config_of, rows_cap, d_ids, d_scores, d_counts, d_row_offs, stream=0):
+        """The same over device-resident buffers (raw pointers), on `stream`; d_ids / d_scores have room for rows_cap slots,
+        d_row_offs for n_q + 1 u64.  The one device call that waits on its stream once (the group sizes come back to the host)."""
+        table = mixed_table(configs)
+        with self._use() as h:
+            _lib.check(_lib.lib().sg_suggest_batch_mixed_device(h, d_blob, d_offs, int(n_q), table, len(table), d_config_of, int(rows_cap),
+                                                                d_ids, d_scores, d_counts, d_row_offs, stream))
+
+    def coalesce_mixed(self, on=True):
+        """sg_coalesce_mixed: let the single-query coalescer answer a take that holds several (metric, similarity, k) keys with ONE
+        mixed call (off by default: such requests then wait for batches of their own key)."""
+        with self._use() as h:
+            _lib.check(_lib.lib().sg_coalesce_mixed(h, 1 if on else 0))
+        return self
 
     # ---- NGramIndex interface (single query) -----------------------------------------------
     def suggest(self, query, similarity, metric, k):

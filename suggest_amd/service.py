@@ -166,6 +166,38 @@ class Service:
             out.append([ResultItem(float(sc[i, j]), self._value(dictionary, int(ids[i, j]))) for j in range(c)])
         return out
 
+    def suggest_many(self, dict_name, configs):
+        """Service.Suggest for a list of SearchConfig — each with its own query, metric, similarity and topK — as ONE mixed batch
+        (NGramIndex.suggest_batch_mixed): -> a list of [ResultItem] in the order of `configs`, None for a query the reference
+        does not answer either (as suggest_batch).  Equal (metric, similarity, topK) share a table entry; more than 256 distinct
+        ones go in several calls."""
+        index, dictionary = self._lookup(dict_name)
+        out = [None] * len(configs)
+        todo = list(range(len(configs)))
+        while todo:
+            table, number, taken, rest = [], {}, [], []
+            for i in todo:
+                c = configs[i]
+                if c.metric.code is None:
+                    raise ValueError("suggest_many takes the metrics with a device twin (jaccard, cosine, dice, exact, overlap)")
+                key = (c.metric.code, c.similarity, c.top_k)
+                if key not in number:
+                    if len(table) == _lib.SG_MAX_MIXED_CONFIGS:
+                        rest.append(i)
+                        continue
+                    number[key] = len(table)
+                    table.append(key)
+                taken.append(i)
+            ids, sc, cnt, row_offs = index.suggest_batch_mixed([configs[i].query for i in taken], table, [number[(configs[i].metric.code, configs[i].similarity, configs[i].top_k)] for i in taken])
+            for j, i in enumerate(taken):
+                c = int(cnt[j])
+                if c >= _lib.SG_COUNT_TOO_LONG:
+                    continue
+                r = int(row_offs[j])
+                out[i] = [ResultItem(float(sc[r + t]), self._value(dictionary, int(ids[r + t]))) for t in range(c)]
+            todo = rest
+        return out
+
     # Go-style aliases so reference call sites read the same
     AddIndexByDescription = add_index_by_description
     AddRunTimeIndex = add_run_time_index
