@@ -516,8 +516,12 @@ func (e *engine) tablesFor(m metric.Metric, sim float64, terms int) (*C.sg_metri
 		return C.int32_t(v)
 	}
 	for a := 1; a < nA; a++ {
-		lo, hi := m.MinY(sim, a), m.MaxY(sim, a)
-		minY[a], maxY[a] = clamp(lo), clamp(hi)
+		minY[a], maxY[a] = clamp(m.MinY(sim, a)), clamp(m.MaxY(sim, a))
+		// the segments the reference visits, not [MinY, MaxY]: a, a-1, ... >= MinY and a+1, ... <= bMax (suggester.go:113-121;
+		// sg_metric_tables_create passes minY / maxY through the same function)
+		var w [2]C.int32_t
+		C.sg_metric_window(minY[a], maxY[a], C.uint32_t(a), C.uint32_t(S), &w[0])
+		lo, hi := int(w[0]), int(w[1])
 		if lo < 0 {
 			lo = 0
 		}

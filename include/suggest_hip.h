@@ -271,7 +271,12 @@ int sg_autocomplete_batch_from(sg_index* index, const uint8_t* q_utf8, const uin
  *   threshold[a * S + b]                    b = 0 .. S - 1          Metric.Threshold(alpha, a, b)
  *   score[(a * S + b) * (a_max + 1) + o]    o = 0 .. a_max          1 - Metric.Distance(o, a, b)   (scorer.go:29-31)
  * S = sg_stats.n_segments of `index`.  A query with more than a_max n-grams comes back SG_COUNT_TOO_LONG.  The tables are
- * copied to the HBM of the index's primary replica and live until released (they retain the index). */
+ * copied to the HBM of the index's primary replica and live until released (they retain the index).
+ * Which b a query of a n-grams visits: NOT [MinY, min(MaxY, S - 1)] but what suggester.go:113-121 sends — a, a - 1, ... down to
+ * MinY and a + 1, a + 2, ... up to min(MaxY, S - 1).  sg_metric_window gives that range as one pair (out[0] .. out[1]; the raw
+ * pair where the span is zero or below: such a query stays flagged); sg_metric_tables_create passes every row of min_y / max_y
+ * through it, and a binding fills threshold and score over out[0] .. min(out[1], S - 1).  It needs no GPU. */
+int sg_metric_window(int32_t min_y, int32_t max_y, uint32_t a, uint32_t n_segments, int32_t* out);
 typedef struct sg_metric_tables sg_metric_tables;
 int sg_metric_tables_create(sg_index* index, uint32_t a_max, const int32_t* min_y, const int32_t* max_y,
                             const int32_t* threshold, const double* score, sg_metric_tables** out);

@@ -26,7 +26,7 @@ EXPORTS = [
     "sg_lm_load_google_ex", "sg_lm_load_binary", "sg_lm_level", "sg_lm_order", "sg_index_tune", "sg_index_forward", "sg_autocomplete_algorithmic_bytes", "sg_debug_pairsort", "sg_debug_tune_choice", "sg_debug_pipe_shape", "sg_debug_tune_index", "sg_debug_knob", "sg_debug_replica_devices", "sg_debug_index_array",
     "sg_debug_poison", "sg_debug_poison_stats", "sg_debug_rows_layout", "sg_debug_pipe_layout",
     "sg_host_alloc", "sg_host_free", "sg_suggest_submit", "sg_suggest_submit_on", "sg_autocomplete_submit", "sg_ticket_wait",
-    "sg_metric_tables_create", "sg_metric_tables_retain", "sg_metric_tables_release", "sg_suggest_batch_tables", "sg_suggest_batch_from", "sg_index_launch_stats", "sg_index_pipe_stats", "sg_index_pipe_volumes",
+    "sg_metric_window", "sg_metric_tables_create", "sg_metric_tables_retain", "sg_metric_tables_release", "sg_suggest_batch_tables", "sg_suggest_batch_from", "sg_index_launch_stats", "sg_index_pipe_stats", "sg_index_pipe_volumes",
     "sg_lm_score_text_batch", "sg_lm_score_text_batch_device", "sg_lm_score_word_ids_batch",
     "sg_lm_build_device", "sg_lm_store_binary", "sg_debug_lm_build_hash_bits",
     "sg_index_store_reference", "sg_dictionary_store_cdb", "sg_debug_index_store_times",
@@ -174,6 +174,7 @@ def lib():
     if hasattr(L, "sg_index_launch_stats"): L.sg_index_launch_stats.argtypes = [vp, vp]
     if hasattr(L, "sg_index_pipe_stats"): L.sg_index_pipe_stats.argtypes = [vp, vp]
     if hasattr(L, "sg_index_pipe_volumes"): L.sg_index_pipe_volumes.argtypes = [vp, vp]
+    if hasattr(L, "sg_metric_window"): L.sg_metric_window.argtypes = [i32, i32, u32, u32, vp]
     if hasattr(L, "sg_metric_tables_create"): L.sg_metric_tables_create.argtypes = [vp, u32, vp, vp, vp, vp, C.POINTER(vp)]
     if hasattr(L, "sg_metric_tables_retain"): L.sg_metric_tables_retain.argtypes = [vp]
     if hasattr(L, "sg_metric_tables_retain"): L.sg_metric_tables_retain.restype = None

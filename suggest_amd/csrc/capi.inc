@@ -1758,10 +1758,29 @@ struct sg_metric_tables {
   std::atomic<int> refs{1};
 };
 
+// The segments the reference visits for a query of `a` n-grams under a metric whose MinY / MaxY are min_y / max_y, over an index
+// of n_segments segments, as the pair the kernels take for [b_min, b_max].  suggester.go:113-121 does not walk [MinY, bMax]
+// (bMax = min(MaxY, n_segments - 1)): it sends i = a, a - 1, ... >= MinY and j = a + 1, a + 2, ... <= bMax, so with a span above
+// zero it visits [MinY, a] and [a + 1, bMax] — also a + 1 .. MinY - 1 where MinY > a + 1, and bMax + 1 .. a where bMax < a.  The
+// five metrics of pkg/metric never leave that gap; a foreign one may.  A span of zero or below is handed back untouched, so that
+// the kernels still flag it (SG_COUNT_REF_DEADLOCK / SG_COUNT_REF_PANIC).  Needs no GPU.
+int sg_metric_window(int32_t min_y, int32_t max_y, uint32_t a, uint32_t n_segments, int32_t* out) {
+  SG_GUARD_BEGIN
+  if (!out) { set_error("null argument"); return SG_E_INVALID; }
+  out[0] = min_y; out[1] = max_y;
+  const int64_t b_max = std::min<int64_t>(max_y, (int64_t)n_segments - 1);
+  if (b_max - (int64_t)min_y + 1 <= 0) return SG_OK;
+  out[0] = (int32_t)std::min<int64_t>(min_y, (int64_t)a + 1);
+  out[1] = (int32_t)std::min<int64_t>(std::max<int64_t>(b_max, a), INT32_MAX);
+  return SG_OK;
+  SG_GUARD_END(SG_RC)
+}
+
 // min_y[a], max_y[a] (a = 0 .. a_max) = Metric.MinY / MaxY(alpha, a); threshold[a * S + b] = Metric.Threshold(alpha, a, b);
 // score[(a * S + b) * (a_max + 1) + o] = 1 - Metric.Distance(o, a, b) — the double metricScorer.Score returns
-// (pkg/suggest/scorer.go:29-31) — for b = 0 .. S - 1 (S = the index's segment count, sg_index_stats), o = 0 .. a_max.  Entries
-// outside [MinY, MaxY] / above min(a, b) are never read for a query that repeats no term; fill them anyway (0 is fine).
+// (pkg/suggest/scorer.go:29-31) — for b = 0 .. S - 1 (S = the index's segment count, sg_index_stats), o = 0 .. a_max.  Every row of
+// min_y / max_y goes through sg_metric_window before the upload: fill threshold and score over THAT range of b (an entry left 0
+// is a segment that is not searched).  Entries above min(a, b) are never read for a query that repeats no term.
 int sg_metric_tables_create(sg_index* index, uint32_t a_max, const int32_t* min_y, const int32_t* max_y, const int32_t* threshold,
                             const double* score, sg_metric_tables** out) {
   SG_GUARD_BEGIN
@@ -1780,8 +1799,14 @@ int sg_metric_tables_create(sg_index* index, uint32_t a_max, const int32_t* min_
   std::unique_ptr<sg_metric_tables> t(new sg_metric_tables());   // (a step that fails below frees it, its block included)
   char* b = nullptr;
   if (int rc = t->mem.alloc(&b, total)) return rc;
-  HIP_TRY(hipMemcpy(b, min_y, n_a * 4, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(b + o_max, max_y, n_a * 4, hipMemcpyHostToDevice));
+  std::vector<int32_t> win_lo(n_a), win_hi(n_a);                 // the visited segments, not [MinY, MaxY] (sg_metric_window)
+  for (size_t a = 0; a < n_a; a++) {
+    int32_t w[2];
+    if (int rc = sg_metric_window(min_y[a], max_y[a], (uint32_t)a, S, w)) return rc;
+    win_lo[a] = w[0]; win_hi[a] = w[1];
+  }
+  HIP_TRY(hipMemcpy(b, win_lo.data(), n_a * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(b + o_max, win_hi.data(), n_a * 4, hipMemcpyHostToDevice));
   if (n_thr) HIP_TRY(hipMemcpy(b + o_thr, threshold, n_thr * 4, hipMemcpyHostToDevice));
   if (n_sc) HIP_TRY(hipMemcpy(b + o_sc, score, n_sc * 8, hipMemcpyHostToDevice));
   t->tab.min_y = (const int32_t*)b; t->tab.max_y = (const int32_t*)(b + o_max); t->tab.thr = (const int32_t*)(b + o_thr);

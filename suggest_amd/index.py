@@ -80,6 +80,41 @@ class MetricTables:
             pass
 
 
+def metric_window(min_y, max_y, a, n_segments):
+    """sg_metric_window: the segments the reference visits for a query of `a` n-grams, as one range (lo, hi) — a, a - 1, ... down
+    to MinY and a + 1, ... up to min(MaxY, n_segments - 1) (suggester.go:113-121), which is more than [MinY, MaxY] where a metric
+    puts its window beside a; the raw pair where the span is zero or below (the query stays flagged).  Needs no GPU."""
+    out = (C.c_int32 * 2)()
+    _lib.check(_lib.lib().sg_metric_window(int(min_y), int(max_y), int(a), int(n_segments), out))
+    return int(out[0]), int(out[1])
+
+
+def tabulate(metric, similarity, a_max, n_segments):
+    """-> (min_y[a_max + 1] i32, max_y[a_max + 1] i32, threshold[a_max + 1, S] i32, score[a_max + 1, S, a_max + 1] f64): `metric`
+    (any object with the four methods of metric.Metric) at `similarity` as sg_metric_tables_create takes it.  MinY / MaxY are
+    the metric's own, clamped to 32 bits; Threshold and 1 - Distance are filled over the segments the reference VISITS
+    (metric_window), 0 elsewhere.  Pure: no GPU, no index."""
+    m = resolve(metric)
+    S = int(n_segments)
+    alpha = float(similarity)
+    n_a = int(a_max) + 1
+    i32 = lambda v: int(max(-2**31, min(2**31 - 1, v)))                                  # noqa: E731
+    min_y = np.array([i32(m.MinY(alpha, a)) for a in range(n_a)], dtype=np.int32)
+    max_y = np.array([i32(m.MaxY(alpha, a)) for a in range(n_a)], dtype=np.int32)
+    thr = np.zeros((n_a, S), dtype=np.int32)
+    score = np.zeros((n_a, S, n_a), dtype=np.float64)
+    for a in range(1, n_a):
+        lo, hi = metric_window(min_y[a], max_y[a], a, S)
+        for b in range(max(0, lo), min(S - 1, hi) + 1):
+            thr[a, b] = i32(m.Threshold(alpha, a, b))
+            for o in range(max(0, int(thr[a, b])), a + 1):          # (a query that repeats a term: overlaps up to a)
+                try:
+                    score[a, b, o] = 1 - m.Distance(o, a, b)          # metricScorer.Score, pkg/suggest/scorer.go:29-31
+                except ZeroDivisionError:
+                    score[a, b, o] = float("nan")
+    return min_y, max_y, thr, score
+
+
 def _max_terms(offs, description):
     """upper bound of the n-grams of the longest query of a batch (bytes + wrap runes)"""
     longest = int((offs[1:] - offs[:-1]).max()) if len(offs) > 1 else 0
@@ -362,24 +397,8 @@ class NGramIndex:
         """MinY / MaxY / Threshold / 1 - Distance of `metric` (any object with the four methods of metric.Metric,
         pkg/metric/metric.go:7-16) at `similarity`, tabulated for queries of up to a_max n-grams and uploaded
         (sg_metric_tables_create).  Reusable across calls; released with the object."""
-        m = resolve(metric)
         a_max = int(max(1, a_max))
-        S = int(self.stats()["n_segments"])
-        alpha = float(similarity)
-        n_a = a_max + 1
-        i32 = lambda v: int(max(-2**31, min(2**31 - 1, v)))                                  # noqa: E731
-        min_y = np.array([i32(m.MinY(alpha, a)) for a in range(n_a)], dtype=np.int32)
-        max_y = np.array([i32(m.MaxY(alpha, a)) for a in range(n_a)], dtype=np.int32)
-        thr = np.zeros((n_a, S), dtype=np.int32)
-        score = np.zeros((n_a, S, n_a), dtype=np.float64)
-        for a in range(1, n_a):
-            for b in range(max(0, int(min_y[a])), min(S - 1, int(max_y[a])) + 1):
-                thr[a, b] = i32(m.Threshold(alpha, a, b))
-                for o in range(max(0, int(thr[a, b])), a + 1):          # (a query that repeats a term: overlaps up to a)
-                    try:
-                        score[a, b, o] = 1 - m.Distance(o, a, b)          # metricScorer.Score, pkg/suggest/scorer.go:29-31
-                    except ZeroDivisionError:
-                        score[a, b, o] = float("nan")
+        min_y, max_y, thr, score = tabulate(metric, similarity, a_max, int(self.stats()["n_segments"]))
         t = C.c_void_p()
         with self._use() as h:
             _lib.check(_lib.lib().sg_metric_tables_create(h, a_max, min_y.ctypes.data, max_y.ctypes.data, thr.ctypes.data, score.ctypes.data, C.byref(t)))
