@@ -1275,6 +1275,142 @@ func StoreCDBDictionary(lines []string, cdbPath string) error {
 	})
 }
 
+// DeviceDictionary is a dictionary.Dictionary's content — docID -> line — held in the HBM of one GPU (sg_dictionary): the rows
+// of a search become strings there, one blob per call in place of a Get per candidate.  Close releases it.
+type DeviceDictionary struct {
+	mu     sync.RWMutex
+	h      *C.sg_dictionary
+	closed bool
+}
+
+// NewDeviceDictionary uploads lines (docID = position) to `device`; device < 0 makes a host-resident handle.
+func NewDeviceDictionary(lines []string, device int) (*DeviceDictionary, error) {
+	var blob []byte
+	offs := make([]C.uint64_t, 1, len(lines)+1)
+	for _, l := range lines {
+		blob = append(blob, l...)
+		offs = append(offs, C.uint64_t(len(blob)))
+	}
+	var bp *C.uint8_t
+	if len(blob) > 0 {
+		bp = (*C.uint8_t)(unsafe.Pointer(&blob[0]))
+	}
+	d := &DeviceDictionary{}
+	if err := ccall(func() C.int {
+		return C.sg_dictionary_upload(bp, &offs[0], C.uint32_t(len(lines)), C.int(device), &d.h)
+	}); err != nil {
+		return nil, err
+	}
+	runtime.SetFinalizer(d, func(d *DeviceDictionary) { d.Close() })
+	return d, nil
+}
+
+// OpenDeviceCDBDictionary opens the <name>.cdb of dictionary.BuildCDBDictionary / StoreCDBDictionary on `device`.
+func OpenDeviceCDBDictionary(cdbPath string, device int) (*DeviceDictionary, error) {
+	cp := C.CString(cdbPath)
+	defer C.free(unsafe.Pointer(cp))
+	d := &DeviceDictionary{}
+	if err := ccall(func() C.int {
+		return C.sg_dictionary_open_cdb(cp, C.int(device), &d.h)
+	}); err != nil {
+		return nil, err
+	}
+	runtime.SetFinalizer(d, func(d *DeviceDictionary) { d.Close() })
+	return d, nil
+}
+
+// Size is Dictionary.Size.
+func (d *DeviceDictionary) Size() int { return int(C.sg_dictionary_size(d.h)) }
+
+// Close drops the caller's reference; calls in flight keep theirs.
+func (d *DeviceDictionary) Close() {
+	d.mu.Lock()
+	if !d.closed {
+		d.closed = true
+		C.sg_dictionary_release(d.h)
+	}
+	d.mu.Unlock()
+}
+
+// SuggestStrings is SuggestBatch with the candidates' lines: values[q][j] is the line of cands[q][j], gathered on the device
+// from dict (sg_suggest_batch_strings).  dict must live on the device of the index's primary replica.
+func (i *Index) SuggestStrings(dict *DeviceDictionary, queries []string, similarity float64, m metric.Metric, k int) (cands [][]suggest.Candidate, values [][]string, status []uint32, err error) {
+	code, known := metricCode(m)
+	if !known {
+		return nil, nil, nil, errors.New("SuggestStrings: a metric without a device twin (use SuggestBatch)")
+	}
+	n := len(queries)
+	if n == 0 || k <= 0 {
+		return nil, nil, nil, nil
+	}
+	var blob []byte
+	offs := make([]C.uint64_t, 1, n+1)
+	for _, q := range queries {
+		blob = append(blob, q...)
+		offs = append(offs, C.uint64_t(len(blob)))
+	}
+	var bp *C.uint8_t
+	if len(blob) > 0 {
+		bp = (*C.uint8_t)(unsafe.Pointer(&blob[0]))
+	}
+	ids := make([]C.uint32_t, n*k)
+	scores := make([]C.double, n*k)
+	counts := make([]C.uint32_t, n)
+	textOffs := make([]C.uint64_t, n*k+1)
+	dict.mu.RLock()
+	if dict.closed {
+		dict.mu.RUnlock()
+		return nil, nil, nil, errClosed
+	}
+	C.sg_dictionary_retain(dict.h)
+	dict.mu.RUnlock()
+	defer func() { C.sg_dictionary_release(dict.h); runtime.KeepAlive(dict) }()
+	e := i.e
+	if err = e.retain(); err != nil {
+		return nil, nil, nil, err
+	}
+	defer func() { e.release(); runtime.KeepAlive(i) }()
+	textCap := uint64(n*k) * uint64(C.sg_dictionary_max_len(dict.h))
+	if textCap > 1<<20 && textCap > uint64(64*n*k) { // a first guess; a call that needs more says how much
+		textCap = uint64(64 * n * k)
+	}
+	var text []byte
+	var needed C.uint64_t
+	for try := 0; ; try++ {
+		text = make([]byte, textCap+1)
+		tp := (*C.uint8_t)(unsafe.Pointer(&text[0]))
+		err = ccall(func() C.int {
+			return C.sg_suggest_batch_strings(e.h, bp, &offs[0], C.uint32_t(n), code, C.double(similarity), C.uint32_t(k), &ids[0], &scores[0], &counts[0], dict.h, tp, C.uint64_t(textCap), &textOffs[0], &needed)
+		})
+		if err != nil && try == 0 && uint64(needed) > textCap && textOffs[n*k] == needed {
+			textCap = uint64(needed)
+			continue
+		}
+		break
+	}
+	if err != nil {
+		return nil, nil, nil, err
+	}
+	cands = make([][]suggest.Candidate, n)
+	values = make([][]string, n)
+	status = make([]uint32, n)
+	for q := 0; q < n; q++ {
+		c := uint32(counts[q])
+		if c >= C.SG_COUNT_LM_ERROR { // an SG_COUNT_* flag: no row
+			status[q] = c
+			continue
+		}
+		cands[q] = make([]suggest.Candidate, c)
+		values[q] = make([]string, c)
+		for j := 0; j < int(c); j++ {
+			s := q*k + j
+			cands[q][j] = suggest.Candidate{Key: uint32(ids[s]), Score: float64(scores[s])}
+			values[q][j] = string(text[textOffs[s]:textOffs[s+1]])
+		}
+	}
+	return cands, values, status, nil
+}
+
 // StoreBinary writes the spellchecker's language model as the <name>.lm / <name>.cdb pair `lm build-lm` leaves behind
 // (StoreBinaryLM, pkg/lm/binary.go:18-57).  mph adds the minimal perfect hash RetrieveLMFromBinary reads after the model
 // (pkg/mph/mph.go): the file the reference's spellchecker service opens (sg_lm_store_binary_ex).

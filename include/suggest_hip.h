@@ -598,6 +598,60 @@ int sg_debug_coalesce_stats(sg_index* index, uint64_t out[4]);
 int sg_debug_mixed_timing(int on);
 int sg_debug_mixed_times(double out_ms[5]);
 
+/* Result rows as strings.  sg_dictionary is the reference's dictionary.Dictionary — docID -> string, docID = line
+ * number — as an immutable, reference-counted handle.  With device >= 0 it lives in the HBM of that GPU as doc_offs[n_docs + 1]
+ * (u64) and the blob, and the rows of any search are turned into strings there; with device < 0 it is host-resident, needs no GPU,
+ * and sg_dictionary_rows is the plain host loop (the reference's Service.Suggest, pkg/suggest/service.go:129-136).
+ *
+ * sg_dictionary_upload takes the (blob, n_docs + 1 u64 offsets) pair of sg_index_build; the offsets may start anywhere and must
+ * not decrease.  sg_dictionary_open_cdb reads the <name>.cdb that BuildCDBDictionary / sg_dictionary_store_cdb writes (key =
+ * docID as 4 bytes little endian); a truncated or corrupted file or a hole in the ids is refused (invalid argument).
+ * Limits: n_docs <= 2^32 - 1; one string is shorter than 4 GiB; every offset and every sum of lengths is 64-bit; the CDB route
+ * inherits the format's 4 GiB.  sg_dictionary_bytes: the bytes of all strings; sg_dictionary_max_len: the longest string, so a
+ * caller can bound a text buffer by slots * max_len.
+ *
+ * The materialise step.  In: id rows, counts[n_rows] and a row geometry — a fixed stride `row` (row_offs null; row i holds slots
+ * i * row .. i * row + row) or ragged row_offs[n_rows + 1] as sg_suggest_batch_mixed returns it (`row` unused).  `slots`: the
+ * slots of `ids` in all (fixed stride: at least n_rows * row).  Out: text_offs[slots + 1] (u64) and text; the string of slot s is
+ * text[text_offs[s] .. text_offs[s + 1]), slots laid out exactly as the id rows are — the form of a query batch or a dictionary.
+ * Row i has min(counts[i], its length) entries; counts[i] >= 0xFFFFFFF0 is a SG_COUNT_* flag: no entries.  Every other slot —
+ * past the count, in a flagged row, in no ragged row — has length 0 and its id is never read.  An entry whose id is >= n_docs has
+ * length 0 and is counted.  A string that would end past text_cap is not written; text_offs is complete whatever text_cap is, so
+ * a caller can size a retry.
+ *
+ * sg_dictionary_rows_device: device pointers, asynchronous on `stream`, writes nothing of the handle, callable from any number of
+ * threads.  d_info: two u64 — [0] the bytes the text needs, [1] the entries with an id outside the dictionary.  A host-resident
+ * handle is refused (unsupported).
+ * sg_dictionary_rows: host buffers; uploads ids and counts, returns the strings.  *needed (may be null) = the bytes the text
+ * needs.  Invalid argument: an id outside the dictionary ("docID outside the dictionary" — the reference's dict.Get fails there
+ * too), needed > text_cap ("text buffer too small": *needed and text_offs are set), null pointers.
+ * sg_suggest_batch_strings / sg_autocomplete_batch_strings: sg_suggest_batch / sg_autocomplete_batch whose rows go from the search
+ * to the gather without visiting the host; text_offs has n_q * k + 1 entries.  ids, scores and counts are bit for bit the plain
+ * call's and are delivered also when the text is refused.  The call waits for the device twice (the total, then rows and text)
+ * and holds no more device memory for text than text_cap.  The dictionary must be on the device of the index's primary replica,
+ * else unsupported. */
+typedef struct sg_dictionary sg_dictionary;
+int sg_dictionary_upload(const uint8_t* utf8, const uint64_t* offs, uint32_t n_docs, int device, sg_dictionary** out);
+int sg_dictionary_open_cdb(const char* cdb_path, int device, sg_dictionary** out);
+void sg_dictionary_retain(sg_dictionary* dict);
+void sg_dictionary_release(sg_dictionary* dict);
+uint32_t sg_dictionary_size(const sg_dictionary* dict);
+uint64_t sg_dictionary_bytes(const sg_dictionary* dict);
+uint32_t sg_dictionary_max_len(const sg_dictionary* dict);
+int sg_dictionary_device(const sg_dictionary* dict);       /* -1: host-resident */
+int sg_dictionary_rows_device(sg_dictionary* dict, const void* d_ids, const void* d_counts, const void* d_row_offs_or_null,
+                              uint32_t n_rows, uint32_t row, uint64_t slots, void* d_text, uint64_t text_cap, void* d_text_offs,
+                              void* d_info, void* stream);
+int sg_dictionary_rows(sg_dictionary* dict, const uint32_t* ids, const uint32_t* counts, const uint64_t* row_offs_or_null,
+                       uint32_t n_rows, uint32_t row, uint64_t slots, uint8_t* text, uint64_t text_cap, uint64_t* text_offs,
+                       uint64_t* needed);
+int sg_suggest_batch_strings(sg_index* index, const uint8_t* q_utf8, const uint64_t* q_offs, uint32_t n_q, int metric,
+                             double similarity, uint32_t k, uint32_t* out_ids, double* out_scores, uint32_t* out_counts,
+                             sg_dictionary* dict, uint8_t* text, uint64_t text_cap, uint64_t* text_offs, uint64_t* needed);
+int sg_autocomplete_batch_strings(sg_index* index, const uint8_t* q_utf8, const uint64_t* q_offs, uint32_t n_q, uint32_t limit,
+                                  uint32_t* out_ids, uint32_t* out_counts, sg_dictionary* dict, uint8_t* text, uint64_t text_cap,
+                                  uint64_t* text_offs, uint64_t* needed);
+
 /* Sets a tuning knob of the index, before or after its first upload: SG_LOG2_CNT, SG_T_FLOOR, SG_FILTER_LEVEL, SG_TIGHTEN, SG_ROOMY,
  * SG_ORDER, SG_PRETOK, SG_SPLIT_CHUNKS, SG_PARTS_CNT_BONUS; the pipeline's SG_PIPE, SG_PIPE_SUB, SG_PIPE_CAND_CAP, SG_PIPE_WIDE,
  * SG_PLAN2.  SG_PIPE_NW, SG_PIPE_LOG2_CNT and SG_PIPE_DT_BYTES freeze the stream workgroup's shape for every launch;

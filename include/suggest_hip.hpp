@@ -145,6 +145,68 @@ inline std::shared_ptr<Dictionary> OpenCDBDictionary(const std::string& path) {
     if (kv.first < words.size()) words[kv.first] = kv.second;
   return NewInMemoryDictionary(std::move(words));
 }
+
+// A dictionary held in the HBM of one GPU (sg_dictionary; device < 0: host-resident, no GPU needed).  It is a Dictionary — Get
+// and Size work, a Get is a one-slot Rows — and Rows turns the id rows of any search into strings on the device: slot s of
+// the rows is text.substr(text_offs[s], text_offs[s + 1] - text_offs[s]).
+class DeviceDictionary : public Dictionary {
+ public:
+  DeviceDictionary(const std::vector<std::string>& words, int device) {
+    std::string blob;
+    std::vector<uint64_t> offs(1, 0);
+    for (auto& w : words) { blob += w; offs.push_back(blob.size()); }
+    Check(sg_dictionary_upload((const uint8_t*)blob.data(), offs.data(), (uint32_t)words.size(), device, &h_));
+  }
+  DeviceDictionary(const Dictionary& from, int device) {
+    std::string blob;
+    std::vector<uint64_t> offs(1, 0);
+    from.Iterate([&](Key, const Value& w) { blob += w; offs.push_back(blob.size()); });
+    Check(sg_dictionary_upload((const uint8_t*)blob.data(), offs.data(), (uint32_t)(offs.size() - 1), device, &h_));
+  }
+  explicit DeviceDictionary(sg_dictionary* adopted) : h_(adopted) {}
+  static std::shared_ptr<DeviceDictionary> OpenCDB(const std::string& path, int device) {   // OpenCDBDictionary, read by the library
+    sg_dictionary* h = nullptr;
+    Check(sg_dictionary_open_cdb(path.c_str(), device, &h));
+    return std::make_shared<DeviceDictionary>(h);
+  }
+  DeviceDictionary(const DeviceDictionary&) = delete;
+  DeviceDictionary& operator=(const DeviceDictionary&) = delete;
+  ~DeviceDictionary() override { sg_dictionary_release(h_); }
+
+  Value Get(Key key) const override {
+    if (key >= sg_dictionary_size(h_)) throw Error("key is not exists");
+    const uint32_t one = 1;
+    std::vector<uint64_t> text_offs;
+    return Rows(&key, &one, nullptr, 1, 1, 1, text_offs);
+  }
+  size_t Size() const override { return sg_dictionary_size(h_); }
+  void Iterate(const Iterator& it) const override {
+    for (size_t i = 0; i < Size(); i++) it((Key)i, Get((Key)i));
+  }
+  int Device() const { return sg_dictionary_device(h_); }
+  sg_dictionary* Handle() const { return h_; }
+  // sg_dictionary_rows: row_offs null: n_rows rows of `row` slots; else ragged rows as sg_suggest_batch_mixed returns them
+  std::string Rows(const uint32_t* ids, const uint32_t* counts, const uint64_t* row_offs, uint32_t n_rows, uint32_t row, uint64_t slots,
+                   std::vector<uint64_t>& text_offs) const {
+    text_offs.assign(slots + 1, 0);
+    std::string text((size_t)std::min<uint64_t>(slots * sg_dictionary_max_len(h_), std::max<uint64_t>(65536, 64 * slots)), '\0');
+    uint64_t needed = 0;
+    int rc = sg_dictionary_rows(h_, ids, counts, row_offs, n_rows, row, slots, (uint8_t*)&text[0], text.size(), text_offs.data(), &needed);
+    if (rc != SG_OK && needed > text.size() && text_offs[slots] == needed) {   // the text was too small: the call says how much it takes
+      text.assign((size_t)needed, '\0');
+      rc = sg_dictionary_rows(h_, ids, counts, row_offs, n_rows, row, slots, (uint8_t*)&text[0], text.size(), text_offs.data(), &needed);
+    }
+    Check(rc);
+    text.resize((size_t)needed);
+    return text;
+  }
+
+ private:
+  static void Check(int rc) {
+    if (rc != SG_OK) throw Error(sg_last_error());
+  }
+  sg_dictionary* h_ = nullptr;
+};
 }  // namespace dictionary
 
 // ---------------------------------------------------------------------------------------------
@@ -786,11 +848,33 @@ class Service {
     std::shared_ptr<NGramIndex> ix;
     std::shared_ptr<dictionary::Dictionary> dict;
     Lookup(dictName, ix, dict);
+    if (auto* dd = dynamic_cast<const dictionary::DeviceDictionary*>(dict.get())) return SuggestMany(*ix, configs, *dd);
     std::vector<std::vector<ResultItem>> out;
     for (auto& row : ix->SuggestMany(configs)) {
       out.emplace_back();
       for (const Candidate& c : row) out.back().push_back(ResultItem{c.Score, dict->Get(c.Key)});
     }
+    return out;
+  }
+  // ... with the values gathered by the dictionary's device (the generic materialise step behind the mixed call): one blob for
+  // the call, no Get per candidate.  What Service::SuggestMany does where the index's dictionary is a DeviceDictionary.
+  static std::vector<std::vector<ResultItem>> SuggestMany(const NGramIndex& ix, const std::vector<SearchConfig>& configs,
+                                                          const dictionary::DeviceDictionary& dict) {
+    const std::vector<std::vector<Candidate>> rows = ix.SuggestMany(configs);
+    std::vector<uint32_t> ids, counts;
+    std::vector<uint64_t> row_offs(1, 0), text_offs;
+    for (auto& row : rows) {
+      for (const Candidate& c : row) ids.push_back(c.Key);
+      counts.push_back((uint32_t)row.size());
+      row_offs.push_back(ids.size());
+    }
+    const std::string text = dict.Rows(ids.data(), counts.data(), row_offs.data(), (uint32_t)rows.size(), 0, ids.size(), text_offs);
+    std::vector<std::vector<ResultItem>> out(rows.size());
+    for (size_t i = 0; i < rows.size(); i++)
+      for (size_t j = 0; j < rows[i].size(); j++) {
+        const uint64_t s = row_offs[i] + j;
+        out[i].push_back(ResultItem{rows[i][j].Score, text.substr((size_t)text_offs[s], (size_t)(text_offs[s + 1] - text_offs[s]))});
+      }
     return out;
   }
 

@@ -37,6 +37,9 @@ EXPORTS = [
     "sg_debug_index_build_table_bits", "sg_debug_index_build_report",
     "sg_suggest_batch_mixed", "sg_suggest_batch_mixed_device", "sg_coalesce_mixed", "sg_debug_mixed_last", "sg_debug_coalesce_hold",
     "sg_debug_coalesce_stats", "sg_debug_mixed_timing", "sg_debug_mixed_times",
+    "sg_dictionary_upload", "sg_dictionary_open_cdb", "sg_dictionary_retain", "sg_dictionary_release", "sg_dictionary_size", "sg_dictionary_bytes",
+    "sg_dictionary_max_len", "sg_dictionary_device", "sg_dictionary_rows_device", "sg_dictionary_rows", "sg_suggest_batch_strings",
+    "sg_autocomplete_batch_strings",
 ]
 SG_MAX_MIXED_CONFIGS = 256
 SG_MAX_SHARDS = 64
@@ -204,6 +207,23 @@ def lib():
     if hasattr(L, "sg_debug_coalesce_stats"): L.sg_debug_coalesce_stats.argtypes = [vp, vp]
     if hasattr(L, "sg_debug_mixed_timing"): L.sg_debug_mixed_timing.argtypes = [i32]
     if hasattr(L, "sg_debug_mixed_times"): L.sg_debug_mixed_times.argtypes = [vp]
+    if hasattr(L, "sg_dictionary_upload"): L.sg_dictionary_upload.argtypes = [vp, vp, u32, i32, C.POINTER(vp)]
+    if hasattr(L, "sg_dictionary_open_cdb"): L.sg_dictionary_open_cdb.argtypes = [C.c_char_p, i32, C.POINTER(vp)]
+    if hasattr(L, "sg_dictionary_retain"): L.sg_dictionary_retain.argtypes = [vp]
+    if hasattr(L, "sg_dictionary_retain"): L.sg_dictionary_retain.restype = None
+    if hasattr(L, "sg_dictionary_release"): L.sg_dictionary_release.argtypes = [vp]
+    if hasattr(L, "sg_dictionary_release"): L.sg_dictionary_release.restype = None
+    if hasattr(L, "sg_dictionary_size"): L.sg_dictionary_size.argtypes = [vp]
+    if hasattr(L, "sg_dictionary_size"): L.sg_dictionary_size.restype = u32
+    if hasattr(L, "sg_dictionary_bytes"): L.sg_dictionary_bytes.argtypes = [vp]
+    if hasattr(L, "sg_dictionary_bytes"): L.sg_dictionary_bytes.restype = u64
+    if hasattr(L, "sg_dictionary_max_len"): L.sg_dictionary_max_len.argtypes = [vp]
+    if hasattr(L, "sg_dictionary_max_len"): L.sg_dictionary_max_len.restype = u32
+    if hasattr(L, "sg_dictionary_device"): L.sg_dictionary_device.argtypes = [vp]
+    if hasattr(L, "sg_dictionary_rows_device"): L.sg_dictionary_rows_device.argtypes = [vp, vp, vp, vp, u32, u32, u64, vp, u64, vp, vp, vp]
+    if hasattr(L, "sg_dictionary_rows"): L.sg_dictionary_rows.argtypes = [vp, vp, vp, vp, u32, u32, u64, vp, u64, vp, C.POINTER(u64)]
+    if hasattr(L, "sg_suggest_batch_strings"): L.sg_suggest_batch_strings.argtypes = [vp, vp, vp, u32, i32, dbl, u32, vp, vp, vp, vp, vp, u64, vp, C.POINTER(u64)]
+    if hasattr(L, "sg_autocomplete_batch_strings"): L.sg_autocomplete_batch_strings.argtypes = [vp, vp, vp, u32, u32, vp, vp, vp, vp, u64, vp, C.POINTER(u64)]
     _lib = L
     return L
 

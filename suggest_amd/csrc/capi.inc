@@ -112,6 +112,19 @@ int device_exclusive_sum(DeviceBlock& mem, const T* in, T* out, size_t n, hipStr
   HIP_TRY(hipcub::DeviceScan::ExclusiveSum(tmp, tb, in, out, (int)n, st));
   return SG_OK;
 }
+// ... over working memory the caller holds already (a call on a caller's stream takes it from its scratch block: nothing is
+// allocated or freed while the stream runs): exclusive_sum_bytes says how much a scan of n elements needs
+template <class T>
+int exclusive_sum_bytes(size_t n, size_t* bytes) {
+  *bytes = 0;
+  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, *bytes, (const T*)nullptr, (T*)nullptr, (int)n, (hipStream_t) nullptr));
+  return SG_OK;
+}
+template <class T>
+int device_exclusive_sum(void* tmp, size_t tmp_bytes, const T* in, T* out, size_t n, hipStream_t st) {
+  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(tmp, tmp_bytes, in, out, (int)n, st));
+  return SG_OK;
+}
 template <class K, class V>   // stable, ascending by bits [begin_bit, end_bit) of the keys
 int device_sort_pairs(DeviceBlock& mem, const K* keys_in, K* keys_out, const V* vals_in, V* vals_out, size_t n, int begin_bit = 0,
                       int end_bit = 8 * (int)sizeof(K), hipStream_t st = nullptr) {
@@ -423,9 +436,10 @@ struct GrowBlock {
 // once, and Predict's block besides when Predict is the caller — four at most.  Sentence scoring (lm_score.inc) holds its own
 // block alone.  A sharded search (shard_merge.inc) holds SCRATCH_SHARD, the shards' rows, around its launches.
 // A mixed call (mixed_batch.inc) holds SCRATCH_MIXED, its lists and offsets, and SCRATCH_MIXED_ROWS, the grouped queries and the
-// groups' rows, around its launches.
+// groups' rows, around its launches.  The materialise step (dict_rows.inc) holds SCRATCH_DICT, its lengths and the scan's working
+// memory, until its gather launch is enqueued.
 enum ScratchTag { SCRATCH_ROWS = 0, SCRATCH_PREDICT = 1, SCRATCH_LONG_LIST = 2, SCRATCH_PRETOK = 3, SCRATCH_PIPE = 4, SCRATCH_LM_SCORE = 5, SCRATCH_SHARD = 6,
-                  SCRATCH_MIXED = 7, SCRATCH_MIXED_ROWS = 8 };
+                  SCRATCH_MIXED = 7, SCRATCH_MIXED_ROWS = 8, SCRATCH_DICT = 9 };
 struct ScratchSlot { int device; hipStream_t stream; int tag; GrowBlock blk; bool held = false; };
 inline bool on_main_thread() { return (long)getpid() == (long)syscall(SYS_gettid); }
 // (a thread that ends hands its buffers back; the main thread's are left to process exit, when the HIP runtime may already
@@ -1482,13 +1496,15 @@ static void thread_contexts_release() {
 // The device block of a host-buffer call: [scores | ids | counts | aux] — the results, one copy back — then, from the next 16
 // bytes on, [offsets | queries] — the inputs, one copy in.  Offsets and sizes in bytes.  Predict: id rows of topK + 1, counts.
 // A mixed call (mixed_batch.inc): ragged rows — `rows` slots in all in place of n_q * k — and, behind the queries, its [n_q] list
-// of config numbers (sel); a fixed-k call has neither and lies exactly as it did.
+// of config numbers (sel); a fixed-k call has neither and lies exactly as it did.  A strings call (dict_rows.inc): behind the
+// result rows, still inside the one copy back, the slots + 1 text offsets (toffs); the text itself is not part of this block.
 struct IoLayout {
-  size_t sc_bytes = 0, id_bytes = 0, cnt_bytes = 0, aux_bytes = 0, off_bytes = 0, q_bytes = 0, sel_bytes = 0;
-  size_t ids = 0, cnt = 0, aux = 0, out_bytes = 0, offs = 0, q = 0, sel = 0, in_bytes = 0, total = 0;   // (the scores start the block)
+  size_t sc_bytes = 0, id_bytes = 0, cnt_bytes = 0, aux_bytes = 0, toffs_bytes = 0, off_bytes = 0, q_bytes = 0, sel_bytes = 0;
+  size_t ids = 0, cnt = 0, aux = 0, toffs = 0, out_bytes = 0, offs = 0, q = 0, sel = 0, in_bytes = 0, total = 0;   // (the scores start the block)
 };
 constexpr uint64_t kRowsFixed = ~0ull;      // HostBufs::rows of a fixed-k call: n_q * row
-static IoLayout io_layout(uint32_t n_q, uint32_t k, bool scores, bool aux, size_t q_bytes, uint64_t rows = kRowsFixed, bool sel = false) {
+static IoLayout io_layout(uint32_t n_q, uint32_t k, bool scores, bool aux, size_t q_bytes, uint64_t rows = kRowsFixed, bool sel = false,
+                          bool text = false) {
   IoLayout L;
   const size_t slots = rows == kRowsFixed ? (size_t)n_q * k : (size_t)rows;
   L.sc_bytes = scores ? slots * 8 : 0; L.id_bytes = slots * 4; L.cnt_bytes = (size_t)n_q * 4;
@@ -1496,6 +1512,7 @@ static IoLayout io_layout(uint32_t n_q, uint32_t k, bool scores, bool aux, size_
   Carve c;
   c.take(L.sc_bytes);
   L.ids = c.take(L.id_bytes, 4); L.cnt = c.take(L.cnt_bytes, 4); L.aux = c.take(L.aux_bytes, 4);
+  if (text) { L.toffs_bytes = (slots + 1) * 8; L.toffs = c.take(L.toffs_bytes + 16, 8); }   // (+ the step's two info words)
   L.out_bytes = c.off;
   L.offs = c.take(L.off_bytes); L.q = c.take(q_bytes, 8);
   if (sel) { L.sel_bytes = (size_t)n_q * 4; L.sel = c.take(L.sel_bytes, 4); }
@@ -1539,6 +1556,7 @@ struct HostBufs {
   uint32_t* ids = nullptr; double* scores = nullptr; uint32_t* counts = nullptr; uint32_t* aux = nullptr;
   uint64_t rows = kRowsFixed;          // a mixed call: the slots of its ragged ids / scores rows in all (`row` unused)
   const uint32_t* sel = nullptr;       // ... and its [n_q] config numbers, staged and copied in with the queries
+  uint64_t* text_offs = nullptr;       // a strings call: the slots + 1 text offsets its enqueue step leaves at IoLayout::toffs
 };
 // What a call runs on.  A synchronous call: the calling thread's HostCtx — one stream for everything, no events, one staging
 // buffer both ways, staging up to kPinnedMax.  A ticket: its AsyncSlot — the copy-in, run and copy-out streams of the replica's
@@ -1566,7 +1584,8 @@ using Enqueue = std::function<int(char* dev, const IoLayout& io, hipStream_t st)
 static int begin_host_call(const HostBufs& b, bool clear_rows, const Enqueue& enqueue, const IoCtx& x, HostCall* c) {
   const uint64_t q0 = b.offs[0];
   if (!b.q && b.offs[b.n_q] != q0) { set_error("null query buffer"); return SG_E_INVALID; }
-  const IoLayout io = io_layout(b.n_q, b.row, b.scores != nullptr, b.aux != nullptr, (size_t)(b.offs[b.n_q] - q0), b.rows, b.sel != nullptr);
+  const IoLayout io = io_layout(b.n_q, b.row, b.scores != nullptr, b.aux != nullptr, (size_t)(b.offs[b.n_q] - q0), b.rows, b.sel != nullptr,
+                                 b.text_offs != nullptr);
   // the routes.  A ticket: caller memory from sg_host_alloc where it lies, the rest staged.  A synchronous call: staged both ways
   // while it fits kPinnedMax, else straight from / to the caller's memory — but offsets that do not start at zero (a slice of a
   // larger batch) are rebased in the staging buffer.
@@ -1621,7 +1640,7 @@ static int begin_host_call(const HostBufs& b, bool clear_rows, const Enqueue& en
                      (uintptr_t)(dev + io.ids) | (uintptr_t)(dev + io.cnt)) % 16 == 0;
   if (out_staged) {
     HIP_TRY(hipMemcpyAsync(x.pin_out->p, dev, io.out_bytes, hipMemcpyDeviceToHost, x.out));
-  } else if (out_pinned && al16 && !b.aux) {
+  } else if (out_pinned && al16 && !b.aux && !b.text_offs) {
     // (sg_host_alloc memory: a kernel's stores, not hipMemcpyAsync — see host_store_kernel; 16-byte pieces — the device block's
     //  regions are, the caller's pinned arrays usually are; anything else takes the runtime's copies)
     HostStoreArgs h{};
@@ -1635,6 +1654,7 @@ static int begin_host_call(const HostBufs& b, bool clear_rows, const Enqueue& en
     HIP_TRY(hipMemcpyAsync(b.ids, dev + io.ids, io.id_bytes, hipMemcpyDeviceToHost, x.out));
     HIP_TRY(hipMemcpyAsync(b.counts, dev + io.cnt, io.cnt_bytes, hipMemcpyDeviceToHost, x.out));
     if (io.aux_bytes) HIP_TRY(hipMemcpyAsync(b.aux, dev + io.aux, io.aux_bytes, hipMemcpyDeviceToHost, x.out));
+    if (io.toffs_bytes) HIP_TRY(hipMemcpyAsync(b.text_offs, dev + io.toffs, io.toffs_bytes, hipMemcpyDeviceToHost, x.out));
   }
   if (x.ev_out) HIP_TRY(hipEventRecord(x.ev_out, x.out));
   drain.armed = false;
@@ -1659,6 +1679,7 @@ static int finish_host_call(const HostCall& c) {
   copy_out(c.b.ids, c.staged + io.ids, io.id_bytes);
   memcpy(c.b.counts, c.staged + io.cnt, io.cnt_bytes);
   if (io.aux_bytes) copy_out(c.b.aux, c.staged + io.aux, io.aux_bytes);
+  if (io.toffs_bytes) copy_out(c.b.text_offs, c.staged + io.toffs, io.toffs_bytes);
   return SG_OK;
 }
 

@@ -250,6 +250,21 @@ __device__ __forceinline__ int wave_min_i32(int v) {
   return (int)readlane((uint32_t)v, 63);
 }
 
+// `lanes` lanes (this one is number `sub`) copy src[0 .. n) to dst[0 .. n).  Where source and destination share their position
+// within 16 (8, 4) bytes the middle goes in pieces of that size, the ragged ends byte by byte; where they share none, every byte
+// on its own.  The byte copy of mixed_gather_kernel (a query to its grouped position) and dict_gather_kernel (a string to its slot).
+__device__ __forceinline__ void d_copy_bytes(uint8_t* dst, const uint8_t* src, uint32_t n, uint32_t sub, uint32_t lanes) {
+  const uint32_t apart = (uint32_t)((uintptr_t)src ^ (uintptr_t)dst);
+  const uint32_t w = (apart & 15u) == 0u ? 16u : (apart & 7u) == 0u ? 8u : (apart & 3u) == 0u ? 4u : 1u;
+  const uint32_t head = w == 1u ? n : min(n, (uint32_t)((0u - (uint32_t)(uintptr_t)dst) & (w - 1u)));   // bytes up to the first whole piece
+  const uint32_t pieces = (n - head) / w;
+  for (uint32_t b = sub; b < head; b += lanes) dst[b] = src[b];
+  if (w == 16u) for (uint32_t p = sub; p < pieces; p += lanes) ((uint4*)(dst + head))[p] = ((const uint4*)(src + head))[p];
+  else if (w == 8u) for (uint32_t p = sub; p < pieces; p += lanes) ((uint2*)(dst + head))[p] = ((const uint2*)(src + head))[p];
+  else if (w == 4u) for (uint32_t p = sub; p < pieces; p += lanes) ((uint32_t*)(dst + head))[p] = ((const uint32_t*)(src + head))[p];
+  for (uint32_t b = head + pieces * w + sub; b < n; b += lanes) dst[b] = src[b];
+}
+
 // pkg/metric — IEEE binary64, Go's evaluation order; built with -ffp-contract=off
 __device__ double d_floor_div_clamp(double x, double hi) { double f = floor(x); return f > hi ? hi : f; }
 __device__ __forceinline__ int d_min_y(int m, double alpha, int size, const MetricTab& mt) {
@@ -2962,3 +2977,4 @@ __global__ __launch_bounds__(64) void pairsort_test_kernel(const uint32_t* keys,
 #include "lm_store.inc"
 #include "shard_merge.inc"
 #include "mixed_batch.inc"
+#include "dict_rows.inc"

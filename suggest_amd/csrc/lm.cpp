@@ -131,7 +131,7 @@ int lm_load_google(const char* dir, uint32_t order, const char* start_symbol, co
 // dictionary.OpenCDBDictionary (pkg/dictionary/cdb_dictionary.go over alldroll/cdb): D. J. Bernstein's constant database as
 // BuildCDBDictionary writes it (helpers.go:52-100) — key = docID as 4 bytes little endian, value = the word.  Records start at
 // byte 2048 and run to the first hash table.
-static bool read_cdb_words(const char* path, std::vector<std::string>& words, std::string& err) {
+bool read_cdb_words(const char* path, std::vector<std::string>& words, std::string& err) {
   std::ifstream f(path, std::ios::binary);
   if (!f) { err = std::string("failed to open cdb dictionary file: ") + path; return false; }
   std::string d((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());

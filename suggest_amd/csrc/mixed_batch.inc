@@ -92,9 +92,8 @@ __global__ __launch_bounds__(kMixedThreads) void mixed_lengths_kernel(const uint
     glen[j] = j < n_q ? (uint64_t)len[perm[j]] : 0ull;
 }
 
-// kMixedSub lanes per query: the bytes q[q_offs[perm[j]] ..) go to gq[goffs[j] ..).  Where source and destination share their
-// position within 16 (8, 4) bytes the middle goes in pieces of that size, the ragged ends byte by byte; where they share none,
-// every byte on its own.  gq_bytes: the room of gq.
+// kMixedSub lanes per query: the bytes q[q_offs[perm[j]] ..) go to gq[goffs[j] ..) by d_copy_bytes (engine.hip: pieces of 16, 8 or
+// 4 bytes where source and destination share their position within one, the ragged ends byte by byte).  gq_bytes: the room of gq.
 __global__ __launch_bounds__(kMixedThreads) void mixed_gather_kernel(const uint8_t* __restrict__ q, const uint64_t* __restrict__ q_offs,
                                                                       const uint32_t* __restrict__ perm, const uint64_t* __restrict__ goffs,
                                                                       uint8_t* __restrict__ gq, uint64_t gq_bytes, uint32_t n_q) {
@@ -104,17 +103,7 @@ __global__ __launch_bounds__(kMixedThreads) void mixed_gather_kernel(const uint8
     const uint64_t from = q_offs[perm[j]], to = goffs[j];
     const uint32_t n = (uint32_t)(goffs[j + 1] - to);
     if (to + n > gq_bytes) continue;          // (offsets that do not ascend: the lengths add up to more than the blob — nothing is written past it)
-    const uint8_t* src = q + from;
-    uint8_t* dst = gq + to;
-    const uint32_t apart = (uint32_t)((uintptr_t)src ^ (uintptr_t)dst);
-    const uint32_t w = (apart & 15u) == 0u ? 16u : (apart & 7u) == 0u ? 8u : (apart & 3u) == 0u ? 4u : 1u;
-    uint32_t head = w == 1u ? n : min(n, (uint32_t)((0u - (uint32_t)(uintptr_t)dst) & (w - 1u)));   // bytes up to the first whole piece
-    const uint32_t pieces = (n - head) / w;
-    for (uint32_t b = sub; b < head; b += kMixedSub) dst[b] = src[b];
-    if (w == 16u) for (uint32_t p = sub; p < pieces; p += kMixedSub) ((uint4*)(dst + head))[p] = ((const uint4*)(src + head))[p];
-    else if (w == 8u) for (uint32_t p = sub; p < pieces; p += kMixedSub) ((uint2*)(dst + head))[p] = ((const uint2*)(src + head))[p];
-    else if (w == 4u) for (uint32_t p = sub; p < pieces; p += kMixedSub) ((uint32_t*)(dst + head))[p] = ((const uint32_t*)(src + head))[p];
-    for (uint32_t b = head + pieces * w + sub; b < n; b += kMixedSub) dst[b] = src[b];
+    d_copy_bytes(gq + to, q + from, n, sub, kMixedSub);
   }
 }
 

@@ -125,6 +125,9 @@ int store_write_files(const HostIndex& ix, const std::vector<StoreList>& lists, 
 // D. J. Bernstein's constant database with key = record number as 4 bytes little endian (dictionary.BuildCDBDictionary,
 // pkg/dictionary/helpers.go:52-95): value(i, &len) = the bytes of record i
 int cdb_write_dictionary(const char* path, size_t n, const std::function<const char*(size_t, size_t*)>& value, std::string& err);
+// ... and its reader (dictionary.OpenCDBDictionary; lm.cpp): the values in record-number order.  false: the file cannot be opened,
+// is truncated or corrupted, or its record numbers have a hole (err says which).  lm_load_binary and sg_dictionary_open_cdb use it.
+bool read_cdb_words(const char* path, std::vector<std::string>& words, std::string& err);
 
 // metric maths in IEEE double, evaluation order of pkg/metric/*.go (host copies; engine.hip has
 // the device twins)

@@ -1,0 +1,131 @@
+"""DeviceDictionary: the reference's dictionary.Dictionary (docID -> string, docID = line number) behind sg_dictionary
+(include/suggest_hip.h) — in the HBM of one GPU, where the rows of any search become strings without a
+Python loop per slot, or host-resident (device=-1: no GPU needed, the plain host loop).
+"""
+import contextlib
+import ctypes as C
+import os
+import threading
+
+import numpy as np
+
+from . import _lib
+from .index import _enc, pack_strings
+
+
+def text_guess(dictionary, slots):
+    """A first text capacity for `slots` slots: twice the dictionary's mean string, never above slots * max_len (which always
+    suffices).  A call that needs more says how much and is repeated once."""
+    n = max(1, dictionary.n_docs)
+    mean = -(-dictionary.bytes // n)
+    return int(min(slots * dictionary.max_len, max(1 << 16, 2 * slots * mean)))
+
+
+def split_text(text, text_offs):
+    """(text, text_offs) -> list[bytes], one per slot"""
+    b = text.tobytes()
+    o = text_offs.tolist()
+    return [b[o[i]:o[i + 1]] for i in range(len(o) - 1)]
+
+
+class DeviceDictionary:
+    def __init__(self, lines=None, blob=None, offs=None, device=0, _handle=None):
+        """`lines`: a list of str / bytes in docID order, or (blob, offs) as pack_strings returns them (sg_dictionary_upload).
+        device < 0: a host-resident handle."""
+        self._hlock = threading.Lock()
+        if _handle is None:
+            if blob is None:
+                blob, offs = pack_strings(lines)
+            blob = np.ascontiguousarray(blob, dtype=np.uint8)
+            offs = np.ascontiguousarray(offs, dtype=np.uint64)
+            _handle = C.c_void_p()
+            _lib.check(_lib.lib().sg_dictionary_upload(blob.ctypes.data if blob.size else None, offs.ctypes.data, len(offs) - 1, int(device),
+                                                       C.byref(_handle)))
+        self._h = _handle
+        L = _lib.lib()
+        self.n_docs, self.bytes, self.max_len = int(L.sg_dictionary_size(_handle)), int(L.sg_dictionary_bytes(_handle)), int(L.sg_dictionary_max_len(_handle))
+        self.device = int(L.sg_dictionary_device(_handle))
+
+    @classmethod
+    def from_cdb(cls, path, device=0):
+        """dictionary.OpenCDBDictionary: the <name>.cdb of BuildCDBDictionary / store_cdb_dictionary (sg_dictionary_open_cdb)"""
+        h = C.c_void_p()
+        _lib.check(_lib.lib().sg_dictionary_open_cdb(_enc(os.fspath(path)), int(device), C.byref(h)))
+        return cls(_handle=h)
+
+    def __len__(self):
+        return self.n_docs
+
+    @contextlib.contextmanager
+    def _use(self):
+        """The handle, retained for the duration of a C call (a concurrent close() only drops its own reference)."""
+        L = _lib.lib()
+        with self._hlock:
+            h = self._h
+            if not h:
+                raise ValueError("dictionary is closed")
+            L.sg_dictionary_retain(h)
+        try:
+            yield h
+        finally:
+            L.sg_dictionary_release(h)
+
+    def close(self):
+        lock = getattr(self, "_hlock", None)
+        if lock is None:
+            return
+        with lock:
+            h, self._h = getattr(self, "_h", None), None
+        if h:
+            _lib.lib().sg_dictionary_release(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def rows(self, ids, counts, row_offs=None, text_cap=None):
+        """The strings of id rows (sg_dictionary_rows) -> (text u8, text_offs[slots + 1] u64): slot s holds
+        text[text_offs[s] : text_offs[s + 1]].  ids [n_rows, row] with counts [n_rows]; or flat ids with ragged
+        row_offs [n_rows + 1] as suggest_batch_mixed returns them.  Slots past a row's count, of a flagged row (SG_COUNT_*) or
+        of no row are empty.  An id outside the dictionary raises."""
+        ids = np.ascontiguousarray(ids, dtype=np.uint32)
+        counts = np.ascontiguousarray(counts, dtype=np.uint32).reshape(-1)
+        n_rows = counts.size
+        if row_offs is None:
+            row = ids.shape[1] if ids.ndim == 2 else (ids.size // n_rows if n_rows else 0)
+            ro = None
+        else:
+            row = 0
+            row_offs = np.ascontiguousarray(row_offs, dtype=np.uint64)
+            ro = row_offs.ctypes.data
+        slots = ids.size
+        text_offs = np.zeros(slots + 1, dtype=np.uint64)
+        cap = text_guess(self, slots) if text_cap is None else int(text_cap)
+        needed = C.c_uint64()
+        L = _lib.lib()
+        while True:
+            text = np.zeros(cap, dtype=np.uint8)
+            with self._use() as h:
+                rc = L.sg_dictionary_rows(h, ids.ctypes.data if slots else None, counts.ctypes.data if n_rows else None, ro, n_rows, int(row), slots,
+                                          text.ctypes.data if cap else None, cap, text_offs.ctypes.data, C.byref(needed))
+            if rc < 0 and text_cap is None and needed.value > cap and int(text_offs[slots]) == needed.value:
+                cap = int(needed.value)        # (the text was too small: the call says how much it takes)
+                continue
+            _lib.check(rc)
+            return text[:needed.value], text_offs
+
+    def rows_device(self, d_ids, d_counts, d_row_offs, n_rows, row, slots, d_text, text_cap, d_text_offs, d_info, stream=0):
+        """sg_dictionary_rows_device: raw device pointers (torch tensors' data_ptr(); d_row_offs None: rows of `row` slots),
+        asynchronous on `stream`.  d_text_offs: slots + 1 u64; d_info: 2 u64 — the bytes needed, the entries outside."""
+        with self._use() as h:
+            _lib.check(_lib.lib().sg_dictionary_rows_device(h, d_ids, d_counts, d_row_offs, int(n_rows), int(row), int(slots), d_text, int(text_cap),
+                                                            d_text_offs, d_info, stream))
+
+    def get(self, doc_id):
+        """Dictionary.Get"""
+        if not 0 <= int(doc_id) < self.n_docs:
+            raise KeyError(doc_id)
+        text, _ = self.rows(np.array([[doc_id]], dtype=np.uint32), np.array([1], dtype=np.uint32), text_cap=max(1, self.max_len))
+        return text.tobytes()

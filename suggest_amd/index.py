@@ -467,6 +467,60 @@ class NGramIndex:
                 h, blob.ctypes.data if blob.size else None, offs.ctypes.data, n_q, int(limit), ids.ctypes.data, cnt.ctypes.data))
         return ids, cnt
 
+    # ---- search: host buffers, rows and their strings (a DeviceDictionary on this index's device) ----
+    def _strings_call(self, dictionary, slots, text_cap, call):
+        """runs call(dict handle, text pointer, cap, text_offs pointer, needed) -> rc, once more where the first text
+        capacity was too small (text_cap=None: guessed from the dictionary's mean string)"""
+        from .dictionary import text_guess
+        text_offs = np.zeros(slots + 1, dtype=np.uint64)
+        cap = text_guess(dictionary, slots) if text_cap is None else int(text_cap)
+        needed = C.c_uint64()
+        while True:
+            text = np.zeros(cap, dtype=np.uint8)
+            with dictionary._use() as dh:
+                rc = call(dh, text.ctypes.data if cap else None, cap, text_offs.ctypes.data, C.byref(needed))
+            if rc < 0 and text_cap is None and needed.value > cap and int(text_offs[slots]) == needed.value:
+                cap = int(needed.value)
+                continue
+            _lib.check(rc)
+            return text[:needed.value], text_offs
+
+    def suggest_batch_strings(self, dictionary, queries=None, metric="jaccard", similarity=0.5, k=10, blob=None, offs=None, text_cap=None):
+        """sg_suggest_batch_strings -> (ids, scores, counts, text u8, text_offs[n_q * k + 1] u64): suggest_batch's rows and, for
+        slot s = i * k + j, the string text[text_offs[s] : text_offs[s + 1]] — gathered on the device from `dictionary`."""
+        if blob is None:
+            blob, offs = pack_strings(queries)
+        blob = np.ascontiguousarray(blob, dtype=np.uint8)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        n_q = len(offs) - 1
+        ids = np.zeros((n_q, k), dtype=np.uint32)
+        sc = np.zeros((n_q, k), dtype=np.float64)
+        cnt = np.zeros(n_q, dtype=np.uint32)
+        code = resolve(metric).code
+        if code is None:
+            raise ValueError("suggest_batch_strings takes the metrics with a device twin; others: suggest_batch, then dictionary.rows")
+        L = _lib.lib()
+        with self._use() as h:
+            text, text_offs = self._strings_call(dictionary, n_q * k, text_cap, lambda dh, tp, cap, op, need: L.sg_suggest_batch_strings(
+                h, blob.ctypes.data if blob.size else None, offs.ctypes.data, n_q, code, float(similarity), int(k), ids.ctypes.data,
+                sc.ctypes.data, cnt.ctypes.data, dh, tp, cap, op, need))
+        return ids, sc, cnt, text, text_offs
+
+    def autocomplete_batch_strings(self, dictionary, queries=None, limit=10, blob=None, offs=None, text_cap=None):
+        """sg_autocomplete_batch_strings -> (ids, counts, text, text_offs), as suggest_batch_strings"""
+        if blob is None:
+            blob, offs = pack_strings(queries)
+        blob = np.ascontiguousarray(blob, dtype=np.uint8)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        n_q = len(offs) - 1
+        ids = np.zeros((n_q, limit), dtype=np.uint32)
+        cnt = np.zeros(n_q, dtype=np.uint32)
+        L = _lib.lib()
+        with self._use() as h:
+            text, text_offs = self._strings_call(dictionary, n_q * limit, text_cap, lambda dh, tp, cap, op, need: L.sg_autocomplete_batch_strings(
+                h, blob.ctypes.data if blob.size else None, offs.ctypes.data, n_q, int(limit), ids.ctypes.data, cnt.ctypes.data, dh, tp, cap, op, need))
+        return ids, cnt, text, text_offs
+
     def autocomplete_all(self, query, page=1024):
         """EVERY document the prefix completes, ascending docID — what the reference's Autocomplete hands to the caller's
         collector (pkg/suggest/autocomplete.go:40-77) — paged through sg_autocomplete_one_from."""

@@ -2,12 +2,15 @@
 
 Same method names, argument meaning and error behaviour as the Go type, plus additive *Batch methods
 (the GPU earns its keep on batches).  Dictionaries stay host side (docID -> string, line order), as in
-pkg/dictionary/memory_dictionary.go.
+pkg/dictionary/memory_dictionary.go — unless the service is made with device_dictionary=True: then every dictionary is also
+held in HBM (DeviceDictionary) and the batch methods take their strings from there, one blob per call instead of a list
+lookup per slot.  Both settings return equal results.
 """
 import json
 import os
 import threading
 
+from .dictionary import DeviceDictionary
 from .index import IndexDescription, NGramIndex
 from . import _lib
 from .metric import resolve
@@ -87,11 +90,13 @@ def read_configs(path):
 
 
 class Service:
-    def __init__(self, device=0):
+    def __init__(self, device=0, device_dictionary=False):
         self._lock = threading.RLock()
         self._indexes = {}
         self._dictionaries = {}
+        self._device_dictionaries = {}
         self.device = device
+        self.device_dictionary = bool(device_dictionary)
 
     # -- AddIndexByDescription / AddRunTimeIndex / AddIndex (service.go:35-91) --
     def add_index_by_description(self, description):
@@ -105,7 +110,8 @@ class Service:
         base = os.path.join(description.output, description.name)
         dictionary = read_cdb_dictionary(base + ".cdb")
         index = NGramIndex.from_reference_files(base + ".hd", base + ".dl", description, device=self.device)
-        return self._install(description.name, index, dictionary)
+        on_device = DeviceDictionary.from_cdb(base + ".cdb", self.device) if self.device_dictionary else None
+        return self._install(description.name, index, dictionary, on_device)
 
     def add_run_time_index(self, description):
         if not description.source or not os.path.exists(description.source):
@@ -117,13 +123,21 @@ class Service:
         index = NGramIndex(dictionary, description, device=self.device)
         return self._install(name, index, dictionary)
 
-    def _install(self, name, index, dictionary):
+    def _install(self, name, index, dictionary, on_device=None):
+        dictionary = list(dictionary)
+        if self.device_dictionary and on_device is None:
+            on_device = DeviceDictionary(dictionary, device=self.device)
         with self._lock:                       # service.go:85-88
             old = self._indexes.get(name)
+            old_dict = self._device_dictionaries.pop(name, None)
             self._indexes[name] = index
-            self._dictionaries[name] = list(dictionary)
+            self._dictionaries[name] = dictionary
+            if on_device is not None:
+                self._device_dictionaries[name] = on_device
         if old is not None:
             old.close()                        # handle is reference counted on the C side
+        if old_dict is not None:
+            old_dict.close()
         return None
 
     def get_dictionaries(self):
@@ -136,6 +150,17 @@ class Service:
         if index is None or dictionary is None:
             raise KeyError("given dictionary %s is not exists" % name)   # service.go:111-113
         return index, dictionary
+
+    def _lookup_device(self, name):
+        with self._lock:
+            return self._device_dictionaries.get(name)
+
+    @staticmethod
+    def _slot_values(text, text_offs, first, n):
+        """the strings of slots first .. first + n of a (text, text_offs) pair"""
+        o = text_offs[first:first + n + 1].tolist()
+        b = text[o[0]:o[-1]].tobytes() if n else b""
+        return [b[o[t] - o[0]:o[t + 1] - o[0]].decode("utf-8", "replace") for t in range(n)]
 
     @staticmethod
     def _value(dictionary, doc_id):
@@ -156,6 +181,18 @@ class Service:
     def suggest_batch(self, dict_name, queries, top_k, metric, similarity):
         SearchConfig("", top_k, metric, similarity)
         index, dictionary = self._lookup(dict_name)
+        on_device = self._lookup_device(dict_name)
+        if on_device is not None and resolve(metric).code is not None:
+            ids, sc, cnt, text, text_offs = index.suggest_batch_strings(on_device, queries, metric, similarity, top_k)
+            out = []
+            for i in range(len(queries)):
+                c = int(cnt[i])
+                if c >= _lib.SG_COUNT_TOO_LONG:
+                    out.append(None)
+                    continue
+                values = self._slot_values(text, text_offs, i * top_k, c)
+                out.append([ResultItem(float(sc[i, j]), values[j]) for j in range(c)])
+            return out
         ids, sc, cnt = index.suggest_batch(queries, metric, similarity, top_k)
         out = []
         for i in range(len(queries)):
@@ -189,6 +226,18 @@ class Service:
                     table.append(key)
                 taken.append(i)
             ids, sc, cnt, row_offs = index.suggest_batch_mixed([configs[i].query for i in taken], table, [number[(configs[i].metric.code, configs[i].similarity, configs[i].top_k)] for i in taken])
+            on_device = self._lookup_device(dict_name)
+            if on_device is not None:          # the generic step behind the mixed call: the ragged rows' strings in one blob
+                text, text_offs = on_device.rows(ids, cnt, row_offs)
+                for j, i in enumerate(taken):
+                    c = int(cnt[j])
+                    if c >= _lib.SG_COUNT_TOO_LONG:
+                        continue
+                    r = int(row_offs[j])
+                    values = self._slot_values(text, text_offs, r, c)
+                    out[i] = [ResultItem(float(sc[r + t]), values[t]) for t in range(c)]
+                todo = rest
+                continue
             for j, i in enumerate(taken):
                 c = int(cnt[j])
                 if c >= _lib.SG_COUNT_TOO_LONG:
