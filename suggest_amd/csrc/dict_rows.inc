@@ -1,6 +1,7 @@
 // dict_rows.inc — result rows as strings from a dictionary held in HBM (sg_dictionary, include/suggest_hip.h; DESIGN.md §5c),
-// included by engine.hip after mixed_batch.inc (it uses run_host_call, HostBufs / IoLayout, search_enqueue, stream_scratch,
-// host_ctx, poison_fill, d_copy_bytes, kCountFlagMin, read_cdb_words, HIP_TRY).  The reference's Service.Suggest maps every docID
+// included by engine.hip after mixed_batch.inc (it uses host_call.inc's run_host_call, HostBufs / IoLayout and host_ctx, search_api.inc's
+// search_enqueue, handles.inc's open_search, capi.inc's stream_scratch and poison_fill, d_copy_bytes, kCountFlagMin, read_cdb_words,
+// HIP_TRY).  The reference's Service.Suggest maps every docID
 // of a row through dict.Get (pkg/suggest/service.go:129-136); here the rows of any search stay on the device and
 //   lengths   dict_lengths_kernel: a thread per slot finds the slot's row and its place in it — a division for a fixed stride, a
 //             search of row_offs for ragged rows — and writes the string's length where the slot holds an entry, 0 where it
@@ -370,20 +371,18 @@ int sg_suggest_batch_strings(sg_index* index, const uint8_t* q, const uint64_t* 
                              uint32_t* ids, double* scores, uint32_t* counts, sg_dictionary* dict, uint8_t* text, uint64_t text_cap,
                              uint64_t* text_offs, uint64_t* needed) {
   SG_GUARD_BEGIN
-  int rc = check_search_args(index, k, true, similarity, metric);
-  if (rc) return rc;
-  if (!offs || !ids || !scores || !counts) { set_error("null argument"); return SG_E_INVALID; }
-  return strings_host_call(index, q, offs, n_q, search_req(metric, similarity, k, 0), ids, scores, counts, dict, text, text_cap, text_offs, needed);
+  const SearchKey c = fuzzy_key(metric, similarity, k);
+  if (int rc = open_search(index, c, true, {offs, ids, scores, counts})) return rc;
+  return strings_host_call(index, q, offs, n_q, search_req(c), ids, scores, counts, dict, text, text_cap, text_offs, needed);
   SG_GUARD_END(SG_RC)
 }
 
 int sg_autocomplete_batch_strings(sg_index* index, const uint8_t* q, const uint64_t* offs, uint32_t n_q, uint32_t limit, uint32_t* ids,
                                   uint32_t* counts, sg_dictionary* dict, uint8_t* text, uint64_t text_cap, uint64_t* text_offs, uint64_t* needed) {
   SG_GUARD_BEGIN
-  int rc = check_search_args(index, limit, false, 0, 0);
-  if (rc) return rc;
-  if (!offs || !ids || !counts) { set_error("null argument"); return SG_E_INVALID; }
-  return strings_host_call(index, q, offs, n_q, search_req(0, 0, limit, 1), ids, nullptr, counts, dict, text, text_cap, text_offs, needed);
+  const SearchKey c = prefix_key(limit);
+  if (int rc = open_search(index, c, false, {offs, ids, counts})) return rc;
+  return strings_host_call(index, q, offs, n_q, search_req(c), ids, nullptr, counts, dict, text, text_cap, text_offs, needed);
   SG_GUARD_END(SG_RC)
 }
 

@@ -1,5 +1,5 @@
 // forward_index.inc — the forward index (doc -> distinct terms) of a replica, derived on the GPU from the CSR that is
-// already there.  Included by capi.inc.
+// already there.  Included by engine.hip after capi.inc; tune.inc's add_replica calls it.
 //
 // The reference verifies nothing: its mergers count exactly (pkg/merger/cp_merge.go:32-117).  The device path counts
 // with lossy LDS counters and verifies every flagged document exactly (DESIGN.md §4); with only the inverted lists that

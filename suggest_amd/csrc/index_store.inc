@@ -1,4 +1,4 @@
-// index_store.inc — the device encoder behind sg_index_store_reference, included by engine.hip after capi.inc (it uses the
+// index_store.inc — the device encoder behind sg_index_store_reference, included by engine.hip after the host files (it uses the
 // handle, HIP_TRY, DeviceGuard and DeviceBlock).  Replaces the single-threaded walk of Writer.Commit + index.NewEncoder
 // (pkg/index/indexer_writer.go:88-167, pkg/index/codec.go:17-51) over the posting lists of a built index; the formats and
 // the host encoder the kernels are read against are in index_store.cpp.

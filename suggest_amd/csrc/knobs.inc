@@ -1,4 +1,4 @@
-// knobs.inc — the index's tuning knobs, said once (included by capi.inc): the table below is what the environment at the first
+// knobs.inc — the index's tuning knobs, said once (included by handles.inc, for sg_index): the table below is what the environment at the first
 // upload, sg_index_tune(), sg_debug_knob() and DESIGN.md §4c all go by.  Results never depend on the knobs; tests sweep them.
 // A row's flags: read from the environment at the first upload / may be set through sg_index_tune(); setting it pins the stream
 // workgroup (takes pipe_shape_auto away); tune_choice() chooses it unless it was set explicitly; powers of two only.

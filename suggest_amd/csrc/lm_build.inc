@@ -1,5 +1,6 @@
-// lm_build.inc — the language model built from a corpus on the device (sg_lm_build_device), included by capi.inc, whose
-// DeviceBlock, device_exclusive_sum and device_total it uses, behind the word tokeniser's helpers of engine.hip (d_next_rune, d_lower_pairs, d_lm_alpha_has, d_put_rune), which it reuses.
+// lm_build.inc — the language model built from a corpus on the device (sg_lm_build_device, lm_api.inc), included by engine.hip after
+// capi.inc.  It uses host_base.inc's DeviceBlock, device_exclusive_sum and device_total and handles.inc's lm_alphabet_tables,
+// behind the word tokeniser's helpers of engine.hip (d_next_rune, d_lower_pairs, d_lm_alpha_has, d_put_rune), which it reuses.
 //
 // What it restates: NGramBuilder.Build over NewSentenceRetriever (pkg/lm/ngram_builder.go:19-64, sentence_retriever.go:54-81),
 // lm.NewTokenizer, buildDictionary's numbering (binary.go:140-198) and the vector builder as lm_load_google restates it — the

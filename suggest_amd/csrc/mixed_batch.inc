@@ -1,7 +1,7 @@
 // mixed_batch.inc — one batch whose queries differ in metric, similarity and k (sg_suggest_batch_mixed, include/suggest_hip.h;
-// DESIGN.md §5b), included by engine.hip after capi.inc (it uses launch(), run_host_call, HostBufs / IoLayout, stream_scratch,
-// poison_fill, replica_of_pointer, check_search_values, HIP_TRY).  Group and dispatch: the search kernels keep one (metric,
-// similarity, k) per launch, and a mixed call is one enqueue step, mixed_enqueue, around the ordinary launch() of every group —
+// DESIGN.md §5b), included by engine.hip after the host files (it uses capi.inc's launch(), stream_scratch and poison_fill,
+// host_call.inc's run_host_call and HostBufs / IoLayout, index_api.inc's replica_of_pointer, handles.inc's check_search_values).
+// The search kernels keep one (metric, similarity, k) per launch: a mixed call is one enqueue step, mixed_enqueue, around the launch() of every group —
 //   count     mixed_count_kernel: every config number checked against n_configs (a bad one raises the call's error word and is
 //             counted nowhere), a histogram over the configs, the queries' byte lengths, the sort's keys and values;
 //   permute   a stable radix sort of the query numbers by the 8-bit config number (hipcub, as device_sort_pairs): within a group
@@ -13,7 +13,7 @@
 //   scatter   mixed_scatter_kernel copies every group row (n_g x k_g, dense, zeroed or poisoned before its launch as a plain
 //             call's rows are) to the caller's ragged row and the count to the caller's order.  It copies all k_g slots, so the
 //             slots past a row's count carry what the plain call leaves there; an autocomplete row's score slots are written zero.
-// The host-buffer route is capi.inc's run_host_call around the step: it knows the group sizes from config_of in host memory.  The
+// The host-buffer route is host_call.inc's run_host_call around the step: it knows the group sizes from config_of in host memory.  The
 // device route reads the n_configs counters (and the error word, and the queries' bytes in all) back through pinned memory with
 // ONE wait on the caller's stream — the one place where a device call is not asynchronous.
 // The call's own device memory is two blocks of the calling thread's per-stream scratch (SCRATCH_MIXED: lists and offsets, sized by

@@ -1,5 +1,5 @@
 // packed_store.inc — the posting store the search kernel streams, derived on the GPU from the u32 CSR (host build, device
-// build or a reference-built index: all the same from here on).  Included by capi.inc.
+// build or a reference-built index: all the same from here on).  Included by engine.hip after capi.inc; tune.inc's add_replica calls it.
 //
 // The reference keeps a list as varint / roaring bytes and decodes it posting by posting (pkg/index/posting_list.go:24-108,
 // pkg/compression/*.go); the u32 CSR of round 1-2 made the stream a plain coalesced read, and the kernel ended up waiting

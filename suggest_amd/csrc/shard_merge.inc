@@ -1,7 +1,8 @@
 // shard_merge.inc — a dictionary sharded by docID range behind one handle (sg_sharded, include/suggest_hip.h), included by
-// engine.hip after capi.inc (it uses launch(), build_any(), add_replica(), stream_scratch, run_host_call, io_layout, GrowBlock,
+// engine.hip after the host files (it uses capi.inc's launch(), stream_scratch and GrowBlock, index_api.inc's build_any(), tune.inc's
+// add_replica(), host_call.inc's run_host_call and io_layout, handles.inc's open_search, host_base.inc's
 // DeviceGuard, HIP_TRY).  A sharded search is one enqueue step, sharded_enqueue: the device-resident call is that step on the
-// caller's stream, a host-buffer call is capi.inc's run_host_call around it, as every other host-buffer call is around its own.
+// caller's stream, a host-buffer call is host_call.inc's run_host_call around it, as every other host-buffer call is around its own.
 // SURVEY.md §8(e) / DESIGN.md §5: every shard indexes the documents [doc_lo, doc_lo + n) under local docIDs, built with the
 // dictionary-wide number of cardinality segments; a call searches the whole batch on every shard and sg_shard_merge_kernel
 // merges the per-shard top-k rows on the device under the reference's total order (score desc, docID asc; collector.go:20-26).
@@ -273,9 +274,9 @@ ShardMergeArgs sharded_merge_args(uint32_t W, const uint64_t* doc_lo, const char
   return a;
 }
 
-int sharded_check_call(sg_sharded* h, uint32_t k, bool fuzzy, double similarity, int metric) {
+int sharded_open(sg_sharded* h, const SearchKey& c, std::initializer_list<const void*> required) {
   if (!h) { set_error("null handle"); return SG_E_INVALID; }
-  return check_search_args(h->shard[0], k, fuzzy, similarity, metric);
+  return open_search(h->shard[0], c, !c.autocomplete, required);
 }
 
 // The enqueue step of a sharded search: n_q > 0 queries, their offsets and the three arrays of merged rows on shard 0's device,
@@ -380,7 +381,6 @@ int sharded_enqueue(sg_sharded* h, const char* d_q, const uint64_t* d_offs, uint
 // Host buffers: a synchronous host-buffer call (run_host_call) on the merge device around the enqueue step.
 int sharded_host_call(sg_sharded* h, const uint8_t* q, const uint64_t* offs, uint32_t n_q, const LaunchReq& base, uint32_t* ids, double* scores,
                       uint32_t* counts) {
-  if (!offs || !ids || !counts || (!base.autocomplete && !scores)) { set_error("null argument"); return SG_E_INVALID; }
   const HostBufs b = search_bufs(q, offs, n_q, base, ids, scores, counts, nullptr);
   // (clear_rows is false: the merge kernel writes every slot of every row, flags included)
   return run_host_call(h->device[0], b, false, [&](char* dev, const IoLayout& io, hipStream_t st) {
@@ -483,23 +483,26 @@ uint32_t sg_sharded_shards(const sg_sharded* h, uint64_t* out_doc_lo, int* out_d
 int sg_sharded_suggest_batch(sg_sharded* h, const uint8_t* q, const uint64_t* offs, uint32_t n_q, int metric, double similarity, uint32_t k,
                              uint32_t* ids, double* scores, uint32_t* counts) {
   SG_GUARD_BEGIN
-  if (int rc = sharded_check_call(h, k, true, similarity, metric)) return rc;
-  return sharded_host_call(h, q, offs, n_q, search_req(metric, similarity, k, 0), ids, scores, counts);
+  const SearchKey c = fuzzy_key(metric, similarity, k);
+  if (int rc = sharded_open(h, c, {offs, ids, scores, counts})) return rc;
+  return sharded_host_call(h, q, offs, n_q, search_req(c), ids, scores, counts);
   SG_GUARD_END(SG_RC)
 }
 
 int sg_sharded_autocomplete_batch(sg_sharded* h, const uint8_t* q, const uint64_t* offs, uint32_t n_q, uint32_t limit, uint32_t* ids,
                                   uint32_t* counts) {
   SG_GUARD_BEGIN
-  if (int rc = sharded_check_call(h, limit, false, 0, 0)) return rc;
-  return sharded_host_call(h, q, offs, n_q, search_req(0, 0, limit, 1), ids, nullptr, counts);
+  const SearchKey c = prefix_key(limit);
+  if (int rc = sharded_open(h, c, {offs, ids, counts})) return rc;
+  return sharded_host_call(h, q, offs, n_q, search_req(c), ids, nullptr, counts);
   SG_GUARD_END(SG_RC)
 }
 
 int sg_sharded_suggest_batch_device(sg_sharded* h, const void* d_q, const void* d_offs, uint32_t n_q, int metric, double similarity, uint32_t k,
                                     void* d_ids, void* d_scores, void* d_counts, void* stream) {
   SG_GUARD_BEGIN
-  if (int rc = sharded_check_call(h, k, true, similarity, metric)) return rc;
+  const SearchKey c = fuzzy_key(metric, similarity, k);
+  if (int rc = sharded_open(h, c, {})) return rc;                // (an empty batch needs no arrays: they are looked at below)
   if (n_q == 0) return SG_OK;
   if (!d_offs || !d_ids || !d_counts || !d_scores) { set_error("null argument"); return SG_E_INVALID; }
   hipPointerAttribute_t at;
@@ -509,7 +512,7 @@ int sg_sharded_suggest_batch_device(sg_sharded* h, const void* d_q, const void* 
     set_error("sg_sharded_*_device: every shard has to be resident on the device that owns the buffers");
     return SG_E_UNSUPPORTED;
   }
-  return sharded_enqueue(h, (const char*)d_q, (const uint64_t*)d_offs, n_q, 0, search_req(metric, similarity, k, 0), (uint32_t*)d_ids,
+  return sharded_enqueue(h, (const char*)d_q, (const uint64_t*)d_offs, n_q, 0, search_req(c), (uint32_t*)d_ids,
                          (uint64_t*)d_scores, (uint32_t*)d_counts, (hipStream_t)stream, false);
   SG_GUARD_END(SG_RC)
 }

@@ -59,6 +59,32 @@ def test_search_without_upload_fails_loudly(cars_lines):
     assert e.value.code == -3
 
 
+def test_search_entry_points_refuse_a_missing_or_unuploaded_index(cars_lines):
+    """The CPU twin of test_gpu_entry_checks.py: every search entry point answers a null index with SG_E_INVALID, and an index that
+    was never uploaded with SG_E_NOT_UPLOADED — before it looks at k, the similarity, the metric or a pointer — and writes nothing.
+    (A sharded handle only adopts uploaded shards: its entry points have the null case alone here.)"""
+    import entry_check_cases as ec
+    from suggest_amd import NGramIndex
+    ix = NGramIndex(cars_lines[:100], _desc(CARS_DESC), upload=False)
+    L, bufs = ec.raw_lib(), ec.Buffers()
+    for entry in ec.ENTRIES:
+        for kw in (dict(), dict(k=0)):
+            bufs.reset()
+            rc, msg = entry.call(L, None, bufs, {}, **kw)
+            assert (rc, msg) == (ec.SG_E_INVALID, ec.null_handle_message(entry)), (entry.name, kw)
+            assert bufs.untouched(), (entry.name, kw)
+        if entry.handle != "index":
+            continue
+        bad = [dict(), dict(k=0), dict(similarity=1.5), dict(metric=99)] + [dict(null=p) for p, _ in entry.required]
+        for kw in bad:
+            bufs.reset()
+            with ix._use() as h:
+                rc, msg = entry.call(L, h, bufs, {}, **kw)
+            assert (rc, msg) == (ec.SG_E_NOT_UPLOADED, ec.MSG_NOT_UPLOADED), (entry.name, kw)
+            assert bufs.untouched(), (entry.name, kw)
+    ix.close()
+
+
 def test_argument_validation(cars_lines):
     from suggest_amd import NGramIndex, IndexDescription, SearchConfig, _lib
     with pytest.raises(ValueError):

@@ -24,7 +24,7 @@ def _pair(n_docs, n_q, desc=None, seed=1, **variant):
 def synth_pipe():
     gpu, ora, qb, qo = _pair(60000, 4096)
     # every eligible launch, and the stream workgroup of the large dictionaries (eight wavefronts, 2^13 counters, 8 KB of
-    # descriptors): a dictionary of this size gets two wavefronts on 2^11 counters by default (tune_choice, capi.inc)
+    # descriptors): a dictionary of this size gets two wavefronts on 2^11 counters by default (tune_choice, tune.inc)
     gpu.tune(SG_PIPE=1, SG_PIPE_NW=8, SG_PIPE_LOG2_CNT=13, SG_PIPE_DT_BYTES=8192)
     return gpu, ora, qb, qo
 

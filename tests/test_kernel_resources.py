@@ -44,7 +44,7 @@ def test_search_kernel_registers_and_stream_loop_schedule(tmp_path):
         nm = b.split()[0]
         res[nm] = {k: int(v) for k, v in re.findall(r"remark:\s+(TotalSGPRs|VGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]): (\d+)", b)}
     stream = [v for k, v in res.items() if "sg_stream_kernelILi" in k]
-    assert len(stream) == 6, list(res)                                    # 8, 4 or 2 wavefronts (capi.inc tune_choice: by the index's query volume) x 4- / 8-byte sub-row descriptors
+    assert len(stream) == 6, list(res)                                    # 8, 4 or 2 wavefronts (tune.inc tune_choice: by the index's query volume) x 4- / 8-byte sub-row descriptors
     for b in stream:
         assert b["VGPRs"] <= 64 and b["TotalSGPRs"] <= 80 and b["ScratchSize [bytes/lane]"] == 0 and b["Occupancy [waves/SIMD]"] == 8, b
     plan = [v for k, v in res.items() if "sg_plan_kernel" in k]
