@@ -1411,6 +1411,96 @@ func (i *Index) SuggestStrings(dict *DeviceDictionary, queries []string, similar
 	return cands, values, status, nil
 }
 
+// EditDistance configures SuggestEdit's second ranking stage: Candidates per query by the q-gram metric, of those the k nearest
+// by edit distance over runes.  Transpositions: optimal string alignment (adjacent runes swapped at cost 1) instead of
+// Levenshtein.  NoFold: leave case as it is.  MaxDistance < 0: no bound.
+type EditDistance struct {
+	Candidates     int
+	Transpositions bool
+	NoFold         bool
+	MaxDistance    int64
+}
+
+// SuggestEdit searches and ranks in one call (sg_suggest_batch_edit): rerank.Candidates per query by (m, similarity), of those the
+// k nearest to the query by edit distance, ties in (score descending, docID ascending); distances[q][j] belongs to cands[q][j].
+// The exact top-k by edit distance AMONG THE CANDIDATES THE Q-GRAM SEARCH RETURNED, not over the whole dictionary.  dict must live
+// on the device of the index's primary replica.
+func (i *Index) SuggestEdit(dict *DeviceDictionary, queries []string, similarity float64, m metric.Metric, k int, rerank EditDistance) (cands [][]suggest.Candidate, distances [][]uint32, status []uint32, err error) {
+	code, known := metricCode(m)
+	if !known {
+		return nil, nil, nil, errors.New("SuggestEdit: a metric without a device twin")
+	}
+	n := len(queries)
+	if n == 0 {
+		return nil, nil, nil, nil
+	}
+	if k <= 0 || rerank.Candidates < k {
+		return nil, nil, nil, errors.New("SuggestEdit: k should be in 1 .. rerank.Candidates")
+	}
+	var blob []byte
+	offs := make([]C.uint64_t, 1, n+1)
+	for _, q := range queries {
+		blob = append(blob, q...)
+		offs = append(offs, C.uint64_t(len(blob)))
+	}
+	var bp *C.uint8_t
+	if len(blob) > 0 {
+		bp = (*C.uint8_t)(unsafe.Pointer(&blob[0]))
+	}
+	ids := make([]C.uint32_t, n*k)
+	scores := make([]C.double, n*k)
+	dist := make([]C.uint32_t, n*k)
+	counts := make([]C.uint32_t, n)
+	var cfg C.sg_edit_config
+	if rerank.Transpositions {
+		cfg.mode = C.SG_EDIT_OSA
+	}
+	if !rerank.NoFold {
+		cfg.fold_case = 1
+	}
+	cfg.max_distance = 0xFFFFFFFF
+	if rerank.MaxDistance >= 0 && rerank.MaxDistance < 0xFFFFFFFF {
+		cfg.max_distance = C.uint32_t(rerank.MaxDistance)
+	}
+	dict.mu.RLock()
+	if dict.closed {
+		dict.mu.RUnlock()
+		return nil, nil, nil, errClosed
+	}
+	C.sg_dictionary_retain(dict.h)
+	dict.mu.RUnlock()
+	defer func() { C.sg_dictionary_release(dict.h); runtime.KeepAlive(dict) }()
+	e := i.e
+	if err = e.retain(); err != nil {
+		return nil, nil, nil, err
+	}
+	defer func() { e.release(); runtime.KeepAlive(i) }()
+	err = ccall(func() C.int {
+		return C.sg_suggest_batch_edit(e.h, bp, &offs[0], C.uint32_t(n), code, C.double(similarity), C.uint32_t(rerank.Candidates), dict.h, &cfg, C.uint32_t(k), &ids[0], &scores[0], &dist[0], &counts[0])
+	})
+	if err != nil {
+		return nil, nil, nil, err
+	}
+	cands = make([][]suggest.Candidate, n)
+	distances = make([][]uint32, n)
+	status = make([]uint32, n)
+	for q := 0; q < n; q++ {
+		c := uint32(counts[q])
+		if c >= C.SG_COUNT_LM_ERROR { // an SG_COUNT_* flag: no row
+			status[q] = c
+			continue
+		}
+		cands[q] = make([]suggest.Candidate, c)
+		distances[q] = make([]uint32, c)
+		for j := 0; j < int(c); j++ {
+			s := q*k + j
+			cands[q][j] = suggest.Candidate{Key: uint32(ids[s]), Score: float64(scores[s])}
+			distances[q][j] = uint32(dist[s])
+		}
+	}
+	return cands, distances, status, nil
+}
+
 // StoreBinary writes the spellchecker's language model as the <name>.lm / <name>.cdb pair `lm build-lm` leaves behind
 // (StoreBinaryLM, pkg/lm/binary.go:18-57).  mph adds the minimal perfect hash RetrieveLMFromBinary reads after the model
 // (pkg/mph/mph.go): the file the reference's spellchecker service opens (sg_lm_store_binary_ex).

@@ -652,6 +652,58 @@ int sg_autocomplete_batch_strings(sg_index* index, const uint8_t* q_utf8, const 
                                   uint32_t* out_ids, uint32_t* out_counts, sg_dictionary* dict, uint8_t* text, uint64_t text_cap,
                                   uint64_t* text_offs, uint64_t* needed);
 
+/* Result rows ranked by edit distance: the second stage of the q-gram count filter.  The rows of a search are
+ * verified against the strings of an sg_dictionary and ranked by the distance between row i's query and each of its entries.
+ * THE RESULT IS THE EXACT TOP-K BY EDIT DISTANCE AMONG THE CANDIDATES THE Q-GRAM SEARCH RETURNED — not over the whole dictionary: a
+ * string the search did not return is never looked at, so fetch more candidates than you keep.
+ *
+ * Distances are over runes: both strings are decoded as Go's `range` does (an invalid byte is one U+FFFD of width 1); nothing is
+ * trimmed, wrapped or mapped through an index alphabet.  fold_case != 0: every rune of both strings first goes through the simple
+ * lower-case pairs of the tokenisers (the handle keeps its own copy of the table; a host-resident handle uses the host's function).
+ * SG_EDIT_LEVENSHTEIN: unit insert, delete, substitute.  SG_EDIT_OSA: the same plus the transposition of two adjacent runes at cost 1
+ * — optimal string alignment: "ca" -> "abc" is 3, not unrestricted Damerau's 2.  Both are symmetric.
+ *
+ * Geometry exactly as sg_dictionary_rows (a fixed `row`, or ragged row_offs); row i belongs to query i = q[q_offs[i] ..
+ * q_offs[i + 1]), 65 536 bytes at most.  dist[slots] (u32): the distance of every entry; 0xFFFFFFFF for a slot that holds none (past
+ * the count, a flagged row, no row) and for an entry whose id is outside the dictionary, which is counted in info[1] (d_info: two
+ * u64, [0] = 0); the host-buffer routes answer invalid argument for such an id after delivering the rest.
+ *
+ * Re-rank: a row's entries are reordered by (distance ascending, then the order they had) — a stable sort: a fuzzy row keeps (score
+ * descending, docID ascending) among equal distances, an autocomplete row (scores null) docID ascending.  Entries with a distance
+ * above max_distance are removed (0xFFFFFFFF: no bound); the count becomes the number kept, at most k_out; slots from the count on are
+ * zeroed in ids, scores and distances.  Flagged rows (SG_COUNT_*) pass through untouched, their distances 0xFFFFFFFF.
+ *
+ * The _device calls take device pointers, are asynchronous on `stream`, write nothing of any handle and may be called from any number
+ * of threads; a host-resident handle is refused (unsupported).  On that route a query of more than 65 536 bytes gets no distances:
+ * its entries stay 0xFFFFFFFF and are counted in info[1].  sg_edit_rows / sg_edit_rerank take host buffers; with a host-resident
+ * handle they are a plain host loop and need no GPU.
+ * sg_suggest_batch_edit: search and rank in one call — k_candidates per query by the q-gram metric, of those the k nearest by edit
+ * distance; rows of k; one staging in, one copy out, one wait.  Invalid argument: null pointers, an unknown mode, k == 0,
+ * k > k_candidates, k_candidates above SG_MAX_TOPK; unsupported: a dictionary that is host-resident or not on the device of the
+ * index's primary replica.
+ * Queries of up to 64 runes take the hot path (a lane per candidate, one 64-bit word of bit vectors); longer ones a slower kernel
+ * whose working memory is bounded by a byte budget — sg_debug_edit_slice_bytes lowers it for tests (0: the default, 64 MiB). */
+enum sg_edit_mode { SG_EDIT_LEVENSHTEIN = 0, SG_EDIT_OSA = 1 };
+typedef struct sg_edit_config { int32_t mode; int32_t fold_case; uint32_t max_distance; uint32_t reserved; } sg_edit_config;
+int sg_edit_rows_device(sg_dictionary* dict, const sg_edit_config* config, const void* d_q_blob, const void* d_q_offs, const void* d_ids,
+                        const void* d_counts, const void* d_row_offs_or_null, uint32_t n_rows, uint32_t row, uint64_t slots, void* d_dist,
+                        void* d_info, void* stream);
+int sg_edit_rows(sg_dictionary* dict, const sg_edit_config* config, const uint8_t* q_utf8, const uint64_t* q_offs, const uint32_t* ids,
+                 const uint32_t* counts, const uint64_t* row_offs_or_null, uint32_t n_rows, uint32_t row, uint64_t slots, uint32_t* dist);
+int sg_edit_rerank_device(sg_dictionary* dict, const sg_edit_config* config, const void* d_q_blob, const void* d_q_offs, void* d_ids,
+                          void* d_scores_or_null, void* d_counts, const void* d_row_offs_or_null, uint32_t n_rows, uint32_t row, uint64_t slots,
+                          uint32_t k_out, void* d_dist, void* d_info, void* stream);
+int sg_edit_rerank(sg_dictionary* dict, const sg_edit_config* config, const uint8_t* q_utf8, const uint64_t* q_offs, uint32_t* ids,
+                   double* scores_or_null, uint32_t* counts, const uint64_t* row_offs_or_null, uint32_t n_rows, uint32_t row, uint64_t slots,
+                   uint32_t k_out, uint32_t* dist);
+int sg_suggest_batch_edit(sg_index* index, const uint8_t* q_utf8, const uint64_t* q_offs, uint32_t n_q, int metric, double similarity,
+                          uint32_t k_candidates, sg_dictionary* dict, const sg_edit_config* config, uint32_t k, uint32_t* out_ids,
+                          double* out_scores, uint32_t* out_dist, uint32_t* out_counts);
+int sg_debug_edit_slice_bytes(uint64_t bytes);
+/* Test hook (no GPU needed): the kernels' own statement of the bit-vector recurrence, run on the host over two rune strings — the
+ * one-word form with its Peq table for n_a <= 64, the blocked form over sorted (rune, position) pairs above. */
+int sg_debug_edit_bitvector(int mode, const uint32_t* a, uint32_t n_a, const uint32_t* b, uint32_t n_b, uint32_t* out);
+
 /* Sets a tuning knob of the index, before or after its first upload: SG_LOG2_CNT, SG_T_FLOOR, SG_FILTER_LEVEL, SG_TIGHTEN, SG_ROOMY,
  * SG_ORDER, SG_PRETOK, SG_SPLIT_CHUNKS, SG_PARTS_CNT_BONUS; the pipeline's SG_PIPE, SG_PIPE_SUB, SG_PIPE_CAND_CAP, SG_PIPE_WIDE,
  * SG_PLAN2.  SG_PIPE_NW, SG_PIPE_LOG2_CNT and SG_PIPE_DT_BYTES freeze the stream workgroup's shape for every launch;

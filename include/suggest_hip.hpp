@@ -200,6 +200,18 @@ class DeviceDictionary : public Dictionary {
     text.resize((size_t)needed);
     return text;
   }
+  // sg_edit_rows: the edit distance, over runes, between queries[i] and every entry of row i (geometry as Rows); 0xFFFFFFFF where
+  // a slot holds no entry.  transpositions: optimal string alignment (adjacent runes swapped at cost 1) instead of Levenshtein.
+  std::vector<uint32_t> EditDistances(const std::vector<std::string>& queries, const uint32_t* ids, const uint32_t* counts, const uint64_t* row_offs,
+                                      uint32_t row, uint64_t slots, bool transpositions = false, bool fold_case = true) const {
+    std::string blob;
+    std::vector<uint64_t> offs(1, 0);
+    for (auto& q : queries) { blob += q; offs.push_back(blob.size()); }
+    const sg_edit_config cfg{transpositions ? SG_EDIT_OSA : SG_EDIT_LEVENSHTEIN, fold_case ? 1 : 0, 0xFFFFFFFFu, 0u};
+    std::vector<uint32_t> dist((size_t)slots);
+    Check(sg_edit_rows(h_, &cfg, (const uint8_t*)blob.data(), offs.data(), ids, counts, row_offs, (uint32_t)queries.size(), row, slots, dist.data()));
+    return dist;
+  }
 
  private:
   static void Check(int rc) {
@@ -422,6 +434,20 @@ struct ResultItem {  // service.go:12-17
   std::string Value;
 };
 
+// A second ranking stage by edit distance over the candidates of a search (sg_suggest_batch_edit): the exact top-k by distance AMONG
+// THE CANDIDATES THE Q-GRAM SEARCH RETURNED, not over the whole dictionary.  max_distance 0xFFFFFFFF: no bound.
+struct EditDistance {
+  int candidates = 64;
+  bool transpositions = false;
+  bool fold_case = true;
+  uint32_t max_distance = 0xFFFFFFFFu;
+};
+struct EditCandidate {
+  uint32_t Key;
+  double Score;
+  uint32_t Distance;
+};
+
 struct SearchConfig {  // search.go:10-15
   std::string query;
   int topK;
@@ -540,12 +566,34 @@ class NGramIndex {
     return out;
   }
 
+  // sg_suggest_batch_edit: rerank.candidates per query by the q-gram metric, of those the topK nearest by edit distance to the
+  // query (ties keep score descending, docID ascending); the strings come from `dict`, on the device of the index
+  std::vector<std::vector<EditCandidate>> SuggestEdit(const dictionary::DeviceDictionary& dict, const std::vector<std::string>& queries, double similarity,
+                                                      metric::Metric m, int topK, const EditDistance& rerank = EditDistance()) const {
+    std::vector<uint64_t> offs;
+    const std::string blob = Pack(queries, offs);
+    const size_t n = queries.size(), k = (size_t)(topK > 0 ? topK : 0);
+    std::vector<uint32_t> ids(n * k + 1), dist(n * k + 1), counts(n + 1);
+    std::vector<double> scores(n * k + 1);
+    const sg_edit_config cfg{rerank.transpositions ? SG_EDIT_OSA : SG_EDIT_LEVENSHTEIN, rerank.fold_case ? 1 : 0, rerank.max_distance, 0u};
+    Check(sg_suggest_batch_edit(h_, (const uint8_t*)blob.data(), offs.data(), (uint32_t)n, m.id, similarity, (uint32_t)(rerank.candidates > 0 ? rerank.candidates : 0),
+                                dict.Handle(), &cfg, (uint32_t)k, ids.data(), scores.data(), dist.data(), counts.data()));
+    std::vector<std::vector<EditCandidate>> out(n);
+    for (size_t i = 0; i < n; i++) {
+      if (counts[i] == SG_COUNT_REF_PANIC) throw Error("reference behaviour: panic: makechan: size out of range");
+      if (counts[i] == SG_COUNT_REF_DEADLOCK) throw Error("reference behaviour: deadlock (unbuffered channel, suggester.go:62)");
+      if (counts[i] == SG_COUNT_TOO_LONG) throw Error("query has more than SG_MAX_QUERY_TERMS n-grams");
+      for (uint32_t j = 0; j < counts[i]; j++) out[i].push_back(EditCandidate{ids[i * k + j], scores[i * k + j], dist[i * k + j]});
+    }
+    return out;
+  }
+
   std::vector<std::vector<Candidate>> AutocompleteBatch(const std::vector<std::string>& queries, int limit) const {
     std::vector<uint64_t> offs;
     const std::string blob = Pack(queries, offs);
     const size_t n = queries.size(), k = (size_t)(limit > 0 ? limit : 0);
     std::vector<uint32_t> ids(n * k), counts(n);
-    Check(sg_autocomplete_batch(h_, (const uint8_t*)blob.data(), offs.data(), (uint32_t)n, (uint32_t)k, ids.data(), counts.data()));
+    Check(sg_autocomplete_batch(h_,(const uint8_t*)blob.data(), offs.data(), (uint32_t)n, (uint32_t)k, ids.data(), counts.data()));
     std::vector<std::vector<Candidate>> out(n);
     for (size_t i = 0; i < n; i++) {
       if (counts[i] == SG_COUNT_TOO_LONG) throw Error("query has more than SG_MAX_QUERY_TERMS n-grams");

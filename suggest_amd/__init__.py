@@ -6,5 +6,5 @@ from .index import IndexDescription, NGramIndex, pack_strings, store_cdb_diction
 from .dictionary import DeviceDictionary  # noqa: F401
 from .metric import CosineMetric, DiceMetric, ExactMetric, JaccardMetric, OverlapMetric  # noqa: F401
 from .sharded import ShardedIndex  # noqa: F401
-from .service import ResultItem, SearchConfig, Service, read_configs, read_dictionary  # noqa: F401
+from .service import EditDistance, ResultItem, SearchConfig, Service, read_configs, read_dictionary  # noqa: F401
 from .spell import LanguageModel, SpellChecker  # noqa: F401

@@ -40,7 +40,12 @@ EXPORTS = [
     "sg_dictionary_upload", "sg_dictionary_open_cdb", "sg_dictionary_retain", "sg_dictionary_release", "sg_dictionary_size", "sg_dictionary_bytes",
     "sg_dictionary_max_len", "sg_dictionary_device", "sg_dictionary_rows_device", "sg_dictionary_rows", "sg_suggest_batch_strings",
     "sg_autocomplete_batch_strings",
+    "sg_edit_rows_device", "sg_edit_rows", "sg_edit_rerank_device", "sg_edit_rerank", "sg_suggest_batch_edit", "sg_debug_edit_slice_bytes",
+    "sg_debug_edit_bitvector",
 ]
+SG_EDIT_LEVENSHTEIN = 0
+SG_EDIT_OSA = 1
+SG_EDIT_NONE = 0xFFFFFFFF          # the distance of a slot that holds no entry; max_distance: no bound
 SG_MAX_MIXED_CONFIGS = 256
 SG_MAX_SHARDS = 64
 SG_LM_STORE_MPH = 1
@@ -60,6 +65,11 @@ class SgStats(C.Structure):
 class SgSearchConfig(C.Structure):
     """sg_search_config: one entry of a mixed batch's table (24 bytes)"""
     _fields_ = [("metric", C.c_int32), ("autocomplete", C.c_int32), ("similarity", C.c_double), ("k", C.c_uint32), ("first_doc", C.c_uint32)]
+
+
+class SgEditConfig(C.Structure):
+    """sg_edit_config (16 bytes)"""
+    _fields_ = [("mode", C.c_int32), ("fold_case", C.c_int32), ("max_distance", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class SuggestHipError(RuntimeError):
@@ -224,6 +234,14 @@ def lib():
     if hasattr(L, "sg_dictionary_rows"): L.sg_dictionary_rows.argtypes = [vp, vp, vp, vp, u32, u32, u64, vp, u64, vp, C.POINTER(u64)]
     if hasattr(L, "sg_suggest_batch_strings"): L.sg_suggest_batch_strings.argtypes = [vp, vp, vp, u32, i32, dbl, u32, vp, vp, vp, vp, vp, u64, vp, C.POINTER(u64)]
     if hasattr(L, "sg_autocomplete_batch_strings"): L.sg_autocomplete_batch_strings.argtypes = [vp, vp, vp, u32, u32, vp, vp, vp, vp, u64, vp, C.POINTER(u64)]
+    ecp = C.POINTER(SgEditConfig)
+    if hasattr(L, "sg_edit_rows_device"): L.sg_edit_rows_device.argtypes = [vp, ecp, vp, vp, vp, vp, vp, u32, u32, u64, vp, vp, vp]
+    if hasattr(L, "sg_edit_rows"): L.sg_edit_rows.argtypes = [vp, ecp, vp, vp, vp, vp, vp, u32, u32, u64, vp]
+    if hasattr(L, "sg_edit_rerank_device"): L.sg_edit_rerank_device.argtypes = [vp, ecp, vp, vp, vp, vp, vp, vp, u32, u32, u64, u32, vp, vp, vp]
+    if hasattr(L, "sg_edit_rerank"): L.sg_edit_rerank.argtypes = [vp, ecp, vp, vp, vp, vp, vp, vp, u32, u32, u64, u32, vp]
+    if hasattr(L, "sg_suggest_batch_edit"): L.sg_suggest_batch_edit.argtypes = [vp, vp, vp, u32, i32, dbl, u32, vp, ecp, u32, vp, vp, vp, vp]
+    if hasattr(L, "sg_debug_edit_slice_bytes"): L.sg_debug_edit_slice_bytes.argtypes = [u64]
+    if hasattr(L, "sg_debug_edit_bitvector"): L.sg_debug_edit_bitvector.argtypes = [i32, vp, u32, vp, u32, vp]
     _lib = L
     return L
 

@@ -81,6 +81,8 @@ struct sg_dictionary {
   std::vector<uint8_t> h_blob;
   DeviceBlock mem;                     // device-resident: owns the two arrays of `view`
   DictView view{nullptr, nullptr, 0};
+  // device-resident: the handle's own copy of the simple lower-case pairs (edit_rank.inc folds case without an sg_index)
+  const uint32_t* d_lower_from = nullptr; const uint32_t* d_lower_to = nullptr; uint32_t n_lower = 0;
 };
 
 namespace {
@@ -236,7 +238,12 @@ int dictionary_make(size_t n, const std::function<const uint8_t*(size_t, uint64_
     if (int rc = d->mem.upload(d->h_offs, &d->view.doc_offs)) return rc;
     if (int rc = d->mem.upload(d->h_blob, &d->view.blob)) return rc;
     d->view.n_docs = d->n_docs;
-    std::vector<uint64_t>().swap(d->h_offs);     // (the device copy is the dictionary: no second one on the host)
+    std::vector<uint32_t> lf, lt;
+    for (const auto& pr : kLowerPairs) { lf.push_back(pr.from); lt.push_back(pr.to); }
+    if (int rc = d->mem.upload(lf, &d->d_lower_from)) return rc;
+    if (int rc = d->mem.upload(lt, &d->d_lower_to)) return rc;
+    d->n_lower = (uint32_t)lf.size();
+    std::vector<uint64_t>().swap(d->h_offs);    // (the device copy is the dictionary: no second one on the host)
     std::vector<uint8_t>().swap(d->h_blob);
   }
   *out = d.release();

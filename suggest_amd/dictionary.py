@@ -28,6 +28,16 @@ def split_text(text, text_offs):
     return [b[o[i]:o[i + 1]] for i in range(len(o) - 1)]
 
 
+EDIT_MODES = {"levenshtein": _lib.SG_EDIT_LEVENSHTEIN, "osa": _lib.SG_EDIT_OSA}
+
+
+def edit_config(mode="levenshtein", fold_case=True, max_distance=None):
+    """sg_edit_config: mode "levenshtein" or "osa" (adjacent transpositions at cost 1), max_distance None: no bound"""
+    if mode not in EDIT_MODES and mode not in EDIT_MODES.values():
+        raise ValueError("unknown edit mode %r" % (mode,))
+    return _lib.SgEditConfig(EDIT_MODES.get(mode, mode), 1 if fold_case else 0, _lib.SG_EDIT_NONE if max_distance is None else int(max_distance), 0)
+
+
 class DeviceDictionary:
     def __init__(self, lines=None, blob=None, offs=None, device=0, _handle=None):
         """`lines`: a list of str / bytes in docID order, or (blob, offs) as pack_strings returns them (sg_dictionary_upload).
@@ -122,6 +132,69 @@ class DeviceDictionary:
         with self._use() as h:
             _lib.check(_lib.lib().sg_dictionary_rows_device(h, d_ids, d_counts, d_row_offs, int(n_rows), int(row), int(slots), d_text, int(text_cap),
                                                             d_text_offs, d_info, stream))
+
+    @staticmethod
+    def _edit_rows(queries, ids, counts, row_offs, blob, offs):
+        if blob is None:
+            blob, offs = pack_strings(queries)
+        blob = np.ascontiguousarray(blob, dtype=np.uint8)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        counts = np.ascontiguousarray(counts, dtype=np.uint32).reshape(-1)
+        n_rows = counts.size
+        if len(offs) - 1 != n_rows:
+            raise ValueError("one query per row: %d queries, %d rows" % (len(offs) - 1, n_rows))
+        if row_offs is None:
+            row = ids.shape[1] if ids.ndim == 2 else (ids.size // n_rows if n_rows else 0)
+        else:
+            row = 0
+            row_offs = np.ascontiguousarray(row_offs, dtype=np.uint64)
+        return blob, offs, counts, n_rows, int(row), row_offs
+
+    def edit_distances(self, queries, ids, counts, row_offs=None, mode="levenshtein", fold_case=True, blob=None, offs=None):
+        """sg_edit_rows -> distances (u32, shaped as ids): the edit distance between row i's query and each of its entries, over
+        runes; 0xFFFFFFFF where a slot holds no entry.  Geometry as rows().  An id outside the dictionary raises."""
+        ids = np.ascontiguousarray(ids, dtype=np.uint32)
+        blob, offs, counts, n_rows, row, row_offs = self._edit_rows(queries, ids, counts, row_offs, blob, offs)
+        dist = np.zeros(ids.shape, dtype=np.uint32)
+        cfg = edit_config(mode, fold_case, None)
+        with self._use() as h:
+            _lib.check(_lib.lib().sg_edit_rows(h, C.byref(cfg), blob.ctypes.data if blob.size else None, offs.ctypes.data, ids.ctypes.data if ids.size else None,
+                                               counts.ctypes.data if n_rows else None, None if row_offs is None else row_offs.ctypes.data, n_rows, row,
+                                               ids.size, dist.ctypes.data if ids.size else None))
+        return dist
+
+    def edit_rerank(self, queries, ids, counts, scores=None, row_offs=None, k_out=None, mode="levenshtein", fold_case=True, max_distance=None, blob=None,
+                    offs=None):
+        """sg_edit_rerank -> (ids, scores or None, distances, counts), copies: every row stably re-ranked by (distance ascending, the
+        order it had), entries above max_distance removed, at most k_out kept (None: the row), tails zeroed.  The exact top-k by
+        edit distance among the row's entries — not over the whole dictionary."""
+        ids = np.array(ids, dtype=np.uint32, order="C")
+        blob, offs, counts, n_rows, row, row_offs = self._edit_rows(queries, ids, counts, row_offs, blob, offs)
+        counts = counts.copy()
+        if scores is not None:
+            scores = np.array(scores, dtype=np.float64, order="C")
+        dist = np.zeros(ids.shape, dtype=np.uint32)
+        if k_out is None:
+            k_out = max(1, row if row_offs is None else ids.size)
+        cfg = edit_config(mode, fold_case, max_distance)
+        with self._use() as h:
+            _lib.check(_lib.lib().sg_edit_rerank(h, C.byref(cfg), blob.ctypes.data if blob.size else None, offs.ctypes.data, ids.ctypes.data if ids.size else None,
+                                                 None if scores is None else scores.ctypes.data, counts.ctypes.data if n_rows else None,
+                                                 None if row_offs is None else row_offs.ctypes.data, n_rows, row, ids.size, int(k_out),
+                                                 dist.ctypes.data if ids.size else None))
+        return ids, scores, dist, counts
+
+    def edit_rows_device(self, config, d_q, d_q_offs, d_ids, d_counts, d_row_offs, n_rows, row, slots, d_dist, d_info, stream=0):
+        """sg_edit_rows_device: raw device pointers, asynchronous on `stream`.  d_dist: slots u32; d_info: 2 u64."""
+        with self._use() as h:
+            _lib.check(_lib.lib().sg_edit_rows_device(h, C.byref(config), d_q, d_q_offs, d_ids, d_counts, d_row_offs, int(n_rows), int(row), int(slots), d_dist,
+                                                      d_info, stream))
+
+    def edit_rerank_device(self, config, d_q, d_q_offs, d_ids, d_scores, d_counts, d_row_offs, n_rows, row, slots, k_out, d_dist, d_info, stream=0):
+        """sg_edit_rerank_device: as edit_rows_device, and the rows re-ranked in place (d_scores None: autocomplete rows)"""
+        with self._use() as h:
+            _lib.check(_lib.lib().sg_edit_rerank_device(h, C.byref(config), d_q, d_q_offs, d_ids, d_scores, d_counts, d_row_offs, int(n_rows), int(row),
+                                                        int(slots), int(k_out), d_dist, d_info, stream))
 
     def get(self, doc_id):
         """Dictionary.Get"""

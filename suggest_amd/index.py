@@ -506,6 +506,31 @@ class NGramIndex:
                 sc.ctypes.data, cnt.ctypes.data, dh, tp, cap, op, need))
         return ids, sc, cnt, text, text_offs
 
+    def suggest_batch_edit(self, dictionary, queries=None, metric="jaccard", similarity=0.5, k_candidates=64, k=10, mode="levenshtein", fold_case=True,
+                           max_distance=None, blob=None, offs=None):
+        """sg_suggest_batch_edit -> (ids, scores, distances, counts), rows of k: the k_candidates best of every query by the q-gram
+        metric, of those the k nearest by edit distance to the query (ties: score descending, docID ascending) — the exact top-k
+        AMONG THE CANDIDATES THE SEARCH RETURNED, not over the whole dictionary.  Strings come from `dictionary` on the device."""
+        from .dictionary import edit_config
+        if blob is None:
+            blob, offs = pack_strings(queries)
+        blob = np.ascontiguousarray(blob, dtype=np.uint8)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        n_q = len(offs) - 1
+        ids = np.zeros((n_q, k), dtype=np.uint32)
+        sc = np.zeros((n_q, k), dtype=np.float64)
+        dist = np.zeros((n_q, k), dtype=np.uint32)
+        cnt = np.zeros(n_q, dtype=np.uint32)
+        code = resolve(metric).code
+        if code is None:
+            raise ValueError("suggest_batch_edit takes the metrics with a device twin")
+        cfg = edit_config(mode, fold_case, max_distance)
+        with self._use() as h, dictionary._use() as dh:
+            _lib.check(_lib.lib().sg_suggest_batch_edit(h, blob.ctypes.data if blob.size else None, offs.ctypes.data, n_q, code, float(similarity),
+                                                        int(k_candidates), dh, C.byref(cfg), int(k), ids.ctypes.data, sc.ctypes.data, dist.ctypes.data,
+                                                        cnt.ctypes.data))
+        return ids, sc, dist, cnt
+
     def autocomplete_batch_strings(self, dictionary, queries=None, limit=10, blob=None, offs=None, text_cap=None):
         """sg_autocomplete_batch_strings -> (ids, counts, text, text_offs), as suggest_batch_strings"""
         if blob is None:

@@ -17,28 +17,54 @@ from .metric import resolve
 
 
 class ResultItem:
-    """pkg/suggest/service.go:12-17"""
-    __slots__ = ("score", "value")
+    """pkg/suggest/service.go:12-17; distance: the edit distance to the query where a search re-ranked by it, else None"""
+    __slots__ = ("score", "value", "distance")
 
-    def __init__(self, score, value):
-        self.score, self.value = score, value
+    def __init__(self, score, value, distance=None):
+        self.score, self.value, self.distance = score, value, distance
 
     def __repr__(self):
-        return "ResultItem(score=%r, value=%r)" % (self.score, self.value)
+        if self.distance is None:
+            return "ResultItem(score=%r, value=%r)" % (self.score, self.value)
+        return "ResultItem(score=%r, value=%r, distance=%r)" % (self.score, self.value, self.distance)
 
     def __eq__(self, o):
-        return isinstance(o, ResultItem) and (self.score, self.value) == (o.score, o.value)
+        return isinstance(o, ResultItem) and (self.score, self.value, self.distance) == (o.score, o.value, o.distance)
+
+
+class EditDistance:
+    """A second ranking stage for SearchConfig(rerank=...): `candidates` per query by the q-gram metric, of those the top_k nearest
+    by edit distance over runes (transpositions: optimal string alignment instead of Levenshtein; max_distance None: no bound).
+    The exact top-k by edit distance AMONG THE CANDIDATES THE Q-GRAM SEARCH RETURNED, not over the whole dictionary.  Needs a
+    Service(device_dictionary=True) and a metric with a device twin."""
+
+    def __init__(self, candidates=64, transpositions=False, fold_case=True, max_distance=None):
+        if candidates <= 0:
+            raise ValueError("candidates should be greater or equal to 1")
+        if max_distance is not None and not 0 <= max_distance <= 0xFFFFFFFF:
+            raise ValueError("max_distance should be in 0 .. 2^32 - 1, or None")
+        self.candidates, self.transpositions, self.fold_case, self.max_distance = int(candidates), bool(transpositions), bool(fold_case), max_distance
+
+    @property
+    def mode(self):
+        return "osa" if self.transpositions else "levenshtein"
+
+    def key(self):
+        return (self.candidates, self.transpositions, self.fold_case, self.max_distance)
 
 
 class SearchConfig:
-    """NewSearchConfig — pkg/suggest/search.go:18-35 (same validation, same messages)"""
+    """NewSearchConfig — pkg/suggest/search.go:18-35 (same validation, same messages); rerank: an EditDistance, or None"""
 
-    def __init__(self, query, top_k, metric, similarity):
+    def __init__(self, query, top_k, metric, similarity, rerank=None):
         if top_k <= 0:
             raise ValueError("topK should be greater or equal to 1")
         if similarity <= 0 or similarity > 1:
             raise ValueError("similarity shouble be in (0.0, 1.0]")
+        if rerank is not None and top_k > rerank.candidates:
+            raise ValueError("topK should not be above the candidates of the re-rank")
         self.query, self.top_k, self.metric, self.similarity = query, int(top_k), resolve(metric), float(similarity)
+        self.rerank = rerank
 
 
 def read_dictionary(path):
@@ -168,7 +194,33 @@ class Service:
         return v.decode("utf-8", "replace") if isinstance(v, (bytes, bytearray)) else v
 
     # -- Suggest / Autocomplete (service.go:105-173) --
+    def _suggest_edit(self, dict_name, queries, top_k, metric, similarity, rerank):
+        """rows of ResultItem with a distance (None for a query the plain call flags): search and rank on the device"""
+        index, dictionary = self._lookup(dict_name)
+        on_device = self._lookup_device(dict_name)
+        if on_device is None:
+            raise ValueError("a re-rank by edit distance needs Service(device_dictionary=True)")
+        if resolve(metric).code is None:
+            raise ValueError("a re-rank by edit distance takes the metrics with a device twin")
+        ids, sc, dist, cnt = index.suggest_batch_edit(on_device, queries, metric, similarity, rerank.candidates, top_k, mode=rerank.mode,
+                                                      fold_case=rerank.fold_case, max_distance=rerank.max_distance)
+        out = []
+        for i in range(len(queries)):
+            c = int(cnt[i])
+            if c >= _lib.SG_COUNT_TOO_LONG:
+                out.append(None)
+                continue
+            out.append([ResultItem(float(sc[i, j]), self._value(dictionary, int(ids[i, j])), int(dist[i, j])) for j in range(c)])
+        return out, cnt
+
     def suggest(self, dict_name, config):
+        if getattr(config, "rerank", None) is not None:
+            rows, cnt = self._suggest_edit(dict_name, [config.query], config.top_k, config.metric, config.similarity, config.rerank)
+            if rows[0] is None:
+                if int(cnt[0]) == _lib.SG_COUNT_TOO_LONG:
+                    raise ValueError("query has more than %d n-grams" % _lib.SG_MAX_QUERY_TERMS)
+                raise RuntimeError("query window is empty: the reference panics or dead-locks here (suggester.go:62)")
+            return rows[0]
         index, dictionary = self._lookup(dict_name)
         cands = index.suggest(config.query, config.similarity, config.metric, config.top_k)
         return [ResultItem(score, self._value(dictionary, doc)) for doc, score in cands]
@@ -178,8 +230,10 @@ class Service:
         return [ResultItem(0, self._value(dictionary, doc)) for doc in index.autocomplete(query, limit)]
 
     # -- additive batch API --
-    def suggest_batch(self, dict_name, queries, top_k, metric, similarity):
-        SearchConfig("", top_k, metric, similarity)
+    def suggest_batch(self, dict_name, queries, top_k, metric, similarity, rerank=None):
+        SearchConfig("", top_k, metric, similarity, rerank)
+        if rerank is not None:
+            return self._suggest_edit(dict_name, list(queries), top_k, metric, similarity, rerank)[0]
         index, dictionary = self._lookup(dict_name)
         on_device = self._lookup_device(dict_name)
         if on_device is not None and resolve(metric).code is not None:
@@ -209,6 +263,8 @@ class Service:
         does not answer either (as suggest_batch).  Equal (metric, similarity, topK) share a table entry; more than 256 distinct
         ones go in several calls."""
         index, dictionary = self._lookup(dict_name)
+        if any(getattr(c, "rerank", None) is not None for c in configs):
+            raise ValueError("suggest_many does not re-rank: use suggest or suggest_batch for a SearchConfig with rerank=")
         out = [None] * len(configs)
         todo = list(range(len(configs)))
         while todo:
