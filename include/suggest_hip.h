@@ -523,7 +523,8 @@ int sg_debug_knob(const sg_index* index, uint32_t i, char name[32], int32_t out[
  * kernel can read safely — capi.inc, "Test-only poison"), so that a read of a word the call did not write shows as a wrong row.
  * Rows past a query's count then hold the pattern instead of zeros.  on = 0: off (the default).  sg_debug_poison_stats: bytes poisoned
  * by the calling thread since its last call, per region — out = {split queue / HBM top-k rows / ordered list (SCRATCH_ROWS),
- * pipeline fb_list, tokeniser launch, long-query list, Predict rows, result ids + aux, result scores, result counts}; clears them. */
+ * pipeline fb_list, tokeniser launch, long-query list, Predict rows, result ids + aux (and the other u32 / u64 result rows of a
+ * host-buffer call: edit distances, sg_dictionary_rows' text offsets, sentence word counts), result scores, result counts}; clears them. */
 int sg_debug_poison(uint32_t on);
 int sg_debug_poison_stats(uint64_t out[8]);
 /* Test hooks (no GPU needed): the carving of a launch's SCRATCH_ROWS block for n_q queries, top-k k, split queries on / off and the
@@ -532,6 +533,14 @@ int sg_debug_poison_stats(uint64_t out[8]);
  * ovf, cand_n, fb_list, bytes, piece, vrec_words, ovf_cap, SG_PIPE_REC_STRIDE, SG_PIPE_OVF_WORDS, SG_PIPE_PIECE}.  Offsets in bytes. */
 int sg_debug_rows_layout(uint32_t n_q, uint32_t k, int32_t split, int32_t reorder, uint64_t out[16]);
 int sg_debug_pipe_layout(uint32_t n_q, uint32_t cand_cap, uint64_t out[12]);
+/* Test hook (no GPU needed): the regions a host-buffer call declares and the device block made of them.  kind: 0 a search of n queries
+ * and rows of k (flags bit 0: scores, bit 1: aux), 1 the same with the text offsets of a _strings call, 2 a mixed call (`rows` slots in
+ * all), 3 Predict (k = topK), 4 sg_dictionary_rows (n rows, `rows` slots; bit 2: ragged), 5 sg_edit_rows and 6 sg_edit_rerank (bit 0:
+ * scores, bit 2: ragged), 7 sg_lm_score_text_batch (bit 0: words, bit 1: unknown), 8 sg_lm_score_word_ids_batch; blob_bytes: the bytes
+ * of the queries / text / ids.  out[0] = the number of regions, [0, out[1]) the one range copied back, [out[2], out[3]) the one range
+ * copied in, out[4] the block's bytes; then four words per region in the order of declaration: offset, bytes, alignment, direction
+ * (1 in, 2 out, 3 both ways). */
+int sg_debug_io_layout(uint32_t kind, uint32_t n, uint32_t k, uint32_t flags, uint64_t blob_bytes, uint64_t rows, uint64_t out[45]);
 /* [r6] Test hook: out[0] = the device ordinal of replica number `replica`, out[1..7] = the device its posting store, seg_off, orig_of,
  * forward-index records and terms, term table and counter block are resident on (-1: null).  All must equal out[0]. */
 int sg_debug_replica_devices(sg_index* index, uint32_t replica, int32_t out[8]);
@@ -676,7 +685,8 @@ int sg_autocomplete_batch_strings(sg_index* index, const uint8_t* q_utf8, const 
  * The _device calls take device pointers, are asynchronous on `stream`, write nothing of any handle and may be called from any number
  * of threads; a host-resident handle is refused (unsupported).  On that route a query of more than 65 536 bytes gets no distances:
  * its entries stay 0xFFFFFFFF and are counted in info[1].  sg_edit_rows / sg_edit_rerank take host buffers; with a host-resident
- * handle they are a plain host loop and need no GPU.
+ * handle they are a plain host loop and need no GPU; with a device handle they are host-buffer calls like sg_suggest_batch (q_offs
+ * may start anywhere; a call whose rows pass 64 MiB copies straight from and to the caller's arrays).
  * sg_suggest_batch_edit: search and rank in one call — k_candidates per query by the q-gram metric, of those the k nearest by edit
  * distance; rows of k; one staging in, one copy out, one wait.  Invalid argument: null pointers, an unknown mode, k == 0,
  * k > k_candidates, k_candidates above SG_MAX_TOPK; unsupported: a dictionary that is host-resident or not on the device of the

@@ -24,7 +24,7 @@ EXPORTS = [
     "sg_lm_score_word_ids", "sg_lm_next_score", "sg_lm_tokenize", "sg_spell_index_build", "sg_spell_predict_batch", "sg_spell_predict_batch_device",
     "sg_index_replicate", "sg_index_replicas", "sg_suggest_batch_multi", "sg_autocomplete_batch_multi", "sg_suggest_one", "sg_autocomplete_one", "sg_autocomplete_one_from", "sg_autocomplete_batch_from",
     "sg_lm_load_google_ex", "sg_lm_load_binary", "sg_lm_level", "sg_lm_order", "sg_index_tune", "sg_index_forward", "sg_autocomplete_algorithmic_bytes", "sg_debug_pairsort", "sg_debug_tune_choice", "sg_debug_pipe_shape", "sg_debug_tune_index", "sg_debug_knob", "sg_debug_replica_devices", "sg_debug_index_array",
-    "sg_debug_poison", "sg_debug_poison_stats", "sg_debug_rows_layout", "sg_debug_pipe_layout",
+    "sg_debug_poison", "sg_debug_poison_stats", "sg_debug_rows_layout", "sg_debug_pipe_layout", "sg_debug_io_layout",
     "sg_host_alloc", "sg_host_free", "sg_suggest_submit", "sg_suggest_submit_on", "sg_autocomplete_submit", "sg_ticket_wait",
     "sg_metric_window", "sg_metric_tables_create", "sg_metric_tables_retain", "sg_metric_tables_release", "sg_suggest_batch_tables", "sg_suggest_batch_from", "sg_index_launch_stats", "sg_index_pipe_stats", "sg_index_pipe_volumes",
     "sg_lm_score_text_batch", "sg_lm_score_text_batch_device", "sg_lm_score_word_ids_batch",
@@ -116,6 +116,7 @@ def lib():
     if hasattr(L, "sg_debug_poison_stats"): L.sg_debug_poison_stats.argtypes = [vp]
     if hasattr(L, "sg_debug_rows_layout"): L.sg_debug_rows_layout.argtypes = [u32, u32, i32, i32, vp]
     if hasattr(L, "sg_debug_pipe_layout"): L.sg_debug_pipe_layout.argtypes = [u32, u32, vp]
+    if hasattr(L, "sg_debug_io_layout"): L.sg_debug_io_layout.argtypes = [u32, u32, u32, u32, u64, u64, vp]
     if hasattr(L, "sg_autocomplete_algorithmic_bytes"): L.sg_autocomplete_algorithmic_bytes.argtypes = [vp, vp, vp, u32, u32, C.POINTER(u64)]
     if hasattr(L, "sg_index_forward"): L.sg_index_forward.argtypes = [vp, u32, u32, u32, vp, vp, vp]
     if hasattr(L, "sg_index_replicas"): L.sg_index_replicas.argtypes = [vp, vp, u32]

@@ -1,5 +1,5 @@
 // dict_rows.inc — result rows as strings from a dictionary held in HBM (sg_dictionary, include/suggest_hip.h; DESIGN.md §5c),
-// included by engine.hip after mixed_batch.inc (it uses host_call.inc's run_host_call, HostBufs / IoLayout and host_ctx, search_api.inc's
+// included by engine.hip after mixed_batch.inc (it uses host_call.inc's run_host_call and IoCall, search_api.inc's
 // search_enqueue, handles.inc's open_search, capi.inc's stream_scratch and poison_fill, d_copy_bytes, kCountFlagMin, read_cdb_words,
 // HIP_TRY).  The reference's Service.Suggest maps every docID
 // of a row through dict.Get (pkg/suggest/service.go:129-136); here the rows of any search stay on the device and
@@ -257,6 +257,15 @@ int dict_check_rows_args(const sg_dictionary* dict, const void* ids, const void*
   return dict_check_geometry(row_offs, n_rows, row, slots);
 }
 
+// sg_dictionary_rows on a device handle: the rows go in (row_offs null: an empty region); the slots + 1 text offsets come back (the
+// scan writes every one: poisoned, never cleared); the step's two info words stay in the block — dict_text_enqueue reads them at
+// its own wait.  The text itself is not part of the block.
+enum { DR_TEXT_OFFS = 0, DR_INFO, DR_ROW_OFFS, DR_IDS, DR_COUNTS };
+IoCall dict_rows_io(const uint32_t* ids, const uint32_t* counts, const uint64_t* row_offs, uint32_t n_rows, uint64_t slots, uint64_t* text_offs) {
+  return IoCall().add(IO_OUT, text_offs, ((size_t)slots + 1) * 8, 8, false, PZ_OUT_IDS).add(IO_OUT, nullptr, 16, 8)
+      .add(IO_IN, row_offs, row_offs ? ((size_t)n_rows + 1) * 8 : 0, 16).add(IO_IN, ids, (size_t)slots * 4, 16).add(IO_IN, counts, (size_t)n_rows * 4, 16);
+}
+
 // sg_suggest_batch_strings / sg_autocomplete_batch_strings: the plain call's staging, launch and copy-out, with the materialise
 // step between the launch and the copy-out
 int strings_host_call(sg_index* index, const uint8_t* q, const uint64_t* offs, uint32_t n_q, const LaunchReq& r, uint32_t* ids, double* scores,
@@ -269,23 +278,17 @@ int strings_host_call(sg_index* index, const uint8_t* q, const uint64_t* offs, u
   if (int rc = dict_check_geometry(nullptr, n_q, r.k, slots)) return rc;
   if (needed) *needed = 0;
   if (n_q == 0) { text_offs[0] = 0; return SG_OK; }
-  HostBufs b = search_bufs(q, offs, n_q, r, ids, scores, counts, nullptr);
-  b.text_offs = text_offs;
-  const Enqueue search = search_enqueue(index, rep, r, b);
-  int status = SG_OK;
-  std::string status_text;
-  const int rc = run_host_call(rep->device, b, true, [&](char* dev, const IoLayout& io, hipStream_t st) -> int {
-    if (int rc2 = search(dev, io, st)) return rc2;
-    uint64_t* d_toffs = (uint64_t*)(dev + io.toffs);
-    uint64_t* d_info = d_toffs + slots + 1;         // (the two words io_layout leaves behind the offsets)
-    if (int rc2 = dict_offsets_enqueue(dict, (const uint32_t*)(dev + io.ids), (const uint32_t*)(dev + io.cnt), nullptr, n_q, r.k, slots, d_toffs, d_info, st)) return rc2;
-    if (int rc2 = dict_text_enqueue(dict, (const uint32_t*)(dev + io.ids), d_toffs, d_info, slots, text, text_cap, needed, &status, st)) return rc2;
-    if (status) status_text = g_err;
-    return SG_OK;
+  // a search's regions and, behind its rows in the one copy back, the text offsets and the step's two info words
+  const IoCall call = search_io(q, offs, n_q, slots, ids, r.autocomplete ? nullptr : scores, counts, nullptr, true, text_offs);
+  const Enqueue search = search_enqueue(index, rep, r, offs, n_q);
+  int status = SG_OK;        // (answered once the rows are out; the step's error text stands: nothing behind it sets one unless it fails)
+  const int rc = run_host_call(rep->device, call, [&](const IoCall& io, hipStream_t st) -> int {
+    if (int rc2 = search(io, st)) return rc2;
+    if (int rc2 = dict_offsets_enqueue(dict, io.at<uint32_t>(IO_IDS), io.at<uint32_t>(IO_COUNTS), nullptr, n_q, r.k, slots, io.at<uint64_t>(IO_TEXT_OFFS),
+                                       io.at<uint64_t>(IO_INFO), st)) return rc2;
+    return dict_text_enqueue(dict, io.at<uint32_t>(IO_IDS), io.at<uint64_t>(IO_TEXT_OFFS), io.at<uint64_t>(IO_INFO), slots, text, text_cap, needed, &status, st);
   });
-  if (rc) return rc;
-  if (status) set_error(status_text);
-  return status;
+  return rc ? rc : status;
 }
 
 }  // namespace
@@ -344,33 +347,14 @@ int sg_dictionary_rows(sg_dictionary* dict, const uint32_t* ids, const uint32_t*
   if (row_offs) for (uint32_t i = 0; i < n_rows; i++)
     if (row_offs[i + 1] < row_offs[i]) { set_error("row offsets must not decrease"); return SG_E_INVALID; }
   if (dict->device < 0) return dict_rows_host(dict, ids, counts, row_offs, n_rows, row, slots, text, text_cap, text_offs, needed);
-  DeviceGuard dg;
-  HIP_TRY(dg.set(dict->device));
-  HostCtx* ctx;
-  if (int rc = host_ctx(dict->device, &ctx)) return rc;
-  hipStream_t st = ctx->stream;
-  // the call's device block: [text_offs | info] — one copy back — then the inputs
-  Carve c;
-  const size_t o_toffs = c.take(((size_t)slots + 1) * 8), o_info = c.take(16), o_roffs = c.take(row_offs ? ((size_t)n_rows + 1) * 8 : 0),
-               o_ids = c.take((size_t)slots * 4), o_cnt = c.take((size_t)n_rows * 4);
-  if (c.size() > ctx->dblock.cap && ctx->dblock.p) HIP_TRY(hipStreamSynchronize(st));
-  if (int rc = ctx->dblock.grow(c.size())) return rc;
-  char* dev = (char*)ctx->dblock.p;
-  struct Drain { hipStream_t st; ~Drain() { (void)hipStreamSynchronize(st); } } drain{st};   // (the block is the next call's too)
-  if (row_offs) HIP_TRY(hipMemcpyAsync(dev + o_roffs, row_offs, ((size_t)n_rows + 1) * 8, hipMemcpyHostToDevice, st));
-  if (slots && ids) HIP_TRY(hipMemcpyAsync(dev + o_ids, ids, (size_t)slots * 4, hipMemcpyHostToDevice, st));
-  if (n_rows) HIP_TRY(hipMemcpyAsync(dev + o_cnt, counts, (size_t)n_rows * 4, hipMemcpyHostToDevice, st));
-  uint64_t* d_toffs = (uint64_t*)(dev + o_toffs);
-  uint64_t* d_info = (uint64_t*)(dev + o_info);
-  if (int rc = dict_offsets_enqueue(dict, (const uint32_t*)(dev + o_ids), (const uint32_t*)(dev + o_cnt), row_offs ? (const uint64_t*)(dev + o_roffs) : nullptr,
-                                    n_rows, row, slots, d_toffs, d_info, st)) return rc;
-  int status = SG_OK;
-  if (int rc = dict_text_enqueue(dict, (const uint32_t*)(dev + o_ids), d_toffs, d_info, slots, text, text_cap, needed, &status, st)) return rc;
-  const std::string status_text = status ? g_err : std::string();
-  HIP_TRY(hipMemcpyAsync(text_offs, d_toffs, ((size_t)slots + 1) * 8, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  if (status) set_error(status_text);
-  return status;
+  if (n_rows == 0 || slots == 0) { std::fill(text_offs, text_offs + slots + 1, 0); if (needed) *needed = 0; return SG_OK; }   // (no entry)
+  int status = SG_OK;        // (as in strings_host_call)
+  const int rc = run_host_call(dict->device, dict_rows_io(ids, counts, row_offs, n_rows, slots, text_offs), [&](const IoCall& io, hipStream_t st) -> int {
+    if (int rc2 = dict_offsets_enqueue(dict, io.at<uint32_t>(DR_IDS), io.at<uint32_t>(DR_COUNTS), row_offs ? io.at<uint64_t>(DR_ROW_OFFS) : nullptr, n_rows, row, slots,
+                                       io.at<uint64_t>(DR_TEXT_OFFS), io.at<uint64_t>(DR_INFO), st)) return rc2;
+    return dict_text_enqueue(dict, io.at<uint32_t>(DR_IDS), io.at<uint64_t>(DR_TEXT_OFFS), io.at<uint64_t>(DR_INFO), slots, text, text_cap, needed, &status, st);
+  });
+  return rc ? rc : status;
   SG_GUARD_END(SG_RC)
 }
 

@@ -1,6 +1,6 @@
 // edit_rank.inc — result rows ranked by edit distance against the dictionary held in HBM (include/suggest_hip.h; DESIGN.md §5d),
 // included by engine.hip after dict_rows.inc (it uses its DictView, sg_dictionary, dict_check_geometry and t_dict, host_call.inc's
-// run_host_call / HostBufs / IoLayout / host_ctx, search_api.inc's search_req and no_long_queries, handles.inc's open_search, capi.inc's
+// run_host_call / IoCall / search_io, search_api.inc's search_req and no_long_queries, handles.inc's open_search, capi.inc's
 // launch, stream_scratch, Carve and the poison, d_next_rune, d_lower_pairs, kCountFlagMin, HIP_TRY).
 //
 // The second stage of the classical q-gram count filter: the rows a search returned are verified and ranked by Levenshtein or
@@ -504,7 +504,7 @@ void edit_host_rows(const sg_dictionary* dict, const sg_edit_config& cfg, const 
 // the rows' kept counts, the permuted rows and the sort's working memory; sg_suggest_batch_edit: the candidate rows besides.
 struct EditLayout {
   size_t long_list = 0, long_mem = 0, keys_in = 0, keys_out = 0, vals_in = 0, vals_out = 0, kept = 0, t_ids = 0, t_scores = 0, t_dist = 0, tmp = 0,
-         c_ids = 0, c_scores = 0, c_counts = 0, c_dist = 0, info = 0, bytes = 0;
+         c_ids = 0, c_scores = 0, c_counts = 0, c_dist = 0, bytes = 0;
   size_t tmp_bytes = 0;
   uint64_t long_region = 0, long_mask_words = 0; uint32_t long_pairs = 0, long_w = 0, long_grid = 0;
   bool sort = false;
@@ -535,7 +535,6 @@ int edit_layout(uint32_t n_rows, uint32_t row, bool ragged, uint64_t slots, uint
   }
   if (cand_rows) {
     L.c_scores = c.take((size_t)slots * 8); L.c_ids = c.take((size_t)slots * 4); L.c_dist = c.take((size_t)slots * 4); L.c_counts = c.take((size_t)n_rows * 4);
-    L.info = c.take(16);
   }
   L.bytes = c.size();
   *out = L;
@@ -636,6 +635,17 @@ int edit_device_call(sg_dictionary* dict, const sg_edit_config* cfg, const void*
   return rerank ? edit_rerank_enqueue(*cfg, r, k_out, L, (char*)blk, st) : SG_OK;
 }
 
+// The regions of sg_edit_rows / sg_edit_rerank on a device handle.  Out: the distances (the step fills every slot) and its info
+// words.  The rows go in, and come back where they are re-ranked.  In: the queries and the row offsets (null: an empty region).
+enum { ER_DIST = 0, ER_INFO, ER_SCORES, ER_IDS, ER_COUNTS, ER_Q_OFFS, ER_Q, ER_ROW_OFFS };
+IoCall edit_rows_io(const uint8_t* q, const uint64_t* q_offs, uint32_t* ids, double* scores, uint32_t* counts, const uint64_t* row_offs, uint32_t n_rows,
+                    uint64_t slots, uint32_t* dist, uint64_t* info, bool rerank) {
+  const IoDir rows_dir = rerank ? IO_BOTH : IO_IN;
+  return IoCall().add(IO_OUT, dist, (size_t)slots * 4, 16, false, PZ_OUT_IDS).add(IO_OUT, info, 16, 8)
+      .add(rows_dir, scores, scores ? (size_t)slots * 8 : 0, 8).add(rows_dir, ids, (size_t)slots * 4, 4).add(rows_dir, counts, (size_t)n_rows * 4, 4)
+      .add_window(q_offs, n_rows, q, 1, false).add(IO_IN, row_offs, row_offs ? ((size_t)n_rows + 1) * 8 : 0, 16);
+}
+
 // sg_edit_rows / sg_edit_rerank: host buffers
 int edit_host_call(sg_dictionary* dict, const sg_edit_config* cfg, const uint8_t* q, const uint64_t* q_offs, uint32_t* ids, double* scores, uint32_t* counts,
                    const uint64_t* row_offs, uint32_t n_rows, uint32_t row, uint64_t slots, uint32_t* dist, bool rerank, uint32_t k_out) {
@@ -653,50 +663,23 @@ int edit_host_call(sg_dictionary* dict, const sg_edit_config* cfg, const uint8_t
   uint64_t outside = 0;
   if (dict->device < 0) {
     edit_host_rows(dict, *cfg, q, q_offs, ids, scores, counts, row_offs, n_rows, row, slots, dist, rerank, k_out, &outside);
+  } else if (n_rows == 0 || slots == 0) {
+    std::fill(dist, dist + slots, kEditNone);                      // (no slot holds an entry)
   } else {
-    DeviceGuard dg;
-    HIP_TRY(dg.set(dict->device));
-    HostCtx* ctx;
-    if (int rc = host_ctx(dict->device, &ctx)) return rc;
-    hipStream_t st = ctx->stream;
-    const uint64_t q0 = n_rows ? q_offs[0] : 0, q_bytes = n_rows ? q_offs[n_rows] - q0 : 0;
-    std::vector<uint64_t> offs0((size_t)n_rows + 1, 0);
-    for (uint32_t i = 0; i <= n_rows && n_rows; i++) offs0[i] = q_offs[i] - q0;
-    // the call's device block: [scores | ids | dist | counts | info] — what comes back — then the inputs
-    Carve c;
-    const size_t o_sc = c.take(scores ? (size_t)slots * 8 : 0), o_ids = c.take((size_t)slots * 4), o_dist = c.take((size_t)slots * 4), o_cnt = c.take((size_t)n_rows * 4),
-                 o_info = c.take(16), o_qoffs = c.take(((size_t)n_rows + 1) * 8), o_roffs = c.take(row_offs ? ((size_t)n_rows + 1) * 8 : 0), o_q = c.take((size_t)q_bytes);
-    if (c.size() > ctx->dblock.cap && ctx->dblock.p) HIP_TRY(hipStreamSynchronize(st));
-    if (int rc = ctx->dblock.grow(c.size())) return rc;
-    char* dev = (char*)ctx->dblock.p;
-    struct Drain { hipStream_t st; ~Drain() { (void)hipStreamSynchronize(st); } } drain{st};   // (the block is the next call's too)
-    HIP_TRY(hipMemcpyAsync(dev + o_qoffs, offs0.data(), ((size_t)n_rows + 1) * 8, hipMemcpyHostToDevice, st));
-    if (q_bytes) HIP_TRY(hipMemcpyAsync(dev + o_q, q + q0, (size_t)q_bytes, hipMemcpyHostToDevice, st));
-    if (row_offs) HIP_TRY(hipMemcpyAsync(dev + o_roffs, row_offs, ((size_t)n_rows + 1) * 8, hipMemcpyHostToDevice, st));
-    if (slots && ids) HIP_TRY(hipMemcpyAsync(dev + o_ids, ids, (size_t)slots * 4, hipMemcpyHostToDevice, st));
-    if (slots && scores) HIP_TRY(hipMemcpyAsync(dev + o_sc, scores, (size_t)slots * 8, hipMemcpyHostToDevice, st));
-    if (n_rows) HIP_TRY(hipMemcpyAsync(dev + o_cnt, counts, (size_t)n_rows * 4, hipMemcpyHostToDevice, st));
-    EditLayout L;
-    if (int rc = edit_layout(n_rows, row, row_offs != nullptr, slots, max_q, rerank, false, &L)) return rc;
-    void* blk = nullptr;
-    if (int rc = stream_scratch(dict->device, st, L.bytes, &blk, SCRATCH_EDIT)) return rc;
-    if (poison_mode()) { if (int rc = poison_fill(blk, L.bytes, PZ_ROWS, st)) return rc; }
-    const EditRows r{(const uint8_t*)(dev + o_q), (const uint64_t*)(dev + o_qoffs), (uint32_t*)(dev + o_ids), scores ? (double*)(dev + o_sc) : nullptr,
-                     (uint32_t*)(dev + o_cnt), row_offs ? (const uint64_t*)(dev + o_roffs) : nullptr, n_rows, row, slots, (uint32_t*)(dev + o_dist),
-                     (uint64_t*)(dev + o_info)};
-    if (int rc = edit_dist_enqueue(dict, *cfg, r, L, (char*)blk, st)) return rc;
-    if (rerank) if (int rc = edit_rerank_enqueue(*cfg, r, k_out, L, (char*)blk, st)) return rc;
-    DictThread& T = t_dict;
-    if (int rc = T.pin.grow(16)) return rc;
-    HIP_TRY(hipMemcpyAsync(T.pin.p, dev + o_info, 16, hipMemcpyDeviceToHost, st));
-    if (slots) HIP_TRY(hipMemcpyAsync(dist, dev + o_dist, (size_t)slots * 4, hipMemcpyDeviceToHost, st));
-    if (rerank) {
-      if (slots) HIP_TRY(hipMemcpyAsync(ids, dev + o_ids, (size_t)slots * 4, hipMemcpyDeviceToHost, st));
-      if (slots && scores) HIP_TRY(hipMemcpyAsync(scores, dev + o_sc, (size_t)slots * 8, hipMemcpyDeviceToHost, st));
-      if (n_rows) HIP_TRY(hipMemcpyAsync(counts, dev + o_cnt, (size_t)n_rows * 4, hipMemcpyDeviceToHost, st));
-    }
-    HIP_TRY(hipStreamSynchronize(st));
-    outside = ((const uint64_t*)T.pin.p)[1];
+    uint64_t info[2] = {0, 0};
+    const int rc = run_host_call(dict->device, edit_rows_io(q, q_offs, ids, scores, counts, row_offs, n_rows, slots, dist, info, rerank), [&](const IoCall& io, hipStream_t st) -> int {
+      EditLayout L;
+      if (int rc2 = edit_layout(n_rows, row, row_offs != nullptr, slots, max_q, rerank, false, &L)) return rc2;
+      void* blk = nullptr;
+      if (int rc2 = stream_scratch(dict->device, st, L.bytes, &blk, SCRATCH_EDIT)) return rc2;
+      if (poison_mode()) { if (int rc2 = poison_fill(blk, L.bytes, PZ_ROWS, st)) return rc2; }
+      const EditRows r{io.at<uint8_t>(ER_Q), io.at<uint64_t>(ER_Q_OFFS), io.at<uint32_t>(ER_IDS), scores ? io.at<double>(ER_SCORES) : nullptr, io.at<uint32_t>(ER_COUNTS),
+                       row_offs ? io.at<uint64_t>(ER_ROW_OFFS) : nullptr, n_rows, row, slots, io.at<uint32_t>(ER_DIST), io.at<uint64_t>(ER_INFO)};
+      if (int rc2 = edit_dist_enqueue(dict, *cfg, r, L, (char*)blk, st)) return rc2;
+      return rerank ? edit_rerank_enqueue(*cfg, r, k_out, L, (char*)blk, st) : SG_OK;
+    });
+    if (rc) return rc;
+    outside = info[1];
   }
   if (outside) { set_error("docID outside the dictionary"); return SG_E_INVALID; }
   return SG_OK;
@@ -758,16 +741,11 @@ int sg_suggest_batch_edit(sg_index* index, const uint8_t* q, const uint64_t* off
   }
   if (max_q > kEditMaxQueryBytes) { set_error("a query of more than 65536 bytes"); return SG_E_INVALID; }
   const LaunchReq req = search_req(c);
-  const HostBufs b{q, offs, n_q, k, out_ids, out_scores, out_counts, out_dist};
+  IoCall call = search_io(q, offs, n_q, (uint64_t)n_q * k, out_ids, out_scores, out_counts, out_dist, true);   // (aux: the distances)
+  uint64_t info[2] = {0, 0};
+  const int io_info = (int)call.add(IO_OUT, info, 16, 8).n - 1;      // (the step's info words come back with the rows)
   const sg_edit_config config = *cfg;
-  DictThread& T = t_dict;
-  {
-    DeviceGuard dg;
-    HIP_TRY(dg.set(rep->device));
-    if (int rc = T.pin.grow(16)) return rc;
-  }
-  ((uint64_t*)T.pin.p)[1] = 0;
-  const int rc = run_host_call(rep->device, b, true, [&](char* dev, const IoLayout& io, hipStream_t st) -> int {
+  const int rc = run_host_call(rep->device, call, [&](const IoCall& io, hipStream_t st) -> int {
     EditLayout L;
     if (int rc2 = edit_layout(n_q, k_candidates, false, slots, max_q, true, true, &L)) return rc2;
     void* blkv = nullptr;
@@ -779,22 +757,46 @@ int sg_suggest_batch_edit(sg_index* index, const uint8_t* q, const uint64_t* off
       HIP_TRY(hipMemsetAsync(blk + L.c_ids, 0, (size_t)slots * 4, st));
     }
     LaunchReq r = req;
-    r.q = dev + io.q; r.offs = dev + io.offs; r.n_q = n_q; r.stream = st; r.no_long_queries = no_long_queries(offs, n_q);
+    r.q = io.at<char>(IO_Q); r.offs = io.at<char>(IO_OFFS); r.n_q = n_q; r.stream = st; r.no_long_queries = no_long_queries(offs, n_q);
     r.ids = blk + L.c_ids; r.scores = blk + L.c_scores; r.counts = blk + L.c_counts;
     if (int rc2 = launch(index, rep, r)) return rc2;
-    const EditRows rows{(const uint8_t*)(dev + io.q), (const uint64_t*)(dev + io.offs), (uint32_t*)(blk + L.c_ids), (double*)(blk + L.c_scores),
-                        (uint32_t*)(blk + L.c_counts), nullptr, n_q, k_candidates, slots, (uint32_t*)(blk + L.c_dist), (uint64_t*)(blk + L.info)};
+    const EditRows rows{io.at<uint8_t>(IO_Q), io.at<uint64_t>(IO_OFFS), (uint32_t*)(blk + L.c_ids), (double*)(blk + L.c_scores),
+                        (uint32_t*)(blk + L.c_counts), nullptr, n_q, k_candidates, slots, (uint32_t*)(blk + L.c_dist), io.at<uint64_t>(io_info)};
     if (int rc2 = edit_dist_enqueue(dict, config, rows, L, blk, st)) return rc2;
     if (int rc2 = edit_rerank_enqueue(config, rows, k, L, blk, st)) return rc2;
     const uint32_t blocks = (uint32_t)std::min<uint64_t>(((uint64_t)n_q * k + 255) / 256, 4096u);
     hipLaunchKernelGGL(edit_take_kernel, dim3(blocks), dim3(256), 0, st, rows.ids, rows.scores, rows.dist, rows.counts, n_q, k_candidates, k,
-                       (uint32_t*)(dev + io.ids), (double*)dev, (uint32_t*)(dev + io.aux), (uint32_t*)(dev + io.cnt));
+                       io.at<uint32_t>(IO_IDS), io.at<double>(IO_SCORES), io.at<uint32_t>(IO_AUX), io.at<uint32_t>(IO_COUNTS));
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(T.pin.p, blk + L.info, 16, hipMemcpyDeviceToHost, st));
     return SG_OK;
   });
   if (rc) return rc;
-  if (((const uint64_t*)T.pin.p)[1]) { set_error("docID outside the dictionary"); return SG_E_INVALID; }
+  if (info[1]) { set_error("docID outside the dictionary"); return SG_E_INVALID; }
+  return SG_OK;
+  SG_GUARD_END(SG_RC)
+}
+
+// Test hook (no GPU needed; here, behind the last kind's declaring function): the regions a host-buffer call of `kind` declares — by
+// the function its call site uses — and the block lay() makes of them.  Of the arrays only the offsets' first and last word are read.
+int sg_debug_io_layout(uint32_t kind, uint32_t n, uint32_t k, uint32_t flags, uint64_t blob_bytes, uint64_t rows, uint64_t out[45]) {
+  SG_GUARD_BEGIN
+  if (!out || n == 0 || kind > 8u) { set_error("bad argument"); return SG_E_INVALID; }
+  static uint64_t w[2];
+  uint8_t* p8 = (uint8_t*)w; uint32_t* p32 = (uint32_t*)w; double* pd = (double*)w;
+  const bool f0 = flags & 1u, f1 = flags & 2u, ragged = flags & 4u;
+  std::vector<uint64_t> offs((size_t)n + 1, 0);
+  offs[n] = kind == 8 ? blob_bytes / 4 : blob_bytes;
+  std::fill(out, out + 45, 0);
+  IoCall io;
+  if (kind <= 2) io = search_io(p8, offs.data(), n, kind == 2 ? rows : (uint64_t)n * k, p32, f0 || kind == 2 ? pd : nullptr, p32, kind == 0 && f1 ? p32 : nullptr,
+                                kind != 2, kind == 1 ? w : nullptr, kind == 2 ? p32 : nullptr);
+  else if (kind == 3) io = search_io(p8, offs.data(), n, (uint64_t)n * (k + 1), p32, nullptr, p32, nullptr, false);
+  else if (kind == 4) io = dict_rows_io(p32, p32, ragged ? w : nullptr, n, rows, w);
+  else if (kind <= 6) io = edit_rows_io(p8, offs.data(), p32, f0 ? pd : nullptr, p32, ragged ? w : nullptr, n, rows, p32, w, kind == 6);
+  else io = lm_score_io(p8, kind == 8 ? 4 : 1, offs.data(), n, pd, kind == 7 && f0 ? p32 : nullptr, kind == 7 && f1 ? p32 : nullptr);
+  io.lay();
+  for (uint64_t v : {(uint64_t)io.n, (uint64_t)io.out_hi, (uint64_t)io.in_lo, (uint64_t)io.in_hi, (uint64_t)io.total}) *out++ = v;
+  for (uint32_t i = 0; i < io.n; i++) for (uint64_t v : {(uint64_t)io.r[i].off, (uint64_t)io.r[i].bytes, (uint64_t)io.r[i].align, (uint64_t)io.r[i].dir}) *out++ = v;
   return SG_OK;
   SG_GUARD_END(SG_RC)
 }

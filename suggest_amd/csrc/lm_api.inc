@@ -365,10 +365,11 @@ int sg_spell_predict_batch(sg_index* index, sg_lm* lm, const uint8_t* q_utf8, co
   const auto held_lm = hold(lm);
   Replica* rep = find_replica(index, -1);
   if ((rc = lm_upload(lm, rep->device))) return rc;
-  const HostBufs b{q_utf8, q_offs, n_q, top_k + 1, out_ids, nullptr, out_counts, nullptr};
-  return run_host_call(rep->device, b, false, [&](char* dev, const IoLayout& io, hipStream_t st) {
-    return predict_on_device(index, lm, rep, (const uint8_t*)(dev + io.q), (const uint64_t*)(dev + io.offs), n_q, io.q_bytes, top_k, similarity,
-                             (uint32_t*)(dev + io.ids), (uint32_t*)(dev + io.cnt), st);
+  // a search's regions without scores, id rows of topK + 1, not cleared (the pipeline writes every row it counts)
+  const IoCall call = search_io(q_utf8, q_offs, n_q, (uint64_t)n_q * (top_k + 1), out_ids, nullptr, out_counts, nullptr, false);
+  return run_host_call(rep->device, call, [&](const IoCall& io, hipStream_t st) {
+    return predict_on_device(index, lm, rep, io.at<uint8_t>(IO_Q), io.at<uint64_t>(IO_OFFS), n_q, io.r[IO_Q].bytes, top_k, similarity,
+                             io.at<uint32_t>(IO_IDS), io.at<uint32_t>(IO_COUNTS), st);
   });
   SG_GUARD_END(SG_RC)
 }
@@ -417,6 +418,16 @@ static int lm_score_check(sg_lm* lm, int device, const void* offs, const void* s
   return SG_OK;
 }
 
+// The regions of a host-buffer scoring call: a score per sentence (cleared), the word and unknown-word counts where the caller
+// wants them (null: an empty region), and the sentences — n + 1 offsets counted in units of `unit` bytes (1: text, 4: word ids; they
+// go in as the byte offsets the kernels read) into `blob`
+enum { LM_SCORES = 0, LM_WORDS, LM_UNKNOWN, LM_OFFS, LM_BLOB };
+static IoCall lm_score_io(const void* blob, uint32_t unit, const uint64_t* offs, uint32_t n, double* scores, uint32_t* words, uint32_t* unknown) {
+  return IoCall().add(IO_OUT, scores, (size_t)n * 8, 16, true, PZ_OUT_SCORES).add(IO_OUT, words, words ? (size_t)n * 4 : 0, 4, true, PZ_OUT_IDS)
+      .add(IO_OUT, unknown, unknown ? (size_t)n * 4 : 0, 4, false, PZ_OUT_COUNTS)
+      .add_window(offs, n, blob, unit, unit == 1);   // (a slice of a text batch above 64 MiB is refused, as a search's is; of ids, served)
+}
+
 // host offsets: ascending, the buffer they index present, at most max_span units of it
 static int lm_check_offsets(const void* buf, const uint64_t* offs, uint32_t n, uint64_t max_span) {
   for (uint32_t i = 0; i < n; i++)
@@ -435,13 +446,9 @@ int sg_lm_score_text_batch(sg_lm* lm, int device, const uint8_t* text, const uin
   if ((rc = lm_check_offsets(text, offs, n, kLmTextMax))) return rc;
   const auto held_lm = hold(lm);
   if ((rc = lm_upload(lm, device))) return rc;
-  std::vector<uint32_t> words_tmp, unknown_tmp;                  // (the host-buffer path copies both rows back)
-  if (!out_words) { words_tmp.resize(n); out_words = words_tmp.data(); }
-  if (!out_unknown) { unknown_tmp.resize(n); out_unknown = unknown_tmp.data(); }
-  const HostBufs b{text, offs, n, 1, out_words, out_scores, out_unknown, nullptr};
-  return run_host_call(device, b, true, [&](char* dev, const IoLayout& io, hipStream_t st) {
-    return lm_score_on_device(lm, device, true, (const uint8_t*)(dev + io.q), io.q_bytes, nullptr, (const uint64_t*)(dev + io.offs), n, 0, (double*)dev,
-                              (uint32_t*)(dev + io.ids), (uint32_t*)(dev + io.cnt), st);
+  return run_host_call(device, lm_score_io(text, 1, offs, n, out_scores, out_words, out_unknown), [&](const IoCall& io, hipStream_t st) {
+    return lm_score_on_device(lm, device, true, io.at<uint8_t>(LM_BLOB), io.r[LM_BLOB].bytes, nullptr, io.at<uint64_t>(LM_OFFS), n, 0, io.at<double>(LM_SCORES),
+                              out_words ? io.at<uint32_t>(LM_WORDS) : nullptr, out_unknown ? io.at<uint32_t>(LM_UNKNOWN) : nullptr, st);
   });
   SG_GUARD_END(SG_RC)
 }
@@ -471,15 +478,8 @@ int sg_lm_score_word_ids_batch(sg_lm* lm, int device, const uint32_t* ids, const
   if ((rc = lm_check_offsets(ids, offs, n, (uint64_t)1 << 30))) return rc;
   const auto held_lm = hold(lm);
   if ((rc = lm_upload(lm, device))) return rc;
-  // the host-buffer path moves bytes: the ids as a blob, offsets in bytes from the first sentence's ids on
-  std::vector<uint64_t> boffs((size_t)n + 1);
-  for (uint32_t i = 0; i <= n; i++) boffs[i] = (offs[i] - offs[0]) * 4;
-  std::vector<uint32_t> rows_a(n), rows_b(n);                    // (the two u32 rows of the host-buffer block: unused here)
-  const HostBufs b{(const uint8_t*)(ids ? ids + offs[0] : nullptr), boffs.data(), n, 1, rows_a.data(), out_scores, rows_b.data(), nullptr};
-  const uint64_t n_ids = offs[n] - offs[0];
-  return run_host_call(device, b, true, [&](char* dev, const IoLayout& io, hipStream_t st) {
-    return lm_score_on_device(lm, device, false, nullptr, 0, (const uint32_t*)(dev + io.q), (const uint64_t*)(dev + io.offs), n, n_ids, (double*)dev,
-                              nullptr, nullptr, st);
+  return run_host_call(device, lm_score_io(ids, 4, offs, n, out_scores, nullptr, nullptr), [&](const IoCall& io, hipStream_t st) {
+    return lm_score_on_device(lm, device, false, nullptr, 0, io.at<uint32_t>(LM_BLOB), io.at<uint64_t>(LM_OFFS), n, offs[n] - offs[0], io.at<double>(LM_SCORES), nullptr, nullptr, st);
   });
   SG_GUARD_END(SG_RC)
 }

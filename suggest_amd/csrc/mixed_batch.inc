@@ -1,6 +1,6 @@
 // mixed_batch.inc — one batch whose queries differ in metric, similarity and k (sg_suggest_batch_mixed, include/suggest_hip.h;
 // DESIGN.md §5b), included by engine.hip after the host files (it uses capi.inc's launch(), stream_scratch and poison_fill,
-// host_call.inc's run_host_call and HostBufs / IoLayout, index_api.inc's replica_of_pointer, handles.inc's check_search_values).
+// host_call.inc's run_host_call and search_io, index_api.inc's replica_of_pointer, handles.inc's check_search_values).
 // The search kernels keep one (metric, similarity, k) per launch: a mixed call is one enqueue step, mixed_enqueue, around the launch() of every group —
 //   count     mixed_count_kernel: every config number checked against n_configs (a bad one raises the call's error word and is
 //             counted nowhere), a histogram over the configs, the queries' byte lengths, the sort's keys and values;
@@ -347,13 +347,11 @@ static int mixed_host_call(sg_index* index, Replica* rep, const uint8_t* q, cons
   if (rows > rows_cap) { set_error("mixed batch: rows_cap is below the sum of the queries' k"); return SG_E_INVALID; }
   if (int rc = mixed_check_index(index)) return rc;
   if (!rep) rep = find_replica(index, -1);
-  HostBufs b{q, offs, n_q, 0, ids, scores, counts, nullptr};
-  b.rows = rows; b.sel = config_of;
-  // (clear_rows is false: the scatter writes every slot of every row)
-  return run_host_call(rep->device, b, false, [&](char* dev, const IoLayout& io, hipStream_t st) {
-    const MixedIo m{(const uint8_t*)(dev + io.q), (const uint64_t*)(dev + io.offs), (const uint32_t*)(dev + io.sel),
-                    (uint32_t*)(dev + io.ids), (uint64_t*)dev, (uint32_t*)(dev + io.cnt), nullptr};
-    return mixed_enqueue(index, rep, m, n_q, configs, n_configs, n_of.data(), io.q_bytes, no_long.data(), rows, st);
+  // a search's regions with ragged rows, not cleared (the scatter writes every slot of every row), and the config numbers behind the queries
+  return run_host_call(rep->device, search_io(q, offs, n_q, rows, ids, scores, counts, nullptr, false, nullptr, config_of), [&](const IoCall& io, hipStream_t st) {
+    const MixedIo m{io.at<uint8_t>(IO_Q), io.at<uint64_t>(IO_OFFS), io.at<uint32_t>(IO_SEL),
+                    io.at<uint32_t>(IO_IDS), io.at<uint64_t>(IO_SCORES), io.at<uint32_t>(IO_COUNTS), nullptr};
+    return mixed_enqueue(index, rep, m, n_q, configs, n_configs, n_of.data(), io.r[IO_Q].bytes, no_long.data(), rows, st);
   });
 }
 

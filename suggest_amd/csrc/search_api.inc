@@ -1,4 +1,4 @@
-// search_api.inc — the host-buffer searches: search_req / search_enqueue / search_bufs / run_host, sg_suggest_batch and
+// search_api.inc — the host-buffer searches: search_req / search_enqueue / run_host, sg_suggest_batch and
 // sg_autocomplete_batch with their _from forms, and the metric-table handle with its two searches.  Uses handles.inc
 // (SearchKey, open_search), capi.inc and host_call.inc.
 
@@ -19,25 +19,20 @@ static bool no_long_queries(const uint64_t* offs, uint32_t n_q) {
   return max_len <= 112;
 }
 
-// the enqueue step of a search: launch() on the device block, with what the caller's buffers say
-static Enqueue search_enqueue(sg_index* index, Replica* rep, const LaunchReq& req, const HostBufs& b) {
-  return [=](char* dev, const IoLayout& io, hipStream_t st) {
+// the enqueue step of a search: launch() on the device block's regions (search_io's indices); aux: the call declared aux rows
+static Enqueue search_enqueue(sg_index* index, Replica* rep, const LaunchReq& req, const uint64_t* offs, uint32_t n_q, bool aux = false) {
+  return [=](const IoCall& io, hipStream_t st) {
     LaunchReq r = req;
-    r.q = dev + io.q; r.offs = dev + io.offs; r.n_q = b.n_q; r.stream = st; r.no_long_queries = no_long_queries(b.offs, b.n_q);
-    r.ids = dev + io.ids; r.scores = r.autocomplete ? nullptr : dev; r.counts = dev + io.cnt;
-    r.out_aux = b.aux ? (uint32_t*)(dev + io.aux) : nullptr;
+    r.q = io.at<char>(IO_Q); r.offs = io.at<char>(IO_OFFS); r.n_q = n_q; r.stream = st; r.no_long_queries = no_long_queries(offs, n_q);
+    r.ids = io.at<char>(IO_IDS); r.scores = r.autocomplete ? nullptr : io.at<char>(IO_SCORES); r.counts = io.at<char>(IO_COUNTS);
+    r.out_aux = aux ? io.at<uint32_t>(IO_AUX) : nullptr;
     return launch(index, rep, r);
   };
 }
-static HostBufs search_bufs(const uint8_t* q, const uint64_t* offs, uint32_t n_q, const LaunchReq& r, uint32_t* ids, double* scores,
-                            uint32_t* counts, uint32_t* aux) {
-  return HostBufs{q, offs, n_q, r.k, ids, r.autocomplete ? nullptr : scores, counts, aux};
-}
-
 static int run_host(sg_index* index, Replica* rep, const uint8_t* q, const uint64_t* offs, uint32_t n_q, const LaunchReq& r,
                     uint32_t* ids, double* scores, uint32_t* counts, uint32_t* aux = nullptr) {
-  const HostBufs b = search_bufs(q, offs, n_q, r, ids, scores, counts, aux);
-  return run_host_call(rep->device, b, true, search_enqueue(index, rep, r, b));
+  if (n_q == 0) return SG_OK;
+  return run_host_call(rep->device, search_io(q, offs, n_q, (uint64_t)n_q * r.k, ids, r.autocomplete ? nullptr : scores, counts, aux, true), search_enqueue(index, rep, r, offs, n_q, aux != nullptr));
 }
 
 int sg_suggest_batch(sg_index* index, const uint8_t* q, const uint64_t* offs, uint32_t n_q, int metric, double similarity,

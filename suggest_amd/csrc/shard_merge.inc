@@ -1,6 +1,6 @@
 // shard_merge.inc — a dictionary sharded by docID range behind one handle (sg_sharded, include/suggest_hip.h), included by
 // engine.hip after the host files (it uses capi.inc's launch(), stream_scratch and GrowBlock, index_api.inc's build_any(), tune.inc's
-// add_replica(), host_call.inc's run_host_call and io_layout, handles.inc's open_search, host_base.inc's
+// add_replica(), host_call.inc's run_host_call and IoCall, handles.inc's open_search, host_base.inc's
 // DeviceGuard, HIP_TRY).  A sharded search is one enqueue step, sharded_enqueue: the device-resident call is that step on the
 // caller's stream, a host-buffer call is host_call.inc's run_host_call around it, as every other host-buffer call is around its own.
 // SURVEY.md §8(e) / DESIGN.md §5: every shard indexes the documents [doc_lo, doc_lo + n) under local docIDs, built with the
@@ -285,7 +285,7 @@ int sharded_open(sg_sharded* h, const SearchKey& c, std::initializer_list<const 
 // with_lanes == false: every shard is searched on `st` into the calling thread's SCRATCH_SHARD block of (device, st) and merged
 // on `st` into the caller's rows at the slice's offset.  Nothing of the handle is written: no lock.
 // with_lanes == true (a host-buffer call on a handle with several lanes; d_q lies q_bytes long right behind the offsets, as in
-// IoLayout): lane 0's shards as above; every other lane searches its shards on its own stream into its own rows, copies them
+// a search's block, host_call.inc): lane 0's shards as above; every other lane searches its shards on its own stream into its own rows, copies them
 // into the SCRATCH_SHARD block behind each search and records ev_rows, which `st` waits for before the merge.  A lane on
 // another device gets one peer copy of [offsets | queries], on its own stream.  h->mu is held while this enqueues, no longer:
 // the lanes' streams order the calls of several threads, and each thread merges from a block of its own.
@@ -381,13 +381,13 @@ int sharded_enqueue(sg_sharded* h, const char* d_q, const uint64_t* d_offs, uint
 // Host buffers: a synchronous host-buffer call (run_host_call) on the merge device around the enqueue step.
 int sharded_host_call(sg_sharded* h, const uint8_t* q, const uint64_t* offs, uint32_t n_q, const LaunchReq& base, uint32_t* ids, double* scores,
                       uint32_t* counts) {
-  const HostBufs b = search_bufs(q, offs, n_q, base, ids, scores, counts, nullptr);
-  // (clear_rows is false: the merge kernel writes every slot of every row, flags included)
-  return run_host_call(h->device[0], b, false, [&](char* dev, const IoLayout& io, hipStream_t st) {
+  if (n_q == 0) return SG_OK;
+  // (the rows are not cleared: the merge kernel writes every slot of every row, flags included)
+  return run_host_call(h->device[0], search_io(q, offs, n_q, (uint64_t)n_q * base.k, ids, base.autocomplete ? nullptr : scores, counts, nullptr, false), [&](const IoCall& io, hipStream_t st) {
     LaunchReq r = base;
     r.no_long_queries = no_long_queries(offs, n_q);
-    return sharded_enqueue(h, dev + io.q, (const uint64_t*)(dev + io.offs), n_q, io.q_bytes, r, (uint32_t*)(dev + io.ids),
-                           b.scores ? (uint64_t*)dev : nullptr, (uint32_t*)(dev + io.cnt), st, h->lanes.size() > 1);
+    return sharded_enqueue(h, io.at<char>(IO_Q), io.at<uint64_t>(IO_OFFS), n_q, io.r[IO_Q].bytes, r, io.at<uint32_t>(IO_IDS),
+                           io.r[IO_SCORES].bytes ? io.at<uint64_t>(IO_SCORES) : nullptr, io.at<uint32_t>(IO_COUNTS), st, h->lanes.size() > 1);
   });
 }
 
@@ -533,19 +533,21 @@ int sg_debug_shard_merge(int device, const uint32_t* ids, const double* scores, 
   if (n_shards == 0 || n_shards > SG_MAX_SHARDS || k == 0 || k > SG_MAX_TOPK || device < 0) { set_error("sg_debug_shard_merge: bad argument"); return SG_E_INVALID; }
   if (n_q == 0) return SG_OK;
   const ShardBlock B(n_shards, n_q, k, sc);
-  const IoLayout io = io_layout(n_q, k, sc, false, 0);
+  // the merged rows as a search lays them: [scores | ids | counts]
+  Carve c;
+  const size_t slots = (size_t)n_q * k, sc_bytes = sc ? slots * 8 : 0, o_sc = c.take(sc_bytes), o_ids = c.take(slots * 4, 4), o_cnt = c.take((size_t)n_q * 4, 4);
   DeviceGuard dg;
   HIP_TRY(dg.set(device));
   DeviceBlock mem;
   char *di = nullptr, *d_o = nullptr;
   int rc;
-  if ((rc = mem.alloc(&di, block_capacity(B.bytes))) || (rc = mem.alloc(&d_o, block_capacity(io.out_bytes)))) return rc;   // (a search's GrowBlock sizes)
+  if ((rc = mem.alloc(&di, block_capacity(B.bytes))) || (rc = mem.alloc(&d_o, block_capacity(c.off)))) return rc;   // (a search's GrowBlock sizes)
   if (sc) HIP_TRY(hipMemcpy(di, scores, B.ids, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(di + B.ids, ids, B.cnt - B.ids, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(di + B.cnt, counts, B.bytes - B.cnt, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemset(d_o, 0xA5, io.out_bytes));          // (the kernel writes every slot of every row)
+  HIP_TRY(hipMemset(d_o, 0xA5, c.off));          // (the kernel writes every slot of every row)
   ShardMergeArgs a = sharded_merge_args(n_shards, doc_lo, di, B, n_q, k, sc);
-  a.out_ids = (uint32_t*)(d_o + io.ids); a.out_scores = sc ? (uint64_t*)d_o : nullptr; a.out_counts = (uint32_t*)(d_o + io.cnt);
+  a.out_ids = (uint32_t*)(d_o + o_ids); a.out_scores = sc ? (uint64_t*)(d_o + o_sc) : nullptr; a.out_counts = (uint32_t*)(d_o + o_cnt);
   hipEvent_t ev[2] = {nullptr, nullptr};
   struct Events { hipEvent_t* e; ~Events() { for (int i = 0; i < 2; i++) if (e[i]) (void)hipEventDestroy(e[i]); } } events_{ev};
   HIP_TRY(hipEventCreate(&ev[0])); HIP_TRY(hipEventCreate(&ev[1]));
@@ -556,9 +558,9 @@ int sg_debug_shard_merge(int device, const uint32_t* ids, const double* scores, 
   float ms = 0;
   HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
   t_shard_merge_ms = ms;
-  if (sc) HIP_TRY(hipMemcpy(out_scores, d_o, io.sc_bytes, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(out_ids, d_o + io.ids, io.id_bytes, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(out_counts, d_o + io.cnt, io.cnt_bytes, hipMemcpyDeviceToHost));
+  if (sc) HIP_TRY(hipMemcpy(out_scores, d_o + o_sc, sc_bytes, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(out_ids, d_o + o_ids, slots * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(out_counts, d_o + o_cnt, (size_t)n_q * 4, hipMemcpyDeviceToHost));
   return SG_OK;
   SG_GUARD_END(SG_RC)
 }

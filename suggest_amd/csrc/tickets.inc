@@ -103,8 +103,7 @@ static int async_submit(sg_index* index, const uint8_t* q, const uint64_t* offs,
   x.dev = &sl->dev; x.pin_in = &sl->pin_in; x.pin_out = &sl->pin_out;
   x.ticket = true;
   const LaunchReq r = search_req(key);
-  const HostBufs b = search_bufs(q, offs, n_q, r, ids, scores, counts, nullptr);
-  if (int rc = begin_host_call(b, true, search_enqueue(index, rep, r, b), x, &t->call)) return rc;
+  if (int rc = begin_host_call(search_io(q, offs, n_q, (uint64_t)n_q * r.k, ids, r.autocomplete ? nullptr : scores, counts, nullptr, true), search_enqueue(index, rep, r, offs, n_q), x, &t->call)) return rc;
   unbusy.keep = true;
   sg_index_retain(index);
   *out = t.release();

@@ -365,6 +365,98 @@ def test_scratch_pipe_layout_is_disjoint_and_sized():
             _assert_carved(reg, total)
 
 
+# ---- the device block of a host-buffer call (csrc/host_call.inc: the regions a call declares) ----
+
+IO_IN, IO_OUT, IO_BOTH = 1, 2, 3
+IO_KINDS = {0: "search", 1: "strings", 2: "mixed", 3: "predict", 4: "dict_rows", 5: "edit_rows", 6: "edit_rerank", 7: "lm_text", 8: "lm_ids"}
+
+
+def _io_layout(kind, n, k, flags, blob, rows):
+    import ctypes as C
+    from suggest_amd import _lib
+    out = (C.c_uint64 * 45)()
+    _lib.check(_lib.lib().sg_debug_io_layout(kind, n, k, flags, blob, rows, out))
+    v = [int(x) for x in out]
+    assert 1 <= v[0] <= 10
+    return dict(out_hi=v[1], in_lo=v[2], in_hi=v[3], total=v[4], regions=[tuple(v[5 + 4 * i:9 + 4 * i]) for i in range(v[0])])
+
+
+def _up(x, a):
+    return (x + a - 1) // a * a
+
+
+def _search_rule(n_q, slots, scores, aux, blob, text=False, sel=False):
+    """The block of a search-shaped call as it has lain since the first host-buffer path: the rule, stated here."""
+    at, reg = 0, {}
+
+    def take(name, size, align):
+        nonlocal at
+        reg[name] = _up(at, align)
+        at = reg[name] + size
+    take("scores", slots * 8 if scores else 0, 16)
+    take("ids", slots * 4, 4)
+    take("counts", n_q * 4, 4)
+    take("aux", slots * 4 if aux else 0, 4)
+    if text:
+        take("text_offs", (slots + 1) * 8 + 16, 8)            # (+ the step's two info words)
+    out_end = at
+    take("offs", (n_q + 1) * 8, 16)
+    take("blob", blob, 8)
+    if sel:
+        take("sel", n_q * 4, 4)
+    return reg, out_end, at, at + 16
+
+
+def test_host_call_block_layout():
+    """Every kind of host-buffer call over a small grid: the regions pairwise disjoint and aligned as declared; the one range
+    copied back holds exactly the out and both-ways regions, the one range copied in exactly the in and both-ways regions; 16
+    bytes follow the last region.  The search-shaped kinds lie where the rule above puts them."""
+    for kind in IO_KINDS:
+        for n in (1, 3, 1000):
+            for k in (1, 7, 64, 100):
+                for flags in range(8):
+                    for blob in ((0, 20) if kind == 8 else (0, 5)):     # (word ids: 4 bytes each)
+                        for rows in (n * k, n * k + 3, max(n * k - 1, 1)):
+                            L = _io_layout(kind, n, k, flags, blob, rows)
+                            ctx = (IO_KINDS[kind], n, k, flags, blob, rows)
+                            R = L["regions"]
+                            _assert_carved({i: (off, size, align) for i, (off, size, align, d) in enumerate(R)}, L["total"])
+                            assert all(d in (IO_IN, IO_OUT, IO_BOTH) for _, _, _, d in R), ctx
+                            last = max(off + size for off, size, _, _ in R)
+                            assert L["total"] >= last + 16 and L["in_hi"] == last, ctx
+                            for off, size, _, d in R:
+                                if not size:
+                                    continue
+                                assert (off + size <= L["out_hi"]) == bool(d & IO_OUT), (ctx, off, size, d)
+                                assert (L["in_lo"] <= off and off + size <= L["in_hi"]) == bool(d & IO_IN), (ctx, off, size, d)
+                                if d == IO_OUT:
+                                    assert off + size <= L["in_lo"], ctx
+                                if d == IO_IN:
+                                    assert off >= L["out_hi"], ctx
+                            if kind > 3:
+                                continue
+                            # ---- today's kinds: equality with the rule ----
+                            scores, aux = bool(flags & 1), bool(flags & 2)
+                            if kind == 0:
+                                want = _search_rule(n, n * k, scores, aux, blob)
+                                names = ["scores", "ids", "counts", "aux", "offs", "blob"]
+                            elif kind == 1:
+                                want = _search_rule(n, n * k, scores, False, blob, text=True)
+                                names = ["scores", "ids", "counts", "aux", "offs", "blob", "text_offs"]
+                            elif kind == 2:
+                                want = _search_rule(n, rows, True, False, blob, sel=True)
+                                names = ["scores", "ids", "counts", "aux", "offs", "blob", "sel"]
+                            else:
+                                want = _search_rule(n, n * (k + 1), False, False, blob)
+                                names = ["scores", "ids", "counts", "aux", "offs", "blob"]
+                            reg, out_end, end, total = want
+                            got = {name: R[i][0] for i, name in enumerate(names)}
+                            assert got == {name: reg[name] for name in names}, (ctx, got, reg)
+                            if kind == 1:                       # the info words: the 16 bytes behind the text offsets
+                                assert R[7][:2] == (reg["text_offs"] + (n * k + 1) * 8, 16), ctx
+                            assert (L["out_hi"], L["in_lo"], L["in_hi"], L["total"]) == (out_end, reg["offs"], end, total), ctx
+
+
 # ---- the knob table (csrc/knobs.inc; DESIGN.md §4c) ----
 
 INT32_MAX = 2**31 - 1

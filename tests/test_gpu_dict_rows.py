@@ -115,6 +115,37 @@ def test_text_cap(torch, step, n_rows, row, v):
     ref.check(host_text, host_toffs, want)
 
 
+# ---- 2b: the host-buffer route's result regions under the poison ----
+def test_host_rows_under_the_poison(torch, step):
+    """sg_dictionary_rows on a device handle is a host-buffer call like every other: its text offsets are a result region of the
+    shared path, poisoned (and counted) while sg_debug_poison is on.  Fixed rows (3 x 4, counts 0 / 2 / 4) and ragged rows: text
+    and offsets equal the restatement's and the unpoisoned call's under both pattern families."""
+    from suggest_amd import _lib
+    n_docs = len(step["lines"])
+    rng = np.random.default_rng(7)
+    fixed_ids = rng.integers(0, n_docs, size=(3, 4), dtype=np.uint32)
+    fixed_cnt = np.array([0, 2, 4], dtype=np.uint32)
+    ragged_offs = np.array([0, 0, 3, 4, 9], dtype=np.uint64)                 # rows of 0, 3, 1 and 5 slots, 2 slots of no row behind them
+    ragged_ids = rng.integers(0, n_docs, size=11, dtype=np.uint32)
+    ragged_cnt = np.array([0, 2, 1, 5], dtype=np.uint32)
+    cases = [(fixed_ids, fixed_cnt, None, ref.materialise(fixed_ids, fixed_cnt, step["blob"], step["offs"], row=4)),
+             (ragged_ids, ragged_cnt, ragged_offs, ref.materialise(ragged_ids, ragged_cnt, step["blob"], step["offs"], row_offs=ragged_offs))]
+    for ids, counts, row_offs, want in cases:
+        assert want[2] > 0 and want[3] == 0
+        plain = step["dd"].rows(ids, counts, row_offs=row_offs)
+        ref.check(plain[0], plain[1], want)
+        for family in (1, 2):
+            _lib.poison_stats()
+            with _lib.poisoned(family):
+                text, toffs = step["dd"].rows(ids, counts, row_offs=row_offs)
+                st = _lib.poison_stats()
+            ref.check(text, toffs, want)
+            assert np.array_equal(toffs, plain[1]) and np.array_equal(text[:want[2]], plain[0][:want[2]])
+            out_bytes = st["out_ids"] + st["out_scores"] + st["out_counts"]
+            print("family %d, %s rows: %s" % (family, "fixed" if row_offs is None else "ragged", st))
+            assert out_bytes >= (ids.size + 1) * 8, st                       # the text offsets at least
+
+
 # ---- 3: ragged geometry from a real mixed call ----
 MIXED = [dict(metric="jaccard", similarity=0.5, k=10), dict(metric="cosine", similarity=0.4, k=1), dict(metric="dice", similarity=0.3, k=300),
          dict(metric="overlap", similarity=0.6, k=65), dict(autocomplete=1, k=7)]

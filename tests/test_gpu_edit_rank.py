@@ -181,6 +181,79 @@ def test_ragged_rows(torch, shapes):
         assert np.array_equal(g_ids[int(ro[-1]):], ids[int(ro[-1]):])                       # the spare tail is no row's
 
 
+# ---- 2b: the host-buffer calls on the shared host-call path: slices, the poison, a block above the staging limit ----
+def _slice_batch(shapes, ragged):
+    """six rows of three slots (ragged: 3, 0, 2, 3, 1, 3), counts within the rows -> (queries, blob, offs, ids, scores, counts, row_offs)"""
+    from suggest_amd.index import pack_strings
+    rng = np.random.default_rng(515)
+    pool = shp.short_ids(shapes)
+    queries = [shp.query_of(n, seed=9) for n in (4, 0, 7, 12, 3, 9)]
+    lens = [3, 0, 2, 3, 1, 3] if ragged else [3] * 6
+    ro = np.concatenate([[0], np.cumsum(lens)]).astype(np.uint64)
+    ids = pool[rng.integers(0, len(pool), int(ro[-1]))].astype(np.uint32)
+    scores = np.round(rng.random(int(ro[-1])), 1)
+    counts = np.array([min(c, n) for c, n in zip((3, 1, 2, 3, 0, 2), lens)], dtype=np.uint32)
+    blob, offs = pack_strings(queries)
+    return queries, blob, offs, ids, scores, counts, ro
+
+
+@pytest.mark.parametrize("family", [0, 1, 2])
+@pytest.mark.parametrize("ragged", [False, True])
+def test_host_calls_on_a_slice_of_a_batch(torch, shapes, ragged, family):
+    """edit_distances and edit_rerank on rows 2..4 of a six-row batch, handed over as a slice — the whole query blob and offsets whose
+    first is not zero — equal the restatement on those rows, with the poison off and under both pattern families."""
+    from suggest_amd import _lib
+    queries, blob, offs, ids, scores, counts, ro = _slice_batch(shapes, ragged)
+    lo, hi = 2, 5
+    s0, s1 = int(ro[lo]), int(ro[hi])
+    assert offs[lo] != 0
+    q, i, s, c = queries[lo:hi], ids[s0:s1], scores[s0:s1], counts[lo:hi]
+    geo = dict(row_offs=(ro[lo:hi + 1] - ro[lo])) if ragged else dict(row=3)
+    d0, outside = ref.edit_rows(q, i, c, shapes["lines"], mode="osa", fold=True, **geo)
+    w_ids, w_sc, w_d, w_c = ref.rerank(i, s, d0, c, max_distance=ref.NONE, k_out=2, **geo)
+    assert outside == 0
+    host_geo = dict(row_offs=geo["row_offs"]) if ragged else {}
+    ids_in = i if ragged else i.reshape(-1, 3)
+    sc_in = s if ragged else s.reshape(-1, 3)
+    with _lib.poisoned(family):
+        _lib.poison_stats()
+        dist = shapes["dd"].edit_distances(None, ids_in, c, mode="osa", fold_case=True, blob=blob, offs=offs[lo:hi + 1], **host_geo)
+        st = _lib.poison_stats()
+        g_ids, g_sc, g_d, g_c = shapes["dd"].edit_rerank(None, ids_in, c, scores=sc_in, k_out=2, mode="osa", blob=blob, offs=offs[lo:hi + 1], **host_geo)
+    assert np.array_equal(dist.reshape(-1), d0)
+    assert np.array_equal(g_ids.reshape(-1), w_ids) and np.array_equal(g_d.reshape(-1), w_d) and np.array_equal(g_c, w_c)
+    assert np.array_equal(g_sc.reshape(-1).view(np.uint64), w_sc.view(np.uint64))
+    assert (st["out_ids"] >= i.size * 4) == (family != 0), st           # the distances are a result region of the shared path
+
+
+def test_rerank_above_the_staging_limit(torch, shapes):
+    """65 536 rows x 64 candidates — 64 distinct rows tiled 1 024 times, strings of 16 runes at most: with 8 + 4 + 4 + 4 bytes per slot
+    the call's block is 84 MB, above the 64 MiB a synchronous call stages, so ids, scores and counts go in and come back straight
+    from / to the caller's arrays.  The batch is handed over as a slice (a query in front of the blob, offsets whose first is not
+    zero): above the limit such offsets are rebased through the staging buffer alone.  Expected: the restatement's answer for the
+    64 rows, tiled."""
+    from suggest_amd.index import pack_strings
+    rng = np.random.default_rng(616)
+    pool = np.array([i for i in shp.short_ids(shapes) if len(ref.runes(shapes["lines"][i], True)) <= 16], dtype=np.uint32)
+    assert len(pool) >= 16
+    n, row, tiles = 64, 64, 1024
+    queries = [shp.query_of(int(rng.integers(0, 17)), seed=i) for i in range(n)]
+    ids = pool[rng.integers(0, len(pool), (n, row))].astype(np.uint32)
+    scores = -np.sort(-np.round(rng.random((n, row)), 1), axis=1)
+    counts = rng.integers(0, row + 1, n).astype(np.uint32)
+    d0, outside = ref.edit_rows(queries, ids, counts, shapes["lines"], row=row, mode="osa", fold=True)
+    w_ids, w_sc, w_d, w_c = ref.rerank(ids, scores, d0, counts, row=row, max_distance=3, k_out=10)
+    assert outside == 0 and n * tiles * row * 20 > 64 << 20
+    blob, offs = pack_strings([b"in front"] + queries * tiles)
+    assert offs[1] != 0
+    g_ids, g_sc, g_d, g_c = shapes["dd"].edit_rerank(None, np.tile(ids, (tiles, 1)), np.tile(counts, tiles), scores=np.tile(scores, (tiles, 1)),
+                                                     k_out=10, mode="osa", max_distance=3, blob=blob, offs=offs[1:])
+    assert np.array_equal(g_ids.reshape(tiles, -1), np.tile(w_ids, (tiles, 1)))
+    assert np.array_equal(g_d.reshape(tiles, -1), np.tile(w_d, (tiles, 1)))
+    assert np.array_equal(g_sc.reshape(tiles, -1).view(np.uint64), np.tile(w_sc.view(np.uint64), (tiles, 1)))
+    assert np.array_equal(g_c.reshape(tiles, -1), np.tile(w_c, (tiles, 1)))
+
+
 def test_an_id_outside_the_dictionary(torch, shapes):
     from suggest_amd import _lib
     n = len(shapes["lines"])

@@ -238,6 +238,49 @@ def test_poisoned_scratch_and_rows_change_nothing():
         assert np.array_equal(ref[1].view(np.uint64), got[1].view(np.uint64))
 
 
+def test_a_slice_of_an_id_array_and_scores_alone():
+    """score_word_ids on sentences 2..4 of a five-sentence id array, handed over as offsets whose first is not zero, equals rows
+    2..4 of the whole call bit for bit; score_text without `words` / `unknown` asked for gives the scores of the full call."""
+    from suggest_amd import LanguageModel, _lib
+    from suggest_amd.index import pack_strings
+    lm = LanguageModel(LM_DIR, 3)
+    V = len(lm)
+    lists = [[0, 1, 2], [UNK], [1, 1, 0, 2, V + 1, 0], [], [2, 0, 1, 1]]
+    ids = np.array([w for s in lists for w in s], dtype=np.uint32)
+    offs = _offs(lists)
+    whole = lm.score_word_ids_batch(ids, offs)
+    assert offs[2] != 0
+    part = lm.score_word_ids_batch(ids, offs[2:5 + 1])
+    assert np.array_equal(part.view(np.uint64), whole[2:5].view(np.uint64))
+    _assert_close(whole, np.array([_host_ids(lm, s) for s in lists]))
+    lines = [b"i am sam", b"", b"sam i am dont", b"I AM", b"qqzz sam"]
+    blob, o = pack_strings(lines)
+    blob, o = np.ascontiguousarray(blob, dtype=np.uint8), np.ascontiguousarray(o, dtype=np.uint64)
+    full = lm.score_text_batch(lines)
+    for want_words, want_unknown in ((False, False), (True, False), (False, True)):
+        s, w, u = np.full(len(lines), 7.0), np.full(len(lines), 7, dtype=np.uint32), np.full(len(lines), 7, dtype=np.uint32)
+        _lib.check(_lib.lib().sg_lm_score_text_batch(lm._h, 0, blob.ctypes.data, o.ctypes.data, len(lines), s.ctypes.data,
+                                                     w.ctypes.data if want_words else None, u.ctypes.data if want_unknown else None))
+        assert np.array_equal(s.view(np.uint64), full[0].view(np.uint64))
+        assert np.array_equal(w, full[1]) if want_words else np.all(w == 7)
+        assert np.array_equal(u, full[2]) if want_unknown else np.all(u == 7)
+
+
+def test_a_slice_of_an_id_array_above_the_staging_limit():
+    """17 M ids (68 MB, above the 64 MiB a synchronous call stages) behind three ids of another sentence, handed over with offsets
+    whose first is 3: served, and bit for bit the call on the same ids with offsets from zero."""
+    from suggest_amd import LanguageModel
+    lm = LanguageModel(LM_DIR, 3)
+    n, per = 1_000_000, 17
+    ids = np.random.RandomState(23).randint(0, len(lm) + 2, size=3 + n * per).astype(np.uint32)
+    offs = 3 + per * np.arange(n + 1, dtype=np.uint64)
+    assert n * per * 4 > 64 << 20
+    part = lm.score_word_ids_batch(ids, offs)
+    whole = lm.score_word_ids_batch(ids[3:], offs - np.uint64(3))
+    assert np.array_equal(part.view(np.uint64), whole.view(np.uint64))
+    _assert_close(part[:50], np.array([_host_ids(lm, ids[3 + i * per:3 + (i + 1) * per]) for i in range(50)]))
+
+
 def test_interleaved_with_predict_and_threads():
     from suggest_amd import LanguageModel, SpellChecker
     lm = LanguageModel(LM_DIR, 3)
