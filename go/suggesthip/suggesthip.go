@@ -1501,6 +1501,88 @@ func (i *Index) SuggestEdit(dict *DeviceDictionary, queries []string, similarity
 	return cands, distances, status, nil
 }
 
+// EditSearch searches the WHOLE dictionary by edit distance (sg_edit_search): every line within maxDistance (0 .. 32) edits of a
+// query, the k (1 .. 1024) nearest returned, ties by docID — no q-gram index proposes candidates, so nothing is missed.
+// ids[q][j] is at distances[q][j]; matches[q] is the number of lines within maxDistance (status[q] = SG_COUNT_TOO_LONG and no
+// row for a query of more than 64 runes).  The search structure (sg_edit_index) is built per call; a caller with many batches
+// keeps one through the C API.
+func (d *DeviceDictionary) EditSearch(queries []string, k int, maxDistance int, transpositions bool, noFold bool) (ids [][]uint32, distances [][]uint32, matches []uint64, status []uint32, err error) {
+	n := len(queries)
+	if n == 0 {
+		return nil, nil, nil, nil, nil
+	}
+	if k <= 0 || k > 1024 || maxDistance < 0 || maxDistance > C.SG_EDIT_SEARCH_MAX_DISTANCE {
+		return nil, nil, nil, nil, errors.New("EditSearch: k should be in 1 .. 1024, maxDistance in 0 .. 32")
+	}
+	var blob []byte
+	offs := make([]C.uint64_t, 1, n+1)
+	for _, q := range queries {
+		blob = append(blob, q...)
+		offs = append(offs, C.uint64_t(len(blob)))
+	}
+	var bp *C.uint8_t
+	if len(blob) > 0 {
+		bp = (*C.uint8_t)(unsafe.Pointer(&blob[0]))
+	}
+	bins := maxDistance + 1
+	cids := make([]C.uint32_t, n*k)
+	dist := make([]C.uint32_t, n*k)
+	counts := make([]C.uint32_t, n)
+	hist := make([]C.uint32_t, n*bins)
+	var cfg C.sg_edit_config
+	if transpositions {
+		cfg.mode = C.SG_EDIT_OSA
+	}
+	fold := C.int(1)
+	if noFold {
+		fold = 0
+	}
+	cfg.fold_case = C.int32_t(fold)
+	cfg.max_distance = C.uint32_t(maxDistance)
+	d.mu.RLock()
+	if d.closed {
+		d.mu.RUnlock()
+		return nil, nil, nil, nil, errClosed
+	}
+	C.sg_dictionary_retain(d.h)
+	d.mu.RUnlock()
+	defer func() { C.sg_dictionary_release(d.h); runtime.KeepAlive(d) }()
+	var ix *C.sg_edit_index
+	if err = ccall(func() C.int {
+		return C.sg_edit_index_create(d.h, fold, &ix)
+	}); err != nil {
+		return nil, nil, nil, nil, err
+	}
+	defer C.sg_edit_index_release(ix)
+	err = ccall(func() C.int {
+		return C.sg_edit_search(ix, &cfg, bp, &offs[0], C.uint32_t(n), C.uint32_t(k), &cids[0], &dist[0], &counts[0], &hist[0])
+	})
+	if err != nil {
+		return nil, nil, nil, nil, err
+	}
+	ids = make([][]uint32, n)
+	distances = make([][]uint32, n)
+	matches = make([]uint64, n)
+	status = make([]uint32, n)
+	for q := 0; q < n; q++ {
+		c := uint32(counts[q])
+		if c >= C.SG_COUNT_LM_ERROR { // an SG_COUNT_* flag: no row
+			status[q] = c
+			continue
+		}
+		for t := 0; t < bins; t++ {
+			matches[q] += uint64(hist[q*bins+t])
+		}
+		ids[q] = make([]uint32, c)
+		distances[q] = make([]uint32, c)
+		for j := 0; j < int(c); j++ {
+			ids[q][j] = uint32(cids[q*k+j])
+			distances[q][j] = uint32(dist[q*k+j])
+		}
+	}
+	return ids, distances, matches, status, nil
+}
+
 // StoreBinary writes the spellchecker's language model as the <name>.lm / <name>.cdb pair `lm build-lm` leaves behind
 // (StoreBinaryLM, pkg/lm/binary.go:18-57).  mph adds the minimal perfect hash RetrieveLMFromBinary reads after the model
 // (pkg/mph/mph.go): the file the reference's spellchecker service opens (sg_lm_store_binary_ex).

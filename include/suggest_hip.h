@@ -714,6 +714,46 @@ int sg_debug_edit_slice_bytes(uint64_t bytes);
  * one-word form with its Peq table for n_a <= 64, the blocked form over sorted (rune, position) pairs above. */
 int sg_debug_edit_bitvector(int mode, const uint32_t* a, uint32_t n_a, const uint32_t* b, uint32_t n_b, uint32_t* out);
 
+/* A complete search of a dictionary by edit distance: every string of the sg_dictionary within max_distance edits
+ * of the query, the k nearest returned — over the WHOLE dictionary, with no q-gram index and no candidates: nothing is missed.
+ * Distance semantics are exactly those above (runes, folding, both modes; nothing trimmed, wrapped or mapped through an alphabet).
+ *
+ * sg_edit_index is the search structure over one dictionary: immutable, reference-counted, it retains `dict`.  It holds two arrays
+ * of n_docs entries — in HBM, built by a kernel, for a device-resident dictionary; host vectors for a host-resident one:
+ * runes[d] (u32) the rune count of string d, and sig[d] (u64) the OR over its runes (folded, if fold_case) of bit
+ * (rune * 0x9E3779B1) >> 26 (a 32-bit product).  One insert, delete or substitute removes at most one rune and adds at most one, a
+ * transposition neither, so distance >= max(popcount(sigQ & ~sigD), popcount(sigD & ~sigQ)) and distance >= |runesQ - runesD|: a
+ * document that breaks either bound for max_distance is rejected without being decoded, and no other is.
+ *
+ * config: mode as above; fold_case must equal the index's; max_distance is a true bound here, 0 .. SG_EDIT_SEARCH_MAX_DISTANCE
+ * (0xFFFFFFFF and anything else above is an invalid argument).  k: 1 .. 1 024.  Queries as (blob, n_q + 1 u64 offsets).
+ * Out: ids[n_q * k], dist[n_q * k], counts[n_q] (all u32) and, unless null, hist[n_q * (max_distance + 1)] (u32): hist[i][t] = the
+ * number of dictionary strings at distance exactly t from query i — their sum is the number of matches.  Row i holds the
+ * min(k, that sum) nearest strings by (distance ascending, docID ascending); slots from the count on are zeroed.  A query of more
+ * than 64 runes comes back with counts[i] = SG_COUNT_TOO_LONG, its row and histogram zeroed (a limit of this version;
+ * sg_suggest_batch_edit remains the route for such queries); a query of 64 runes, of one, of none is answered — for the empty query
+ * the distance is the document's rune count.
+ * sg_edit_search_device: device pointers, asynchronous on `stream`, writes nothing of any handle, callable from any number of
+ * threads; its working memory is a block of the calling thread's per-stream scratch, bounded whatever the number of matches; a
+ * host-resident index is refused (unsupported).  sg_edit_search: host buffers; over a device index a host-buffer call like
+ * sg_suggest_batch (offsets may start anywhere), over a host-resident index a plain host loop that needs no GPU.
+ * Test hooks: sg_debug_edit_index_array reads one of the two arrays back raw (which 0: runes, 1: sig; out null: *out_bytes alone);
+ * sg_debug_edit_search_slices forces the number of docID slices the scan cuts the dictionary into (slice s = documents
+ * [s * ceil(n_docs / n), (s + 1) * ceil(n_docs / n)); 0: automatic); sg_debug_edit_search_bytes lowers the byte budget of the rows
+ * one chunk of queries may take (0: the default, 256 MiB), so that a batch is enqueued in several chunks. */
+#define SG_EDIT_SEARCH_MAX_DISTANCE 32u
+typedef struct sg_edit_index sg_edit_index;
+int sg_edit_index_create(sg_dictionary* dict, int fold_case, sg_edit_index** out);
+void sg_edit_index_retain(sg_edit_index* index);
+void sg_edit_index_release(sg_edit_index* index);
+int sg_edit_search_device(sg_edit_index* index, const sg_edit_config* config, const void* d_q_blob, const void* d_q_offs, uint32_t n_q, uint32_t k,
+                          void* d_ids, void* d_dist, void* d_counts, void* d_hist_or_null, void* stream);
+int sg_edit_search(sg_edit_index* index, const sg_edit_config* config, const uint8_t* q_utf8, const uint64_t* q_offs, uint32_t n_q, uint32_t k,
+                   uint32_t* ids, uint32_t* dist, uint32_t* counts, uint32_t* hist_or_null);
+int sg_debug_edit_index_array(sg_edit_index* index, uint32_t which, void* out, uint64_t cap_bytes, uint64_t* out_bytes);
+int sg_debug_edit_search_slices(uint32_t n);
+int sg_debug_edit_search_bytes(uint64_t bytes);
+
 /* Sets a tuning knob of the index, before or after its first upload: SG_LOG2_CNT, SG_T_FLOOR, SG_FILTER_LEVEL, SG_TIGHTEN, SG_ROOMY,
  * SG_ORDER, SG_PRETOK, SG_SPLIT_CHUNKS, SG_PARTS_CNT_BONUS; the pipeline's SG_PIPE, SG_PIPE_SUB, SG_PIPE_CAND_CAP, SG_PIPE_WIDE,
  * SG_PLAN2.  SG_PIPE_NW, SG_PIPE_LOG2_CNT and SG_PIPE_DT_BYTES freeze the stream workgroup's shape for every launch;

@@ -61,6 +61,7 @@ inline Metric OverlapMetric() { return {SG_OVERLAP, "overlap"}; }
 // ---------------------------------------------------------------------------------------------
 // dictionary — docID (uint32, dictionary order) -> word
 // ---------------------------------------------------------------------------------------------
+struct EditCandidate;   // (defined below, with EditDistance)
 namespace dictionary {
 using Key = uint32_t;
 using Value = std::string;
@@ -212,12 +213,24 @@ class DeviceDictionary : public Dictionary {
     Check(sg_edit_rows(h_, &cfg, (const uint8_t*)blob.data(), offs.data(), ids, counts, row_offs, (uint32_t)queries.size(), row, slots, dist.data()));
     return dist;
   }
+  // sg_edit_search: every string of the dictionary within max_distance (<= 32) edits of each query, the k (<= 1 024)
+  // nearest by (distance, docID) — over the whole dictionary, nothing is missed.  *matches (may be null): per query the number of
+  // strings within max_distance, 0xFFFFFFFD (SG_COUNT_TOO_LONG) for a query of more than 64 runes, whose row is empty.  The search
+  // structure (sg_edit_index) is made on first use, per fold_case, and kept.
+  std::vector<std::vector<EditCandidate>> EditSearch(const std::vector<std::string>& queries, int k, uint32_t max_distance, bool transpositions = false,
+                                                     bool fold_case = true, std::vector<uint64_t>* matches = nullptr) const;
 
  private:
   static void Check(int rc) {
     if (rc != SG_OK) throw Error(sg_last_error());
   }
   sg_dictionary* h_ = nullptr;
+  struct EditIndexes {
+    std::mutex mu;
+    sg_edit_index* ix[2] = {nullptr, nullptr};
+    ~EditIndexes() { sg_edit_index_release(ix[0]); sg_edit_index_release(ix[1]); }
+  };
+  mutable EditIndexes edit_;
 };
 }  // namespace dictionary
 
@@ -447,6 +460,32 @@ struct EditCandidate {
   double Score;
   uint32_t Distance;
 };
+
+inline std::vector<std::vector<EditCandidate>> dictionary::DeviceDictionary::EditSearch(const std::vector<std::string>& queries, int k, uint32_t max_distance,
+                                                                                        bool transpositions, bool fold_case,
+                                                                                        std::vector<uint64_t>* matches) const {
+  sg_edit_index* ix = nullptr;
+  {
+    std::lock_guard<std::mutex> lock(edit_.mu);
+    if (!edit_.ix[fold_case]) Check(sg_edit_index_create(h_, fold_case ? 1 : 0, &edit_.ix[fold_case]));
+    ix = edit_.ix[fold_case];
+  }
+  std::string blob;
+  std::vector<uint64_t> offs(1, 0);
+  for (auto& q : queries) { blob += q; offs.push_back(blob.size()); }
+  const sg_edit_config cfg{transpositions ? SG_EDIT_OSA : SG_EDIT_LEVENSHTEIN, fold_case ? 1 : 0, max_distance, 0u};
+  const size_t n = queries.size(), kk = k > 0 ? (size_t)k : 0, bins = (size_t)std::min<uint32_t>(max_distance, SG_EDIT_SEARCH_MAX_DISTANCE) + 1;
+  std::vector<uint32_t> ids(n * kk + 1), dist(n * kk + 1), counts(n + 1), hist(n * bins + 1);
+  Check(sg_edit_search(ix, &cfg, (const uint8_t*)blob.data(), offs.data(), (uint32_t)n, (uint32_t)kk, ids.data(), dist.data(), counts.data(), hist.data()));
+  std::vector<std::vector<EditCandidate>> out(n);
+  if (matches) matches->assign(n, 0);
+  for (size_t i = 0; i < n; i++) {
+    if (counts[i] == SG_COUNT_TOO_LONG) { if (matches) (*matches)[i] = SG_COUNT_TOO_LONG; continue; }
+    for (uint32_t j = 0; j < counts[i]; j++) out[i].push_back(EditCandidate{ids[i * kk + j], 0.0, dist[i * kk + j]});
+    if (matches) for (size_t t = 0; t < bins; t++) (*matches)[i] += hist[i * bins + t];
+  }
+  return out;
+}
 
 struct SearchConfig {  // search.go:10-15
   std::string query;

@@ -42,9 +42,13 @@ EXPORTS = [
     "sg_autocomplete_batch_strings",
     "sg_edit_rows_device", "sg_edit_rows", "sg_edit_rerank_device", "sg_edit_rerank", "sg_suggest_batch_edit", "sg_debug_edit_slice_bytes",
     "sg_debug_edit_bitvector",
+    "sg_edit_index_create", "sg_edit_index_retain", "sg_edit_index_release", "sg_edit_search_device", "sg_edit_search", "sg_debug_edit_index_array",
+    "sg_debug_edit_search_slices", "sg_debug_edit_search_bytes",
 ]
 SG_EDIT_LEVENSHTEIN = 0
 SG_EDIT_OSA = 1
+SG_EDIT_SEARCH_MAX_DISTANCE = 32
+SG_EDIT_SEARCH_MAX_K = 1024
 SG_EDIT_NONE = 0xFFFFFFFF          # the distance of a slot that holds no entry; max_distance: no bound
 SG_MAX_MIXED_CONFIGS = 256
 SG_MAX_SHARDS = 64
@@ -243,6 +247,14 @@ def lib():
     if hasattr(L, "sg_suggest_batch_edit"): L.sg_suggest_batch_edit.argtypes = [vp, vp, vp, u32, i32, dbl, u32, vp, ecp, u32, vp, vp, vp, vp]
     if hasattr(L, "sg_debug_edit_slice_bytes"): L.sg_debug_edit_slice_bytes.argtypes = [u64]
     if hasattr(L, "sg_debug_edit_bitvector"): L.sg_debug_edit_bitvector.argtypes = [i32, vp, u32, vp, u32, vp]
+    if hasattr(L, "sg_edit_index_create"): L.sg_edit_index_create.argtypes = [vp, i32, C.POINTER(vp)]
+    if hasattr(L, "sg_edit_index_retain"): L.sg_edit_index_retain.argtypes = [vp]; L.sg_edit_index_retain.restype = None
+    if hasattr(L, "sg_edit_index_release"): L.sg_edit_index_release.argtypes = [vp]; L.sg_edit_index_release.restype = None
+    if hasattr(L, "sg_edit_search_device"): L.sg_edit_search_device.argtypes = [vp, ecp, vp, vp, u32, u32, vp, vp, vp, vp, vp]
+    if hasattr(L, "sg_edit_search"): L.sg_edit_search.argtypes = [vp, ecp, vp, vp, u32, u32, vp, vp, vp, vp]
+    if hasattr(L, "sg_debug_edit_index_array"): L.sg_debug_edit_index_array.argtypes = [vp, u32, vp, u64, C.POINTER(u64)]
+    if hasattr(L, "sg_debug_edit_search_slices"): L.sg_debug_edit_search_slices.argtypes = [u32]
+    if hasattr(L, "sg_debug_edit_search_bytes"): L.sg_debug_edit_search_bytes.argtypes = [u64]
     _lib = L
     return L
 

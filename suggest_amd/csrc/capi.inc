@@ -63,8 +63,9 @@ struct GrowBlock {
 // groups' rows, around its launches.  The materialise step (dict_rows.inc) holds SCRATCH_DICT, its lengths and the scan's working
 // memory, until its gather launch is enqueued.  An edit-distance call (edit_rank.inc) holds SCRATCH_EDIT — the list of long rows, the
 // long kernel's regions, a sort's arrays, sg_suggest_batch_edit's candidate rows — around the search launch it may contain.
+// An edit search (edit_search.inc) holds SCRATCH_EDIT_SEARCH alone: a chunk's rows and, where the caller wants none, the histograms.
 enum ScratchTag { SCRATCH_ROWS = 0, SCRATCH_PREDICT = 1, SCRATCH_LONG_LIST = 2, SCRATCH_PRETOK = 3, SCRATCH_PIPE = 4, SCRATCH_LM_SCORE = 5, SCRATCH_SHARD = 6,
-                  SCRATCH_MIXED = 7, SCRATCH_MIXED_ROWS = 8, SCRATCH_DICT = 9, SCRATCH_EDIT = 10 };
+                  SCRATCH_MIXED = 7, SCRATCH_MIXED_ROWS = 8, SCRATCH_DICT = 9, SCRATCH_EDIT = 10, SCRATCH_EDIT_SEARCH = 11 };
 struct ScratchSlot { int device; hipStream_t stream; int tag; GrowBlock blk; bool held = false; };
 inline bool on_main_thread() { return (long)getpid() == (long)syscall(SYS_gettid); }
 // (a thread that ends hands its buffers back; the main thread's are left to process exit, when the HIP runtime may already

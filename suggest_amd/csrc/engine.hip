@@ -2979,3 +2979,4 @@ __global__ __launch_bounds__(64) void pairsort_test_kernel(const uint32_t* keys,
 #include "mixed_batch.inc"
 #include "dict_rows.inc"
 #include "edit_rank.inc"
+#include "edit_search.inc"

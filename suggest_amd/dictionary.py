@@ -196,9 +196,129 @@ class DeviceDictionary:
             _lib.check(_lib.lib().sg_edit_rerank_device(h, C.byref(config), d_q, d_q_offs, d_ids, d_scores, d_counts, d_row_offs, int(n_rows), int(row),
                                                         int(slots), int(k_out), d_dist, d_info, stream))
 
+    def edit_index(self, fold_case=True):
+        """sg_edit_index_create -> EditIndex: the search structure for a complete search of this dictionary by edit distance"""
+        return EditIndex(self, fold_case)
+
     def get(self, doc_id):
         """Dictionary.Get"""
         if not 0 <= int(doc_id) < self.n_docs:
             raise KeyError(doc_id)
         text, _ = self.rows(np.array([[doc_id]], dtype=np.uint32), np.array([1], dtype=np.uint32), text_cap=max(1, self.max_len))
         return text.tobytes()
+
+
+class EditIndex:
+    """sg_edit_index: a rune count and a 64-bit rune signature per string of a DeviceDictionary, and over them the
+    complete search by edit distance — every string within max_distance edits of a query, the k nearest returned, ties by docID.
+    Nothing is missed: no q-gram index proposes the candidates."""
+
+    def __init__(self, dictionary, fold_case=True):
+        self._hlock = threading.Lock()
+        self.dictionary = dictionary
+        self.fold_case = bool(fold_case)
+        h = C.c_void_p()
+        with dictionary._use() as dh:
+            _lib.check(_lib.lib().sg_edit_index_create(dh, 1 if fold_case else 0, C.byref(h)))
+        self._h = h
+        self.n_docs, self.device = dictionary.n_docs, dictionary.device
+
+    @contextlib.contextmanager
+    def _use(self):
+        L = _lib.lib()
+        with self._hlock:
+            h = self._h
+            if not h:
+                raise ValueError("edit index is closed")
+            L.sg_edit_index_retain(h)
+        try:
+            yield h
+        finally:
+            L.sg_edit_index_release(h)
+
+    def close(self):
+        lock = getattr(self, "_hlock", None)
+        if lock is None:
+            return
+        with lock:
+            h, self._h = getattr(self, "_h", None), None
+        if h:
+            _lib.lib().sg_edit_index_release(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def config(self, max_distance, transpositions=False):
+        return _lib.SgEditConfig(_lib.SG_EDIT_OSA if transpositions else _lib.SG_EDIT_LEVENSHTEIN, 1 if self.fold_case else 0, int(max_distance), 0)
+
+    def array(self, which):
+        """Test hook (sg_debug_edit_index_array): "runes" (u32 per string) or "sig" (u64 per string), as they lie in memory"""
+        sel, dt = {"runes": (0, np.uint32), "sig": (1, np.uint64)}[which]
+        n = C.c_uint64()
+        with self._use() as h:
+            _lib.check(_lib.lib().sg_debug_edit_index_array(h, sel, None, 0, C.byref(n)))
+            out = np.zeros(n.value // np.dtype(dt).itemsize, dtype=dt)
+            if out.size:
+                _lib.check(_lib.lib().sg_debug_edit_index_array(h, sel, out.ctypes.data, out.nbytes, C.byref(n)))
+        return out
+
+    def search(self, queries, k, max_distance, transpositions=False, blob=None, offs=None):
+        """sg_edit_search -> (ids [n_q, k], dist [n_q, k], counts [n_q], hist [n_q, max_distance + 1]), all u32.  Row i: the
+        min(k, hist[i].sum()) strings nearest to query i by (distance, docID); counts[i] = SG_COUNT_TOO_LONG for a query of more
+        than 64 runes.  hist[i][t]: the strings at distance exactly t."""
+        if blob is None:
+            blob, offs = pack_strings(queries)
+        blob = np.ascontiguousarray(blob, dtype=np.uint8)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        n_q, k = len(offs) - 1, int(k)
+        cfg = self.config(max_distance, transpositions)
+        ids = np.zeros((n_q, max(k, 0)), dtype=np.uint32)
+        dist = np.zeros((n_q, max(k, 0)), dtype=np.uint32)
+        counts = np.zeros(n_q, dtype=np.uint32)
+        hist = np.zeros((n_q, min(int(max_distance), _lib.SG_EDIT_SEARCH_MAX_DISTANCE) + 1), dtype=np.uint32)
+        with self._use() as h:
+            _lib.check(_lib.lib().sg_edit_search(h, C.byref(cfg), blob.ctypes.data if blob.size else None, offs.ctypes.data, n_q, k,
+                                                 ids.ctypes.data, dist.ctypes.data, counts.ctypes.data, hist.ctypes.data))
+        return ids, dist, counts, hist
+
+    def search_device(self, config, d_q, d_q_offs, n_q, k, d_ids, d_dist, d_counts, d_hist=None, stream=0):
+        """sg_edit_search_device: raw device pointers (torch tensors' data_ptr()), asynchronous on `stream`.  d_ids, d_dist: n_q * k
+        u32; d_counts: n_q u32; d_hist: n_q * (max_distance + 1) u32 or None."""
+        with self._use() as h:
+            _lib.check(_lib.lib().sg_edit_search_device(h, C.byref(config), d_q, d_q_offs, int(n_q), int(k), d_ids, d_dist, d_counts, d_hist, stream))
+
+    def search_strings(self, queries, k, max_distance, transpositions=False):
+        """The rows as strings -> (values: a list[bytes] per query, dist, counts, hist).  The search and the dictionary's
+        materialise step (sg_dictionary_rows_device) run back to back on one stream over device-resident rows; needs torch and a
+        device-resident dictionary."""
+        import torch
+        blob, offs = pack_strings(queries)
+        n_q, k = len(offs) - 1, int(k)
+        dev = torch.device("cuda", self.device)
+        bins = int(max_distance) + 1
+        slots = n_q * k
+        text_cap = max(1, slots * self.dictionary.max_len)
+
+        def on_dev(a, view):
+            return torch.from_numpy(np.ascontiguousarray(a).view(view).copy()).to(dev)
+        d_q = on_dev(blob if blob.size else np.zeros(1, dtype=np.uint8), np.uint8)
+        d_qo = on_dev(offs, np.int64)
+        d_ids, d_dist = torch.zeros(max(slots, 1), dtype=torch.int32, device=dev), torch.zeros(max(slots, 1), dtype=torch.int32, device=dev)
+        d_cnt, d_hist = torch.zeros(max(n_q, 1), dtype=torch.int32, device=dev), torch.zeros(max(n_q * bins, 1), dtype=torch.int32, device=dev)
+        d_text, d_to = torch.zeros(text_cap, dtype=torch.uint8, device=dev), torch.zeros(slots + 1, dtype=torch.int64, device=dev)
+        d_info = torch.zeros(2, dtype=torch.int64, device=dev)
+        st = torch.cuda.current_stream(dev)
+        st.synchronize()
+        self.search_device(self.config(max_distance, transpositions), d_q.data_ptr(), d_qo.data_ptr(), n_q, k, d_ids.data_ptr(), d_dist.data_ptr(),
+                           d_cnt.data_ptr(), d_hist.data_ptr(), stream=st.cuda_stream)
+        self.dictionary.rows_device(d_ids.data_ptr(), d_cnt.data_ptr(), None, n_q, k, slots, d_text.data_ptr(), text_cap, d_to.data_ptr(), d_info.data_ptr(),
+                                    stream=st.cuda_stream)
+        st.synchronize()
+        counts = d_cnt.cpu().numpy().view(np.uint32)[:n_q]
+        values = split_text(d_text.cpu().numpy(), d_to.cpu().numpy().view(np.uint64))
+        rows = [values[i * k:i * k + (0 if counts[i] >= 0xFFFFFFF0 else int(counts[i]))] for i in range(n_q)]
+        return (rows, d_dist.cpu().numpy().view(np.uint32)[:slots].reshape(n_q, k), counts,
+                d_hist.cpu().numpy().view(np.uint32)[:n_q * bins].reshape(n_q, bins))
